@@ -18,7 +18,14 @@ expansion/backup, then action sampling, re-rooting with fresh Dirichlet noise an
 step, all resident in HBM (alphazero-al_amd/src/selfplay.py).  Ranks hold independent game
 shards (weak scaling); the only collective is one all-reduce of the counters at the end.
 
-Output: ONE JSON line on rank 0.  `value` = positions/s of the whole job.  `roofline` is for
+Output: ONE JSON line on rank 0.  `value` = positions/s of the whole job, `ms_per_step` = milliseconds of one
+timed step.  A plain run measures that headline and nothing else: set-up, lead-in, warm-up, the `--steps` timed
+plies, the line.  `--dump-outputs DIR` then writes what the last timed ply handed its caller as DIR/<name>.npy
+(dump_outputs); the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds the figures that take work of their own: HIP event pairs around every 16th tree / evaluator launch
+of the timed region and the per-kernel figures drawn from them, a device-to-device copy, a synthetic
+convolution launch, the CPU baselines and the tree-only pair.  `roofline` is for
 the tree path's selection kernel - the path `north_star` asks an HBM roofline for; it is NOT the kernel
 with the largest share of a step (the evaluator's kernels are: `roofline_evaluator_kernels` carries all of
 them against both roofs): algorithmic bytes per launch (SURVEY.md
@@ -144,12 +151,20 @@ def parse():
                     help="split the games of a GPU into this many independent drivers, each on its own HIP stream and "
                          "host thread (selfplay.StreamedSelfPlay): one group's tree kernels run under another group's "
                          "evaluator kernels; 1 = one driver, one batch of games x vl_batch leaves per iteration")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tree-only", action="store_true", help="skip the tree-only pair (tree_only / cpu_baseline_tree_only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's games)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel timings and rooflines, the CPU "
+                         "baselines, the tree-only pair")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-tree-only", action="store_true", help="with --full: skip the tree-only pair (tree_only / cpu_baseline_tree_only)")
     ap.add_argument("--tree-only-steps", type=int, default=40)
     ap.add_argument("--cpu-games", type=int, default=256)
     ap.add_argument("--cpu-plies", type=int, default=6)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.lead_in < 0:
+        ap.error("--steps must be >= 1, --warmup and --lead-in >= 0")
+    return args
 
 
 def dump_positions(sp, n):
@@ -326,6 +341,228 @@ def conv_roofline(torch, fast, leaves, launches=20):
             "algorithmic bytes (profiles/r02_pmc_fetch_write_by_kernel.csv)"}
 
 
+def start_profiles(F, L, handles):
+    """--full: HIP event pairs around every PROFILE_EVERY-th selection / backup launch of each engine and every
+    PROFILE_EVERY-th forward call of the evaluator, kernel by kernel."""
+    import ctypes as C
+    from src.fast_net import glue
+    for h in handles:
+        F.check(L.az_mcts_profile(h, PROFILE_EVERY))      # every 16th selection / backup launch carries an event pair
+    G = glue()
+    G.az_nn_model_profile.argtypes = [C.c_int]
+    G.az_nn_model_profile(PROFILE_EVERY)                   # and every 16th forward call of the evaluator, kernel by kernel
+
+
+def read_profiles(F, L, handles):
+    """What start_profiles timed (milliseconds and launches; tree kernels summed over the engines), both profiles
+    switched off again."""
+    import ctypes as C
+    from src.fast_net import glue
+    G = glue()
+    G.az_nn_model_profile_read_kernels.argtypes = [C.POINTER(C.c_double * 4), C.POINTER(C.c_int64 * 4)]
+    ev_ms, ev_n = (C.c_double * 4)(), (C.c_int64 * 4)()
+    G.az_nn_model_profile_read_kernels(C.byref(ev_ms), C.byref(ev_n))
+    G.az_nn_model_profile(0)
+    ms = [0.0, 0.0]; nl = [0, 0]
+    for h in handles:
+        ms_h = (C.c_double * 2)(); nl_h = (C.c_int64 * 2)()
+        F.check(L.az_mcts_profile_read(h, C.byref(ms_h), C.byref(nl_h)))
+        F.check(L.az_mcts_profile(h, 0))
+        for i in range(2):
+            ms[i] += float(ms_h[i]); nl[i] += int(nl_h[i])
+    return {"tree_ms": ms, "tree_n": nl, "ev_ms": list(ev_ms), "ev_n": list(ev_n)}
+
+
+def dump_outputs(torch, sp, out_dir):
+    """What the timed path handed its caller after its last step, one row per game in slot order over the drivers:
+    the root visit counts of the ply it searched, the move it played, the position and result after that move
+    (bitboards, side to move, game over, winner), and the root statistics of the subtrees kept for the next ply
+    (az_mcts_dev_root_stats).  Integers are written as float64 (exact: a Connect4 bitboard uses 49 bits), the
+    engine's float32 statistics as float32; 8192 games come to about 3 MB."""
+    import numpy as np
+    from src import fused as F
+    L = F.lib()
+    sp.synchronize()
+    cols = {}
+    for part, st in zip(sp.parts, sp.streams):
+        with torch.cuda.stream(st):
+            stats = torch.empty((part.B, 6 + 8 * part.search.action_size), dtype=torch.float32, device=part.device)
+            F.check(L.az_mcts_dev_root_stats(part.h, stats.data_ptr(), F._stream()))
+            st.synchronize()
+        for name, t, dt in (("visit_counts", part.counts, np.float64), ("actions", part.actions, np.float64),
+                            ("bb_p1", part.bb_p1, np.float64), ("bb_p2", part.bb_p2, np.float64),
+                            ("turn", part.turn, np.float64), ("done", part.done, np.float64),
+                            ("winner", part.winner, np.float64), ("root_stats", stats, np.float32)):
+            cols.setdefault(name, []).append(t.cpu().numpy().astype(dt))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, parts in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.concatenate(parts))
+    log(f"outputs of the last timed step: {', '.join(sorted(cols))} -> {out_dir}")
+
+
+def full_figures(out, args, torch, sp, cnt, prof, elapsed, dev, world):
+    """--full, rank 0: the figures beside the headline, added to the line `out` - rooflines and kernel timings from
+    the event pairs of the timed region (`prof`, read_profiles) and the CPU baseline."""
+    from src import fused as F
+    L = F.lib()
+    handles = [part.h for part in sp.parts]
+    sel_ms, sel_n = float(prof["tree_ms"][0]), int(prof["tree_n"][0])
+    bp_ms, bp_n = float(prof["tree_ms"][1]), int(prof["tree_n"][1])
+    ev_ms, ev_n = prof["ev_ms"], prof["ev_n"]
+    sel_bytes = cnt["levels"] * SEL_BYTES_PER_LEVEL + cnt["sims"] * LEAF_STATE_BYTES
+    roofline = None
+    pair_ms = 0.0
+    if sel_n > 0 and sel_ms > 0:
+        # counters cover every launch of the timed region; events every PROFILE_EVERY-th of them
+        launches = max(cnt["select_launches"], 1)
+        per_launch_bytes = sel_bytes / launches
+        # An event pair brackets more than the kernel: the two records take time on the stream
+        # themselves.  That constant is measured here with empty pairs and taken off, which is
+        # what makes the figure agree with rocprofv3's kernel durations (profiles/README.md).
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(128)]
+        for i in range(0, 128, 2):
+            ev[i].record(); ev[i + 1].record()
+        torch.cuda.synchronize()
+        gaps = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(0, 128, 2))
+        pair_ms = gaps[len(gaps) // 2]
+        raw_ms = sel_ms / sel_n
+        avg_ms = max(raw_ms - pair_ms, raw_ms * 0.25)
+        achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
+        # HBM bytes per launch from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 passes,
+        # tools/collect_traffic.py): a stored measurement is only quoted for the configuration it was
+        # taken on - kernel, trees per launch, n_playout, K, streams, evaluator - otherwise null
+        traffic = None
+        sel_kernel = select_kernel_name(L, handles[0])
+        traffic_key = "%s|games=%d|n_playout=%d|K=%d|streams=%d|evaluator=%s|lead_in=%d" % (
+            sel_kernel, args.games, args.n_playout, args.vl_batch, args.streams, args.evaluator, args.lead_in)
+        tf = os.path.join(ROOT, "profiles", "traffic_select.json")
+        if os.path.exists(tf):
+            try:
+                traffic = json.load(open(tf)).get("by_config", {}).get(traffic_key, {}).get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        # achievable copy bandwidth on this box (SURVEY 8d asks for it beside the datasheet peak)
+        src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        dst.copy_(src)
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0.record()
+        for _ in range(5):
+            dst.copy_(src)
+        c1.record()
+        torch.cuda.synchronize()
+        copy_gbs = 5 * 2 * (1 << 30) / (c0.elapsed_time(c1) * 1e-3) / 1e9
+        del src, dst
+        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_key": traffic_key,
+                    "traffic_source": "profiles/traffic_select.json: PMC passes (FETCH_SIZE x 2 + WRITE_SIZE) taken on exactly this "
+                                      "configuration by tools/collect_traffic.py; null for any other" if traffic is not None else None,
+                    "kernel": sel_kernel, "avg_launch_us": round(avg_ms * 1e3, 2),
+                    "bound_note": "priced against the HBM roof as north_star asks for the tree walk; the counters say the kernel is "
+                                  "limited by vector-instruction issue (DESIGN.md section 3), and it is a few percent of a step - the "
+                                  "kernels that dominate a step are in roofline_evaluator_kernels",
+                    "avg_event_pair_us": round(raw_ms * 1e3, 2), "empty_event_pair_us": round(pair_ms * 1e3, 2),
+                    "launches_timed": sel_n, "algorithmic_bytes_per_launch": int(per_launch_bytes),
+                    "measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 6),
+                    "trees_per_launch": args.games // max(args.streams, 1), "concurrent_streams": args.streams}
+        if args.streams > 1:
+            roofline["note"] = ("%d drivers on separate streams: a launch covers %d trees and shares the chip with the "
+                                "other drivers' evaluator kernels while it runs, so its duration is not the kernel's "
+                                "isolated time (--streams 1: one launch over all trees, profiles/README.md)"
+                                % (args.streams, args.games // args.streams))
+    # (event pairs with the empty pair's cost taken off, as for the selection kernel: agrees with rocprofv3's durations)
+    out["backprop_kernel_avg_us"] = round(max(bp_ms / bp_n - pair_ms, bp_ms / bp_n * 0.25) * 1e3, 2) if bp_n else None
+    out["backprop_event_pair_us"] = round(bp_ms / bp_n * 1e3, 2) if bp_n else None
+    out["tree_kernels_share_of_step"] = round(((max(sel_ms / sel_n - pair_ms, 0.0) if sel_n else 0.0) * cnt["select_launches"] +
+                                               (max(bp_ms / bp_n - pair_ms, 0.0) if bp_n else 0.0) * cnt["backprop_launches"])
+                                              / (elapsed * 1e3) / max(args.streams, 1), 4)
+    out["roofline"] = roofline
+    fast = sp.parts[0].fused.fast
+    if args.evaluator == "cnn" and fast is not None and getattr(fast, "mfma_conv", False):
+        synth = conv_roofline(torch, fast, args.games * args.vl_batch // max(args.streams, 1))
+        if ev_n[1] > 0:
+            # measured on launches of the timed region: the evaluator sees the non-terminal leaves only
+            live = (cnt["sims"] - cnt["terminal"]) / max(cnt["select_launches"], 1)
+            raw_us = ev_ms[1] / ev_n[1] * 1e3
+            us = max(raw_us - (roofline["empty_event_pair_us"] if roofline else 0.0), raw_us * 0.25)
+            flops = 2.0 * 42 * 64 * 576 * live
+            ach = flops / (us * 1e-6) / 1e12
+            out["roofline_evaluator"] = {
+                "bound": "mfma", "kernel": "k_conv_block<64,norm,residual> (3 of the 6 evaluator launches, ~43 % of a step)",
+                "achieved": round(ach, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(ach / 2500.0, 4),
+                "avg_launch_us": round(us, 1), "launches_timed": int(ev_n[1]), "leaves_per_launch": round(live, 1),
+                "flops_per_launch": int(flops), "traffic": int(2 * live * 42 * 64 * 2),
+                "note": "HIP events around every %d-th first residual block inside the timed region (az_nn_model_profile), "
+                        "event-pair overhead removed; dense bf16 MFMA peak; the kernel's HBM traffic equals its algorithmic "
+                        "bytes (profiles/r02_pmc_fetch_write_by_kernel.csv)" % PROFILE_EVERY,
+                "synthetic_launch": {"achieved": synth["achieved"], "avg_launch_us": synth["avg_launch_us"],
+                                     "leaves": args.games * args.vl_batch // max(args.streams, 1),
+                                     "note": "same kernel on random activations after the run: slower, the clock follows the data"}}
+            # every kernel of the evaluator, same event pairs, same timed region.  FLOPs per leaf from the layer
+            # shapes (Network.py:27-93,96-141): stem 42 x 64 x 288 MACs, residual block 42 x 64 x 576, attention
+            # 42 x 196 x 64 (QKVG) + 2 x 4 x 42 x 42 x 16 (scores, PV) + 42 x 64 x 64 (out); the heads are
+            # pooling + 64-wide linears on a few vectors: memory traffic, not matrix work, bounds them.
+            act = 42 * 64 * 2                                  # one sample's bf16 activations
+            pair = roofline["empty_event_pair_us"] if roofline else 0.0
+            table = []
+            for idx, name, flops_leaf, bytes_leaf in (
+                    # the stem is a K = 18 (one k step of 32, table in a bf16 high and low part) GEMM on a 0/1 operand
+                    # built from two bitboards (nn_stem.hip): 24 + 8 bytes in, one sample's activations out
+                    ((0, "k_stem (embedding + stem convolution from the bitboards)", 2.0 * 2 * 48 * 64 * 32, 32 + act)
+                     if getattr(fast, "folded_stem", False) else
+                     (0, "k_conv_block<32,..,EMBED> (stem + embedding)", 2.0 * 42 * 64 * 288, 504 + act)),
+                    (1, "k_conv_block<64,norm,residual> (x3 per forward)", 2.0 * 42 * 64 * 576, 2 * act),
+                    (2, "k_attn_block", 2.0 * (42 * 196 * 64 + 2 * 4 * 42 * 42 * 16 + 42 * 64 * 64), 2 * act),
+                    (3, "k_heads", 2.0 * (42 * 64 + 9 * 64 * 64 + 4 * 64 * 64 + 64 * 46), act + 7 + 44)):
+                if ev_n[idx] <= 0:
+                    continue
+                raw = ev_ms[idx] / ev_n[idx] * 1e3
+                us_k = max(raw - pair, raw * 0.25)
+                tf_s = flops_leaf * live / (us_k * 1e-6) / 1e12
+                gb_s = bytes_leaf * live / (us_k * 1e-6) / 1e9
+                bound = "mfma" if tf_s / 2500.0 >= gb_s / HBM_PEAK_GBS else "hbm"
+                table.append({"kernel": name, "avg_launch_us": round(us_k, 1), "launches_timed": int(ev_n[idx]),
+                              "bound": bound,
+                              "achieved": round(tf_s if bound == "mfma" else gb_s, 1),
+                              "peak": 2500.0 if bound == "mfma" else HBM_PEAK_GBS,
+                              "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                              "frac": round(max(tf_s / 2500.0, gb_s / HBM_PEAK_GBS), 4),
+                              "frac_mfma": round(tf_s / 2500.0, 4), "frac_hbm": round(gb_s / HBM_PEAK_GBS, 4),
+                              "flops_per_launch": int(flops_leaf * live), "algorithmic_bytes_per_launch": int(bytes_leaf * live)})
+            out["roofline_evaluator_kernels"] = table
+        else:
+            out["roofline_evaluator"] = synth
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args, args.evaluator, dump_positions(sp, args.cpu_games))
+
+
+def tree_only_pair(out, args, torch, dev, rank):
+    """--full: the CPU baseline's pair with the network factored out - tree kernels only (integer-hash evaluator,
+    native on the GPU, numpy on the CPU): GPU search against the reference's search, nothing else in the way.  Runs
+    on an engine of its own, after the headline's engine is released."""
+    from src import fused as F
+    from src.hash_eval import HashEvaluator
+    from src.selfplay import StreamedSelfPlay
+    L = F.lib()
+    sp2 = StreamedSelfPlay(HashEvaluator(dev), args.games, streams=1, n_playout=args.n_playout,
+                           vl_batch=args.vl_batch, seed=rank)
+    sp2.step(args.lead_in + 1)
+    torch.cuda.synchronize()
+    before = sp2.read_totals()["positions"]
+    F.check(L.az_mcts_counters_reset(sp2.parts[0].h))
+    t1 = time.perf_counter()
+    sp2.step(args.tree_only_steps)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t1
+    c2 = sp2.engine_counters()
+    pos2 = sp2.read_totals()["positions"] - before
+    out["tree_only"] = {"value": round(pos2 / dt, 1), "unit": "positions/s", "steps": args.tree_only_steps,
+                        "ms_per_step": round(dt / args.tree_only_steps * 1e3, 3),
+                        "sims_per_s": round(c2["sims"] / dt, 1), "node_expansions_per_s": round(c2["expansions"] / dt, 1),
+                        "evaluator": "integer-hash evaluator (native, no network): selection + leaf preparation + backup + game logic"}
+    out["cpu_baseline_tree_only"] = cpu_baseline(args, "hash", dump_positions(sp2, max(args.cpu_games, 4096)))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -394,13 +631,8 @@ def main():
     torch.cuda.synchronize()
     for h in handles:
         F.check(L.az_mcts_counters_reset(h))
-        F.check(L.az_mcts_profile(h, PROFILE_EVERY))      # every 16th selection / backup launch carries an event pair
-    import ctypes as C
-    from src.fast_net import glue
-    G = glue()
-    G.az_nn_model_profile.argtypes = [C.c_int]
-    G.az_nn_model_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    G.az_nn_model_profile(PROFILE_EVERY)                   # and every 16th forward call of the evaluator, kernel by kernel
+    if args.full:
+        start_profiles(F, L, handles)
     t_before = sp.read_totals()
 
     if world > 1:
@@ -415,22 +647,13 @@ def main():
     elapsed = time.perf_counter() - t0
     log(f"timed region: {args.steps} steps in {elapsed:.2f} s")
 
-    G.az_nn_model_profile_read_kernels.argtypes = [C.POINTER(C.c_double * 4), C.POINTER(C.c_int64 * 4)]
-    ev_ms, ev_n = (C.c_double * 4)(), (C.c_int64 * 4)()
-    G.az_nn_model_profile_read_kernels(C.byref(ev_ms), C.byref(ev_n))
-    G.az_nn_model_profile(0)
-    conv_ms, conv_n = C.c_double(ev_ms[1]), C.c_int64(ev_n[1])
-    ms = [0.0, 0.0]; nl = [0, 0]
-    for h in handles:
-        ms_h = (C.c_double * 2)(); nl_h = (C.c_int64 * 2)()
-        F.check(L.az_mcts_profile_read(h, C.byref(ms_h), C.byref(nl_h)))
-        F.check(L.az_mcts_profile(h, 0))
-        for i in range(2):
-            ms[i] += float(ms_h[i]); nl[i] += int(nl_h[i])
+    prof = read_profiles(F, L, handles) if args.full else None
     cnt = sp.engine_counters()
     tot = sp.read_totals()
     positions = tot["positions"] - t_before["positions"]
     games = tot["games"] - t_before["games"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(torch, sp, args.dump_outputs)
 
     # one collective: sum the counters, max the time (xGMI, a few dozen bytes)
     from src.shard import reduce_counters
@@ -442,69 +665,6 @@ def main():
         sims_rank = max(cnt["sims"], 1)
         depth = cnt["levels"] / sims_rank
         xps = cnt["expansions"] / sims_rank
-        sel_ms, sel_n = float(ms[0]), int(nl[0])
-        bp_ms, bp_n = float(ms[1]), int(nl[1])
-        sel_bytes = cnt["levels"] * SEL_BYTES_PER_LEVEL + cnt["sims"] * LEAF_STATE_BYTES
-        roofline = None
-        pair_ms = 0.0
-        if sel_n > 0 and sel_ms > 0:
-            # counters cover every launch of the timed region; events every PROFILE_EVERY-th of them
-            launches = max(cnt["select_launches"], 1)
-            per_launch_bytes = sel_bytes / launches
-            # An event pair brackets more than the kernel: the two records take time on the stream
-            # themselves.  That constant is measured here with empty pairs and taken off, which is
-            # what makes the figure agree with rocprofv3's kernel durations (profiles/README.md).
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(128)]
-            for i in range(0, 128, 2):
-                ev[i].record(); ev[i + 1].record()
-            torch.cuda.synchronize()
-            gaps = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(0, 128, 2))
-            pair_ms = gaps[len(gaps) // 2]
-            raw_ms = sel_ms / sel_n
-            avg_ms = max(raw_ms - pair_ms, raw_ms * 0.25)
-            achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
-            # HBM bytes per launch from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 passes,
-            # tools/collect_traffic.py): a stored measurement is only quoted for the configuration it was
-            # taken on - kernel, trees per launch, n_playout, K, streams, evaluator - otherwise null
-            traffic = None
-            sel_kernel = select_kernel_name(L, handles[0])
-            traffic_key = "%s|games=%d|n_playout=%d|K=%d|streams=%d|evaluator=%s|lead_in=%d" % (
-                sel_kernel, args.games, args.n_playout, args.vl_batch, args.streams, args.evaluator, args.lead_in)
-            tf = os.path.join(ROOT, "profiles", "traffic_select.json")
-            if os.path.exists(tf):
-                try:
-                    traffic = json.load(open(tf)).get("by_config", {}).get(traffic_key, {}).get("hbm_bytes_per_launch")
-                except Exception:
-                    traffic = None
-            # achievable copy bandwidth on this box (SURVEY 8d asks for it beside the datasheet peak)
-            src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
-            dst = torch.empty_like(src)
-            dst.copy_(src)
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0.record()
-            for _ in range(5):
-                dst.copy_(src)
-            c1.record()
-            torch.cuda.synchronize()
-            copy_gbs = 5 * 2 * (1 << 30) / (c0.elapsed_time(c1) * 1e-3) / 1e9
-            del src, dst
-            roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_key": traffic_key,
-                        "traffic_source": "profiles/traffic_select.json: PMC passes (FETCH_SIZE x 2 + WRITE_SIZE) taken on exactly this "
-                                          "configuration by tools/collect_traffic.py; null for any other" if traffic is not None else None,
-                        "kernel": sel_kernel, "avg_launch_us": round(avg_ms * 1e3, 2),
-                        "bound_note": "priced against the HBM roof as north_star asks for the tree walk; the counters say the kernel is "
-                                      "limited by vector-instruction issue (DESIGN.md section 3), and it is a few percent of a step - the "
-                                      "kernels that dominate a step are in roofline_evaluator_kernels",
-                        "avg_event_pair_us": round(raw_ms * 1e3, 2), "empty_event_pair_us": round(pair_ms * 1e3, 2),
-                        "launches_timed": sel_n, "algorithmic_bytes_per_launch": int(per_launch_bytes),
-                        "measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 6),
-                        "trees_per_launch": args.games // max(args.streams, 1), "concurrent_streams": args.streams}
-            if args.streams > 1:
-                roofline["note"] = ("%d drivers on separate streams: a launch covers %d trees and shares the chip with the "
-                                    "other drivers' evaluator kernels while it runs, so its duration is not the kernel's "
-                                    "isolated time (--streams 1: one launch over all trees, profiles/README.md)"
-                                    % (args.streams, args.games // args.streams))
         out = {
             "metric": "self-play positions/sec (Connect4 n_playout=%d, batch=%d games/GPU, vl_batch=%d%s)"
                       % (args.n_playout, args.games, args.vl_batch, "" if args.evaluator == "cnn" else ", tree kernels only: integer-hash evaluator"),
@@ -524,100 +684,19 @@ def main():
             "sims_per_s": round(g_sims / t, 1), "node_expansions_per_s": round(g_exp / t, 1),
             "node_expansions_per_s_per_gpu": round(g_exp / t / world, 1),
             "games_finished": g_games, "mean_select_depth": round(depth, 3), "expansions_per_sim": round(xps, 3),
-            # (event pairs with the empty pair's cost taken off, as for the selection kernel: agrees with rocprofv3's durations)
-            "backprop_kernel_avg_us": round(max(bp_ms / bp_n - pair_ms, bp_ms / bp_n * 0.25) * 1e3, 2) if bp_n else None,
-            "backprop_event_pair_us": round(bp_ms / bp_n * 1e3, 2) if bp_n else None,
-            "tree_kernels_share_of_step": round(((max(sel_ms / sel_n - pair_ms, 0.0) if sel_n else 0.0) * cnt["select_launches"] +
-                                                 (max(bp_ms / bp_n - pair_ms, 0.0) if bp_n else 0.0) * cnt["backprop_launches"])
-                                                / (elapsed * 1e3) / max(args.streams, 1), 4),
-            "roofline": roofline,
         }
-        fast = sp.parts[0].fused.fast
-        if args.evaluator == "cnn" and fast is not None and getattr(fast, "mfma_conv", False):
-            synth = conv_roofline(torch, fast, args.games * args.vl_batch // max(args.streams, 1))
-            if conv_n.value > 0:
-                # measured on launches of the timed region: the evaluator sees the non-terminal leaves only
-                live = (cnt["sims"] - cnt["terminal"]) / max(cnt["select_launches"], 1)
-                raw_us = conv_ms.value / conv_n.value * 1e3
-                us = max(raw_us - (roofline["empty_event_pair_us"] if roofline else 0.0), raw_us * 0.25)
-                flops = 2.0 * 42 * 64 * 576 * live
-                ach = flops / (us * 1e-6) / 1e12
-                out["roofline_evaluator"] = {
-                    "bound": "mfma", "kernel": "k_conv_block<64,norm,residual> (3 of the 6 evaluator launches, ~43 % of a step)",
-                    "achieved": round(ach, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(ach / 2500.0, 4),
-                    "avg_launch_us": round(us, 1), "launches_timed": int(conv_n.value), "leaves_per_launch": round(live, 1),
-                    "flops_per_launch": int(flops), "traffic": int(2 * live * 42 * 64 * 2),
-                    "note": "HIP events around every %d-th first residual block inside the timed region (az_nn_model_profile), "
-                            "event-pair overhead removed; dense bf16 MFMA peak; the kernel's HBM traffic equals its algorithmic "
-                            "bytes (profiles/r02_pmc_fetch_write_by_kernel.csv)" % PROFILE_EVERY,
-                    "synthetic_launch": {"achieved": synth["achieved"], "avg_launch_us": synth["avg_launch_us"],
-                                         "leaves": args.games * args.vl_batch // max(args.streams, 1),
-                                         "note": "same kernel on random activations after the run: slower, the clock follows the data"}}
-                # every kernel of the evaluator, same event pairs, same timed region.  FLOPs per leaf from the layer
-                # shapes (Network.py:27-93,96-141): stem 42 x 64 x 288 MACs, residual block 42 x 64 x 576, attention
-                # 42 x 196 x 64 (QKVG) + 2 x 4 x 42 x 42 x 16 (scores, PV) + 42 x 64 x 64 (out); the heads are
-                # pooling + 64-wide linears on a few vectors: memory traffic, not matrix work, bounds them.
-                act = 42 * 64 * 2                                  # one sample's bf16 activations
-                pair = roofline["empty_event_pair_us"] if roofline else 0.0
-                table = []
-                for idx, name, flops_leaf, bytes_leaf in (
-                        # the stem is a K = 18 (one k step of 32, table in a bf16 high and low part) GEMM on a 0/1 operand
-                        # built from two bitboards (nn_stem.hip): 24 + 8 bytes in, one sample's activations out
-                        ((0, "k_stem (embedding + stem convolution from the bitboards)", 2.0 * 2 * 48 * 64 * 32, 32 + act)
-                         if getattr(fast, "folded_stem", False) else
-                         (0, "k_conv_block<32,..,EMBED> (stem + embedding)", 2.0 * 42 * 64 * 288, 504 + act)),
-                        (1, "k_conv_block<64,norm,residual> (x3 per forward)", 2.0 * 42 * 64 * 576, 2 * act),
-                        (2, "k_attn_block", 2.0 * (42 * 196 * 64 + 2 * 4 * 42 * 42 * 16 + 42 * 64 * 64), 2 * act),
-                        (3, "k_heads", 2.0 * (42 * 64 + 9 * 64 * 64 + 4 * 64 * 64 + 64 * 46), act + 7 + 44)):
-                    if ev_n[idx] <= 0:
-                        continue
-                    raw = ev_ms[idx] / ev_n[idx] * 1e3
-                    us_k = max(raw - pair, raw * 0.25)
-                    tf_s = flops_leaf * live / (us_k * 1e-6) / 1e12
-                    gb_s = bytes_leaf * live / (us_k * 1e-6) / 1e9
-                    bound = "mfma" if tf_s / 2500.0 >= gb_s / HBM_PEAK_GBS else "hbm"
-                    table.append({"kernel": name, "avg_launch_us": round(us_k, 1), "launches_timed": int(ev_n[idx]),
-                                  "bound": bound,
-                                  "achieved": round(tf_s if bound == "mfma" else gb_s, 1),
-                                  "peak": 2500.0 if bound == "mfma" else HBM_PEAK_GBS,
-                                  "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-                                  "frac": round(max(tf_s / 2500.0, gb_s / HBM_PEAK_GBS), 4),
-                                  "frac_mfma": round(tf_s / 2500.0, 4), "frac_hbm": round(gb_s / HBM_PEAK_GBS, 4),
-                                  "flops_per_launch": int(flops_leaf * live), "algorithmic_bytes_per_launch": int(bytes_leaf * live)})
-                out["roofline_evaluator_kernels"] = table
-            else:
-                out["roofline_evaluator"] = synth
         if args.table:
             st = sp.table_stats()                        # whole run, warm-up included
             out["config"]["workload"] += ", transposition table 2^%d entries" % args.table
             out["transposition_table"] = {"entries": 1 << args.table, "lookups": st["lookups"], "hits": st["hits"],
                                           "hit_rate": round(st["hit_rate"], 4), "replaced": st["replaced"]}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args, args.evaluator, dump_positions(sp, args.cpu_games))
-            if args.evaluator == "cnn" and not args.no_tree_only:
-                # the same pair with the network factored out: tree kernels only (integer-hash evaluator, native on
-                # the GPU, numpy on the CPU) - GPU search against the reference's search, nothing else in the way
+        if args.full:
+            full_figures(out, args, torch, sp, cnt, prof, elapsed, dev, world)
+            if world == 1 and not args.no_cpu_baseline and args.evaluator == "cnn" and not args.no_tree_only:
                 sp.close()
-                del sp, handles
+                del sp, handles                          # the headline's engine gives its memory back first
                 torch.cuda.empty_cache()
-                from src.hash_eval import HashEvaluator
-                sp2 = StreamedSelfPlay(HashEvaluator(dev), args.games, streams=1, n_playout=args.n_playout,
-                                       vl_batch=args.vl_batch, seed=rank)
-                sp2.step(args.lead_in + 1)
-                torch.cuda.synchronize()
-                before = sp2.read_totals()["positions"]
-                F.check(L.az_mcts_counters_reset(sp2.parts[0].h))
-                t1 = time.perf_counter()
-                sp2.step(args.tree_only_steps)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t1
-                c2 = sp2.engine_counters()
-                pos2 = sp2.read_totals()["positions"] - before
-                out["tree_only"] = {"value": round(pos2 / dt, 1), "unit": "positions/s", "steps": args.tree_only_steps,
-                                    "ms_per_step": round(dt / args.tree_only_steps * 1e3, 3),
-                                    "sims_per_s": round(c2["sims"] / dt, 1), "node_expansions_per_s": round(c2["expansions"] / dt, 1),
-                                    "evaluator": "integer-hash evaluator (native, no network): selection + leaf preparation + backup + game logic"}
-                out["cpu_baseline_tree_only"] = cpu_baseline(args, "hash", dump_positions(sp2, max(args.cpu_games, 4096)))
+                tree_only_pair(out, args, torch, dev, rank)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -408,7 +408,15 @@ def gen_g13():
     p, w, u = net.predict(planes, masks)
     save("g13_othello_network", planes=planes.astype(np.int8), masks=masks.astype(np.uint8), logp=lp.numpy(), logv=lv.numpy(),
          aux=aux.numpy(), probs=p, wdl=w, utility=u)
-    save("g13_othello_weights", **{k: v.numpy() for k, v in net.state_dict().items()})
+    # in two files, split at half the bytes: no committed file may exceed 1 MiB (test_oracle_golden.load_split)
+    sd = {k: v.numpy() for k, v in net.state_dict().items()}
+    half, first, acc = sum(a.nbytes for a in sd.values()) / 2, {}, 0
+    for k, a in sd.items():
+        if first and acc + a.nbytes > half:
+            break
+        first[k] = a; acc += a.nbytes
+    save("g13_othello_weights", **first)
+    save("g13_othello_weights_2", **{k: a for k, a in sd.items() if k not in first})
 
 
 def gen_gomoku():

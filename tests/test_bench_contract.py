@@ -23,9 +23,19 @@ def test_defaults_are_baseline_config_1(monkeypatch):
     a = b.parse()
     assert (a.gpus, a.games, a.n_playout, a.vl_batch, a.streams, a.evaluator, a.table) == (1, 8192, 200, 4, 1, "cnn", 0)
     assert a.steps > 0 and a.warmup >= 0 and not a.no_cpu_baseline
+    assert not a.full and a.dump_outputs is None, "a plain run measures the headline only and writes nothing"
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "1"])
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 1)
+
+
+def test_steps_must_be_at_least_one(monkeypatch):
+    """`--steps` is the number of timed steps `ms_per_step` divides by: zero is refused, not measured."""
+    import pytest
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
 
 
 def test_select_kernel_name_follows_the_variant(monkeypatch):

@@ -1,6 +1,7 @@
 """bench.py run for real on the GPU box: the one-rank line carries the contract's fields with
-consistent numbers, and the multi-rank path (one process per shard, counters reduced once at the
-end) is rehearsed with two ranks on one GPU over gloo - RCCL cannot open one device twice; the
+consistent numbers (a plain run the headline, `--full` the rooflines and the CPU baseline as well), the
+outputs of the last timed step are written on request, and the multi-rank path (one process per shard,
+counters reduced once at the end) is rehearsed with two ranks on one GPU over gloo - RCCL cannot open one device twice; the
 reduction code is the same call with another backend (src/shard.py)."""
 import json
 import os
@@ -31,7 +32,7 @@ SMALL = ["--games", "1024", "--steps", "3", "--warmup", "1", "--lead-in", "4"]
 
 
 def test_one_rank_line_has_the_contract_fields():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-games", "8", "--cpu-plies", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--cpu-games", "8", "--cpu-plies", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _last_json(r.stdout)
@@ -55,6 +56,37 @@ def test_one_rank_line_has_the_contract_fields():
     assert {"k_conv_block", "k_attn_block", "k_heads"} <= kinds
     for e in j["roofline_evaluator_kernels"]:
         assert 0 < e["frac"] < 1 and e["bound"] in ("mfma", "hbm") and e["launches_timed"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes work of its own; --dump-outputs writes
+    the last timed step's per-game results as float .npy files, the same for every run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _last_json(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+            assert k in j, k
+        assert j["steps"] == 3 and j["unit"] == "positions/s" and j["higher_is_better"] is True
+        assert abs(j["value"] - 1024 * 3 / (j["ms_per_step"] * 3 * 1e-3)) / j["value"] < 1e-3
+        for k in ("roofline", "roofline_evaluator", "roofline_evaluator_kernels", "cpu_baseline", "tree_only",
+                  "cpu_baseline_tree_only", "backprop_kernel_avg_us"):
+            assert k not in j, k
+        d = {f.name[:-4]: np.load(out / f.name) for f in out.iterdir()}
+        assert set(d) == {"visit_counts", "actions", "bb_p1", "bb_p2", "turn", "done", "winner", "root_stats"}
+        assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+        assert sum(a.nbytes for a in d.values()) <= 64 << 20
+        assert d["visit_counts"].shape == (1024, 7) and d["root_stats"].shape == (1024, 6 + 8 * 7)
+        acts = d["actions"].astype(np.int64)
+        assert d["actions"].shape == (1024,) and ((acts >= 0) & (acts < 7)).all()
+        assert (d["visit_counts"][np.arange(1024), acts] > 0).all(), "a move is drawn from the visited ones"
+        dumps.append(d)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_two_rank_rehearsal_reduces_the_counters():

@@ -7,15 +7,14 @@
 * host logic of src/MCTS_cpp.py (wrapper loop, LRU transposition path) against golden set G6,
   with the plain-C oracle monkeypatched in as the native backend - test-only, the product
   has no such switch;
-* the reference's own unmodified player.py / game.py running on top of our modules (G8),
-  only where /root/reference exists (it never travels to the GPU box).
+* tests/harness.py, the restatement of the reference's self-play harness, on top of our modules
+  against golden set G8, which the reference's own player.py / game.py recorded.
 """
 import ctypes as C
 import os
 import pickle
 import re
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -26,7 +25,6 @@ from oracle import oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "alphazero-al_amd")
 G = os.path.join(ROOT, "tests", "golden")
-REF = "/root/reference"
 
 
 def load(name):
@@ -266,46 +264,7 @@ def test_wrapper_vl_cleanup_on_evaluator_failure(built, monkeypatch):
     assert np.array_equal(before, np.array(w2.mcts.get_all_root_stats()))
 
 
-# ------------------------------------------------------------------ reference callers on our modules (G8)
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference checkout not present")
-def test_reference_selfplay_harness_g8(built, monkeypatch):
-    """Game.batch_self_play + AlphaZeroPlayer (reference python, unmodified, imported from
-    /root/reference) on top of OUR src.MCTS_cpp / src.env_cpp; native backend = oracle here."""
-    numba = types.ModuleType("numba")
-    numba.njit = lambda *a, **k: (lambda f: f)
-    monkeypatch.setitem(sys.modules, "numba", numba)
-    monkeypatch.syspath_prepend(REF)
-    monkeypatch.syspath_prepend(PKG)          # ours first: shadows MCTS_cpp / mcts_cpp / env_cpp
-    from src import MCTS_cpp
-    assert MCTS_cpp.__file__.startswith(PKG)
-    monkeypatch.setitem(MCTS_cpp._BACKENDS, "Connect4", _OracleBackend)
-    from src.env_cpp.connect4 import Env
-    from src.game import Game
-    from src.player import AlphaZeroPlayer
-    import src.player as ref_player
-    assert ref_player.__file__.startswith(REF)
-
-    g = load("g8_selfplay")
-    pv = S.HashPV()
-    np.random.seed(11)
-    player = AlphaZeroPlayer(pv, n_envs=8, c_init=1.4, c_base=160, n_playout=32, alpha=0.3,
-                             is_selfplay=1, noise_epsilon=0.25, fpu_reduction=0.2,
-                             use_symmetry=True, mlh_slope=0.1, mlh_cap=0.2, vl_batch=4)
-    player.mcts.seed(21)
-    data = Game(Env()).batch_self_play(player, 8, temperature=1.0, temp_decay_moves=6,
-                                       temp_endgame=0, td_steps=2)
-    for i, (winner, play) in enumerate(data):
-        assert winner == int(g[f"g{i}_winner"][0])
-        for j, nm in enumerate(("state", "prob", "z", "steps", "aux", "root_wdl", "mask", "fut")):
-            got = np.array([np.asarray(t[j]) for t in play])
-            ref = g[f"g{i}_{nm}"]
-            assert got.shape == ref.shape, (i, nm)
-            if ref.dtype.kind == "f":
-                assert np.array_equal(bits(got), bits(ref)), (i, nm)
-            else:
-                assert np.array_equal(got, ref), (i, nm)
-
+# ------------------------------------------------------------------ the reference's self-play harness on our modules (G8)
 
 def test_restated_selfplay_harness_g8(built, monkeypatch):
     """tests/harness.py - the restatement of Game.batch_self_play + get_batch_action that the GPU suite
@@ -406,9 +365,10 @@ def test_othello_network_port_matches_reference_outputs_g13(built):
     the CPU): its state dict loads strictly, forward and predict agree to float rounding."""
     import torch
     from src.az_net import OthelloNet, load_reference_weights
-    g, w = load("g13_othello_network"), load("g13_othello_weights")
+    from test_oracle_golden import load_split
+    g = load("g13_othello_network")
     net = OthelloNet(h_dim=32, num_res_blocks=2)
-    load_reference_weights(net, {k: w[k] for k in w.files})
+    load_reference_weights(net, load_split("g13_othello_weights"))
     planes = g["planes"].astype(np.float32)
     masks = g["masks"].astype(bool)
     with torch.no_grad():

@@ -12,7 +12,7 @@ import pytest
 
 import scenarios as S
 from oracle import oracle as O
-from test_oracle_golden import bits, load
+from test_oracle_golden import bits, load, load_split
 
 pytestmark = pytest.mark.gpu
 
@@ -961,9 +961,8 @@ def test_fused_othello_with_network(env):
     fixture G13 weights) as a torch module under autocast, fused path vs host path - same simulation
     budget, near-equal root Q, mostly equal best moves - and the self-play driver on top of it."""
     torch = env["torch"]
-    w13 = load("g13_othello_weights")
     net = env["N"].OthelloNet(h_dim=32, num_res_blocks=2, device="cuda")
-    env["N"].load_reference_weights(net, {k: w13[k] for k in w13.files})
+    env["N"].load_reference_weights(net, load_split("g13_othello_weights"))
     rng = np.random.default_rng(3)
     boards, turns = S.ot_openings(rng, 96, 20, 0)
     res = []

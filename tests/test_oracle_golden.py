@@ -21,6 +21,15 @@ def load(name):
     return np.load(os.path.join(G, name + ".npz"))
 
 
+def load_split(name):
+    """A fixture kept as name.npz + name_2.npz (no committed file over 1 MiB), as one dict of arrays."""
+    out = {}
+    for part in (name, name + "_2"):
+        z = load(part)
+        out.update({k: z[k] for k in z.files})
+    return out
+
+
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 

@@ -1,6 +1,6 @@
-// nn_model.hip - the leaf evaluator as ONE C call: the six launches of the inference twin
-// (stem with the embedding, residual blocks, gated attention, both heads; Network.py:144-288 of
-// the reference's Connect4 network) issued from native code on the caller's stream.
+// nn_model.hip - the leaf evaluator as ONE C call: the launches of the inference twin (stem with the
+// embedding, residual blocks, gated attention with both heads in one kernel; Network.py:144-288 of the
+// reference's Connect4 network) issued from native code on the caller's stream.
 //
 // The object holds POINTERS to the caller's weight arrays (bf16, the layouts az_nn.h documents
 // for each kernel) and nothing else: it is immutable after creation, so any number of host
@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -17,6 +19,7 @@
 
 struct az_nn_model {
     int kind = AZ_NN_KIND_CONNECT4_CNN;
+    bool attn_heads_fused = true;        // az_nn_attn_heads in place of az_nn_attn_block + az_nn_heads
     az_nn_model_weights w{};
     az_nn_othello_weights ow{};
 };
@@ -178,6 +181,9 @@ int az_nn_model_create(const az_nn_model_weights *w, az_nn_model **out)
     auto *m = new (std::nothrow) az_nn_model();
     if (m == nullptr) return 1;
     m->w = *w;
+    // AZ_ATTN_HEADS_FUSED=0: the attention block and the heads as two launches (A/B of the fused kernel in one process)
+    const char *fused = getenv("AZ_ATTN_HEADS_FUSED");
+    m->attn_heads_fused = fused == nullptr || strcmp(fused, "0") != 0;
     *out = m;
     return 0;
 }
@@ -338,6 +344,11 @@ static int forward_impl(const az_nn_model *m, const float *features, const az_nn
         if (i == 0) end(AZ_NN_PROFILE_CONV);
         char *t = a; a = b; b = t;
     }
+    // a call that carries event pairs runs the attention block and the heads as two launches, so that the ATTN and
+    // HEADS rings keep timing the kernels they are named after (the fused kernel has no split to time)
+    if (rc == 0 && m->attn_heads_fused && !timed)
+        return az_nn_attn_heads(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, &w.heads, mask, probs, wdl, moves_left, batch,
+                                w.eps, rows, n_rows, stream);
     if (rc == 0) {
         begin(AZ_NN_PROFILE_ATTN);
         rc = az_nn_attn_block(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, b, batch, w.eps, n_rows, stream);

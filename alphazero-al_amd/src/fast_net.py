@@ -47,6 +47,8 @@ def glue():
             L.az_nn_conv_block2.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp, vp]
             L.az_nn_attn_block.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp]
             L.az_nn_heads.argtypes = [vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp, vp, vp]
+            L.az_nn_attn_heads.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp,
+                                           vp, vp]
             L.az_nn_stem_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
             L.az_nn_stem_folded.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
             L.az_nn_model_create.argtypes = [C.POINTER(ModelWeights), C.POINTER(vp)]
@@ -204,6 +206,9 @@ class FastConnect4Net(torch.nn.Module):
         self.hip = (self.device.type == "cuda" and dtype == torch.bfloat16 and self.embed_dim == 32
                     and self.h_dim == 64 and heads == 4 and glue() is not None)
         self.mfma_conv = self.mfma_attn = self.fused_stem = self.fused_heads = self.hip
+        # predict_device: attention block and heads as one kernel (az_nn_attn_heads), as the native model object runs
+        # them; AZ_ATTN_HEADS_FUSED=0 (read here, and by az_nn_model_create): the two launches
+        self.attn_heads_fused = self.hip and os.environ.get("AZ_ATTN_HEADS_FUSED", "1") != "0"
         self._heads_w = None
         if self.fused_heads:
             hw = HeadsWeights()
@@ -291,11 +296,10 @@ class FastConnect4Net(torch.nn.Module):
         rows of `out` = (probs, wdl, ml) are written; the cost follows n_rows, not B."""
         if rows is not None:
             assert self.supports_compact and out is not None and n_rows is not None
-            t, bsz, L, s = self._body_hip(x, rows, n_rows)
+            t, bsz, L, s = self._body_hip(x, rows, n_rows, attention=not self.attn_heads_fused)
             probs, wdl, ml = out
             m = action_mask.contiguous()
-            L.az_nn_heads(t.data_ptr(), C.byref(self._heads_w), m.data_ptr(), probs.data_ptr(), wdl.data_ptr(),
-                          ml.data_ptr(), bsz, 1e-5, rows.data_ptr(), n_rows.data_ptr(), s)
+            self._heads_launch(t, m, probs, wdl, ml, bsz, rows.data_ptr(), n_rows.data_ptr(), L, s)
             self._keep_mask = m
             return probs, wdl, ml
         if not (self.hip and x.is_cuda):
@@ -304,7 +308,7 @@ class FastConnect4Net(torch.nn.Module):
         if not self.fused_heads:
             lp, v, st = self._forward_hip(x, action_mask)
             return lp.exp(), v.exp(), st * float(self.aux_target_offset)
-        t, bsz, L, s = self._body_hip(x)
+        t, bsz, L, s = self._body_hip(x, attention=not self.attn_heads_fused)
         probs = torch.empty((bsz, COLS), dtype=torch.float32, device=self.device)
         wdl = torch.empty((bsz, 3), dtype=torch.float32, device=self.device)
         ml = torch.empty((bsz,), dtype=torch.float32, device=self.device)
@@ -312,10 +316,20 @@ class FastConnect4Net(torch.nn.Module):
         if action_mask is not None:
             m = action_mask if action_mask.dtype in (torch.uint8, torch.bool) else action_mask.to(torch.bool)
             m = m.contiguous()
-        L.az_nn_heads(t.data_ptr(), C.byref(self._heads_w), None if m is None else m.data_ptr(), probs.data_ptr(),
-                      wdl.data_ptr(), ml.data_ptr(), bsz, 1e-5, None, None, s)
+        self._heads_launch(t, m, probs, wdl, ml, bsz, None, None, L, s)
         self._keep_mask = m
         return probs, wdl, ml
+
+    def _heads_launch(self, t, m, probs, wdl, ml, bsz, rows_ptr, n_rows_ptr, L, s):
+        """the heads on the final tokens t, or (attn_heads_fused) attention + heads on the block's input t"""
+        mp = None if m is None else m.data_ptr()
+        if self.attn_heads_fused:
+            L.az_nn_attn_heads(t.data_ptr(), self.pre_w.data_ptr(), self.qkvg_w.data_ptr(), self.qn_w.data_ptr(),
+                               self.kn_w.data_ptr(), self.o_w.data_ptr(), C.byref(self._heads_w), mp, probs.data_ptr(),
+                               wdl.data_ptr(), ml.data_ptr(), bsz, 1e-5, rows_ptr, n_rows_ptr, s)
+        else:
+            L.az_nn_heads(t.data_ptr(), C.byref(self._heads_w), mp, probs.data_ptr(), wdl.data_ptr(), ml.data_ptr(), bsz,
+                          1e-5, rows_ptr, n_rows_ptr, s)
 
     @torch.no_grad()
     def _forward_hip(self, x, action_mask):
@@ -323,8 +337,8 @@ class FastConnect4Net(torch.nn.Module):
         return self._heads_hip(t, action_mask, bsz, L, s)
 
     @torch.no_grad()
-    def _body_hip(self, x, rows=None, n_rows=None):
-        """embedding, stem, residual blocks and attention on the MFMA kernels -> final tokens
+    def _body_hip(self, x, rows=None, n_rows=None, attention=True):
+        """embedding, stem, residual blocks and (attention=True) attention on the MFMA kernels -> final tokens
         (of the compact batch when rows / n_rows are given)"""
         L = glue()
         gp = None if rows is None else rows.data_ptr()
@@ -347,6 +361,8 @@ class FastConnect4Net(torch.nn.Module):
                                getattr(self, g).data_ptr(), getattr(self, beta).data_ptr(), 1, t2.data_ptr(),
                                bsz, 1e-5, np_, s)
             t = t2
+        if not attention:
+            return t, bsz, L, s
         t2 = torch.empty_like(t)
         L.az_nn_attn_block(t.data_ptr(), self.pre_w.data_ptr(), self.qkvg_w.data_ptr(), self.qn_w.data_ptr(),
                            self.kn_w.data_ptr(), self.o_w.data_ptr(), t2.data_ptr(), bsz, 1e-5, np_, s)

@@ -134,10 +134,19 @@ typedef struct az_nn_heads_weights {
 int az_nn_heads(const void *tokens, const az_nn_heads_weights *w, const uint8_t *mask, float *probs, float *wdl,
                 float *moves_left, int64_t batch, float eps, const int32_t *scatter, const int64_t *batch_dev,
                 void *stream);
+/* az_nn_attn_block followed by az_nn_heads as ONE kernel (nn_attn_heads.hip): the residual stream x (batch, 42, 64)
+ * and the weights of both, as those two take them, in; probs, wdl, moves_left out, with mask / scatter / batch_dev as
+ * az_nn_heads reads them.  The block's output stays on chip (no token tensor is written); the rounding points are
+ * those of the two kernels, so results differ from them only through f32 summation order. */
+int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w, const void *k_norm_w,
+                     const void *o_w, const az_nn_heads_weights *w, const uint8_t *mask, float *probs, float *wdl,
+                     float *moves_left, int64_t batch, float eps, const int32_t *scatter, const int64_t *batch_dev,
+                     void *stream);
 
 /* The whole evaluator as one call (nn_model.hip): az_nn_stem_embed, n_blocks x az_nn_conv_block
- * (64 -> 64, normalised, residual), az_nn_attn_block, az_nn_heads on `stream`, issued from native
- * code - what alphazero-al_amd/src/fast_net.py does per call from Python.  The object keeps the
+ * (64 -> 64, normalised, residual), az_nn_attn_heads (az_nn_attn_block + az_nn_heads as one kernel;
+ * AZ_ATTN_HEADS_FUSED=0 in the environment when the object is created: the two launches) on `stream`, issued
+ * from native code - what alphazero-al_amd/src/fast_net.py does per call from Python.  The object keeps the
  * POINTERS given here (the caller keeps the arrays alive and unchanged) and is immutable, so it
  * may be used from several host threads / streams at once; each call brings its own `scratch`
  * (device memory, az_nn_model_scratch_bytes(batch) bytes: two activation tensors).
@@ -186,7 +195,8 @@ int az_nn_model_profile(int enable);
 int az_nn_model_profile_read(double *out_ms, int64_t *out_launches);
 /* The same for every kernel kind of the forward pass: the stem, the first residual block, the attention
  * block, the heads (an event pair around each on every n-th call): summed milliseconds and launches
- * per kind, in the order of AZ_NN_PROFILE_*.  Reading empties the rings (either reader). */
+ * per kind, in the order of AZ_NN_PROFILE_*.  A call that carries event pairs runs az_nn_attn_block and
+ * az_nn_heads as two launches (the fused az_nn_attn_heads has no split to time).  Reading empties the rings. */
 #define AZ_NN_PROFILE_STEM  0
 #define AZ_NN_PROFILE_CONV  1
 #define AZ_NN_PROFILE_ATTN  2

@@ -68,7 +68,14 @@ def stem_folded():
     L.az_nn_stem_folded(feat.data_ptr(), net.stem_frag.data_ptr(), net.stem_pmap.data_ptr(), y.data_ptr(), B, None, None, s)
 
 
-KERNELS = {"conv": conv, "stem": stem, "stem_embed": stem_embed, "stem_folded": stem_folded, "attn": attn, "heads": heads}
+def attn_heads():
+    L.az_nn_attn_heads(x.data_ptr(), net.pre_w.data_ptr(), net.qkvg_w.data_ptr(), net.qn_w.data_ptr(), net.kn_w.data_ptr(),
+                       net.o_w.data_ptr(), C.byref(net._heads_w), mask.data_ptr(), probs.data_ptr(), wdl.data_ptr(),
+                       ml.data_ptr(), B, 1e-5, None, None, s)
+
+
+KERNELS = {"conv": conv, "stem": stem, "stem_embed": stem_embed, "stem_folded": stem_folded, "attn": attn, "heads": heads,
+           "attn_heads": attn_heads}
 
 
 def timed(fn, n=20):

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1471,6 +1472,320 @@ int az_rng_gamma_selftest(uint32_t seed, float alpha, int count, float *out)
     r.seed(seed);
     r.gamma_fill(alpha, out, count);
     return AZ_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- self-play driver (az_selfplay_*)
+// Whole plies from native code: the search (az_mcts_dev_search) and the ply tail of selfplay_kernels.hip.
+// Everything a driver needs between calls lives in its object - no function-level statics - so that
+// drivers on different engines, streams and host threads run side by side.
+
+struct az_selfplay {
+    az_mcts *m = nullptr;
+    az_selfplay_config c;
+    int B = 0, A = 0, rows_per_game = 0;
+    DevBuf<uint64_t> bb0, bb1;
+    DevBuf<int32_t> turn, aux, ply, actions, winner, counts;
+    DevBuf<uint8_t> done, dead;
+    DevBuf<float> stats, eps;
+    DevBuf<unsigned long long> totals, alloc;      // alloc: [0] games asked for, [1] rows handed out
+    // trajectories of the games in progress and the packed store of finished games
+    struct Rows {
+        DevBuf<uint64_t> bb0, bb1;
+        DevBuf<int8_t> turn;
+        DevBuf<float> prob, wdl;
+        DevBuf<uint8_t> mask;
+        void ensure(size_t rows, int A)
+        {
+            bb0.ensure(rows); bb1.ensure(rows); turn.ensure(rows); prob.ensure(rows * A); wdl.ensure(rows * 3); mask.ensure(rows * A);
+        }
+        az::SpRows view() { return az::SpRows{bb0.p, bb1.p, turn.p, prob.p, wdl.p, mask.p}; }
+    } rec, fin;
+    DevBuf<int32_t> fin_slot, fin_len, fin_winner;
+    DevBuf<int64_t> fin_ply, fin_row0;
+    int64_t capacity = 0;
+    int64_t driver_ply = 0;        // plies finished: the sampler's call counter
+    int64_t dropped = 0;           // games dropped before the last drain
+    const int32_t *tape = nullptr;
+    int64_t tape_plies = 0, tape_next = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_used[2] = {false, false};
+
+    ~az_selfplay()
+    {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+
+    void begin_ply(hipStream_t s)
+    {
+        HIP_OK(hipSetDevice(m->device));
+        az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
+    }
+
+    void require_tape() const
+    {
+        if (tape != nullptr && tape_next >= tape_plies)
+            throw AzError(AZ_ERR_STATE, "az_selfplay: the action tape (az_selfplay_set_action_tape) is exhausted");
+    }
+
+    void finish_ply(void *stream)
+    {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        HIP_OK(hipSetDevice(m->device));
+        require_tape();
+        az::launch_counts(m->game, m->arena(), counts.p, s);
+        if (c.record) az::launch_root_stats(m->game, m->arena(), stats.p, s);
+        az::SpPick p{};
+        p.counts = counts.p; p.stats = stats.p; p.ply = ply.p; p.dead = dead.p;
+        p.tape = tape != nullptr ? tape + tape_next * B : nullptr;
+        p.actions = actions.p; p.bb0 = bb0.p; p.bb1 = bb1.p; p.turn = turn.p; p.aux = aux.p;
+        p.rec = rec.view(); p.rows_per_game = rows_per_game;
+        p.temperature = c.temperature; p.temp_endgame = c.temp_endgame; p.temp_decay_moves = c.temp_decay_moves;
+        p.seed = m->dev_seed; p.call = static_cast<uint64_t>(driver_ply); p.n = B;
+        az::launch_sp_pick(m->game, p, c.record != 0, s);
+        if (tape != nullptr) ++tape_next;
+        m->prune_on(actions.p, nullptr, true, m->replay_noise, s);
+        az::launch_bump_call(m->call_ctr.p, s);
+        // the end state has to survive the step (it is the last row of a recorded game): k_sp_advance refills
+        az::launch_game_step(m->game, bb0.p, bb1.p, turn.p, aux.p, actions.p, done.p, winner.p, B, false, s);
+        az::launch_reset_masked(m->arena(), done.p, s);
+        az::SpAdvance a{};
+        a.bb0 = bb0.p; a.bb1 = bb1.p; a.turn = turn.p; a.aux = aux.p; a.ply = ply.p; a.dead = dead.p;
+        a.done = done.p; a.winner = winner.p; a.n = B; a.refill = c.refill; a.record = c.record;
+        a.rec = rec.view(); a.fin = fin.view(); a.rows_per_game = rows_per_game;
+        a.fin_slot = fin_slot.p; a.fin_len = fin_len.p; a.fin_winner = fin_winner.p; a.fin_ply = fin_ply.p; a.fin_row0 = fin_row0.p;
+        a.n_alloc = alloc.p; a.n_rows = alloc.p + 1; a.capacity = capacity; a.driver_ply = driver_ply;
+        a.eps = c.noise_steps > 0 ? eps.p : nullptr;
+        a.noise_steps = c.noise_steps; a.noise_eps_init = c.noise_eps_init; a.noise_eps_min = c.noise_eps_min;
+        a.totals = totals.p;
+        az::launch_sp_advance(m->game, a, s);
+        ++driver_ply;
+        const int rc = az_mcts_dev_check(m, stream);
+        if (rc != AZ_OK) throw AzError(rc, g_last_error);
+        // bounded run-ahead: the host may be one ply ahead of the device
+        const int slot = static_cast<int>(driver_ply & 1);
+        HIP_OK(hipEventRecord(ev[slot], s));
+        ev_used[slot] = true;
+        if (ev_used[slot ^ 1]) HIP_OK(hipEventSynchronize(ev[slot ^ 1]));
+    }
+
+    // games and rows in the store, games dropped so far (after a device-wide wait)
+    void store_figures(int64_t &n_games, int64_t &n_rows, int64_t &n_dropped)
+    {
+        n_games = n_rows = 0;
+        n_dropped = dropped;
+        if (!c.record) return;
+        unsigned long long h[2];
+        HIP_OK(hipMemcpy(h, alloc.p, sizeof h, hipMemcpyDeviceToHost));
+        n_games = std::min<int64_t>(static_cast<int64_t>(h[0]), capacity);
+        n_rows = static_cast<int64_t>(h[1]);
+        n_dropped = dropped + static_cast<int64_t>(h[0]) - n_games;
+    }
+};
+
+namespace {
+template <class T>
+void fetch(std::vector<T> &h, const T *dev, size_t n)
+{
+    h.resize(n);
+    if (n) HIP_OK(hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
+}
+}  // namespace
+
+extern "C" {
+
+int az_selfplay_create(az_mcts *m, const az_selfplay_config *c, az_selfplay **out)
+{
+    return guarded([&] {
+        require(m != nullptr && c != nullptr && out != nullptr, "az_selfplay_create: null argument");
+        HIP_OK(hipSetDevice(m->device));
+        auto sp = std::make_unique<az_selfplay>();
+        sp->m = m; sp->c = *c; sp->B = m->B; sp->A = m->geo.actions;
+        // the longest game in plies: 42 stones; Othello: 60 stones + passes, never two in a row before the end
+        sp->rows_per_game = m->game == AZ_GAME_CONNECT4 ? 42 : 126;
+        const size_t B = static_cast<size_t>(m->B);
+        az::GameState st;
+        if (m->game == AZ_GAME_CONNECT4) az::Connect4Dev::start(st); else az::OthelloDev::start(st);
+        sp->bb0.ensure(B); sp->bb1.ensure(B); sp->turn.ensure(B);
+        const std::vector<uint64_t> h0(B, st.bb0), h1(B, st.bb1);
+        const std::vector<int32_t> ht(B, 1);
+        HIP_OK(hipMemcpy(sp->bb0.p, h0.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(sp->bb1.p, h1.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(sp->turn.p, ht.data(), B * sizeof(int32_t), hipMemcpyHostToDevice));
+        sp->aux.ensure(B, true); sp->ply.ensure(B, true); sp->actions.ensure(B, true); sp->winner.ensure(B, true);
+        sp->done.ensure(B, true); sp->dead.ensure(B, true);
+        sp->counts.ensure(B * sp->A, true);
+        sp->totals.ensure(5, true); sp->alloc.ensure(2, true);
+        if (c->noise_steps > 0) {
+            const std::vector<float> he(B, static_cast<float>(c->noise_eps_min + (c->noise_eps_init - c->noise_eps_min) * 1.0));
+            sp->eps.ensure(B);
+            HIP_OK(hipMemcpy(sp->eps.p, he.data(), B * sizeof(float), hipMemcpyHostToDevice));
+            m->noise_eps_tree = sp->eps.p;
+        }
+        if (c->record) {
+            sp->stats.ensure(B * m->geo.stats, true);
+            sp->capacity = c->max_finished_games > 0 ? c->max_finished_games : std::max<int64_t>(4 * m->B, 1024);
+            sp->rec.ensure(B * sp->rows_per_game, sp->A);
+            sp->fin.ensure(static_cast<size_t>(sp->capacity) * (sp->rows_per_game + 1), sp->A);
+            const size_t G = static_cast<size_t>(sp->capacity);
+            sp->fin_slot.ensure(G); sp->fin_len.ensure(G); sp->fin_winner.ensure(G); sp->fin_ply.ensure(G); sp->fin_row0.ensure(G);
+        }
+        for (auto &e : sp->ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        // the games start over: so do the trees (flushed by the first search's az_mcts_dev_prepare)
+        std::fill(m->pending_reset.begin(), m->pending_reset.end(), 1);
+        m->any_pending_reset = true;
+        *out = sp.release();
+    });
+}
+
+void az_selfplay_destroy(az_selfplay *sp)
+{
+    if (!sp) return;
+    (void)hipSetDevice(sp->m->device);
+    (void)hipDeviceSynchronize();
+    if (sp->eps.p != nullptr && sp->m->noise_eps_tree == sp->eps.p) sp->m->noise_eps_tree = nullptr;
+    delete sp;
+}
+
+int az_selfplay_step(az_selfplay *sp, const az_nn_model *model, int n_playout, int K, int use_table, int n_plies, void *stream)
+{
+    return guarded([&] {
+        require(sp != nullptr && model != nullptr && n_plies >= 0, "az_selfplay_step: bad argument");
+        for (int i = 0; i < n_plies; ++i) {
+            sp->require_tape();
+            sp->begin_ply(static_cast<hipStream_t>(stream));
+            const int rc = az_mcts_dev_search(sp->m, model, n_playout, K, use_table, stream);
+            if (rc != AZ_OK) throw AzError(rc, g_last_error);
+            sp->finish_ply(stream);
+        }
+    });
+}
+
+int az_selfplay_begin_ply(az_selfplay *sp, void *stream)
+{
+    return guarded([&] {
+        require(sp != nullptr, "az_selfplay_begin_ply: null driver");
+        sp->require_tape();
+        sp->begin_ply(static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_selfplay_finish_ply(az_selfplay *sp, void *stream)
+{
+    return guarded([&] {
+        require(sp != nullptr, "az_selfplay_finish_ply: null driver");
+        sp->finish_ply(stream);
+    });
+}
+
+int az_selfplay_set_action_tape(az_selfplay *sp, const int32_t *actions, int64_t n_plies)
+{
+    return guarded([&] {
+        require(sp != nullptr && (actions == nullptr || n_plies > 0), "az_selfplay_set_action_tape: a tape needs a length");
+        sp->tape = actions;
+        sp->tape_plies = actions ? n_plies : 0;
+        sp->tape_next = 0;
+    });
+}
+
+int az_selfplay_totals(az_selfplay *sp, int64_t out[5])
+{
+    return guarded([&] {
+        require(sp != nullptr && out != nullptr, "az_selfplay_totals: null argument");
+        HIP_OK(hipSetDevice(sp->m->device));
+        HIP_OK(hipDeviceSynchronize());
+        unsigned long long h[5];
+        HIP_OK(hipMemcpy(h, sp->totals.p, sizeof h, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 5; ++i) out[i] = static_cast<int64_t>(h[i]);
+    });
+}
+
+int az_selfplay_positions(az_selfplay *sp, uint64_t *bb_p1, uint64_t *bb_p2, int32_t *turns, int32_t *ply)
+{
+    return guarded([&] {
+        require(sp != nullptr, "az_selfplay_positions: null driver");
+        HIP_OK(hipSetDevice(sp->m->device));
+        HIP_OK(hipDeviceSynchronize());
+        const size_t B = static_cast<size_t>(sp->B);
+        if (bb_p1) HIP_OK(hipMemcpy(bb_p1, sp->bb0.p, B * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (bb_p2) HIP_OK(hipMemcpy(bb_p2, sp->bb1.p, B * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (turns) HIP_OK(hipMemcpy(turns, sp->turn.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (ply) HIP_OK(hipMemcpy(ply, sp->ply.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    });
+}
+
+int az_selfplay_finished(az_selfplay *sp, int64_t *n_games, int64_t *n_rows, int64_t *n_dropped)
+{
+    return guarded([&] {
+        require(sp != nullptr, "az_selfplay_finished: null driver");
+        HIP_OK(hipSetDevice(sp->m->device));
+        HIP_OK(hipDeviceSynchronize());
+        int64_t g, r, d;
+        sp->store_figures(g, r, d);
+        if (n_games) *n_games = g;
+        if (n_rows) *n_rows = r;
+        if (n_dropped) *n_dropped = d;
+    });
+}
+
+int az_selfplay_drain(az_selfplay *sp, const az_selfplay_games *out, int64_t n_games, int64_t n_rows)
+{
+    return guarded([&] {
+        require(sp != nullptr && out != nullptr, "az_selfplay_drain: null argument");
+        require(sp->c.record != 0, "az_selfplay_drain: the driver does not record");
+        HIP_OK(hipSetDevice(sp->m->device));
+        HIP_OK(hipDeviceSynchronize());
+        int64_t g, r, d;
+        sp->store_figures(g, r, d);
+        require(g == n_games && r == n_rows, "az_selfplay_drain: sizes differ from what az_selfplay_finished reports");
+        const size_t G = static_cast<size_t>(g), R = static_cast<size_t>(r), A = static_cast<size_t>(sp->A);
+        std::vector<int32_t> slot, len, win;
+        std::vector<int64_t> fply, row0;
+        fetch(slot, sp->fin_slot.p, G); fetch(len, sp->fin_len.p, G); fetch(win, sp->fin_winner.p, G);
+        fetch(fply, sp->fin_ply.p, G); fetch(row0, sp->fin_row0.p, G);
+        std::vector<uint64_t> b0, b1;
+        std::vector<int8_t> tn;
+        std::vector<float> pr, wd;
+        std::vector<uint8_t> mk;
+        fetch(b0, sp->fin.bb0.p, R); fetch(b1, sp->fin.bb1.p, R); fetch(tn, sp->fin.turn.p, R);
+        fetch(pr, sp->fin.prob.p, R * A); fetch(wd, sp->fin.wdl.p, R * 3); fetch(mk, sp->fin.mask.p, R * A);
+        // the store fills in no particular order: hand the games out by (finishing ply, slot)
+        std::vector<size_t> order(G);
+        for (size_t i = 0; i < G; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+            return fply[x] != fply[y] ? fply[x] < fply[y] : slot[x] < slot[y];
+        });
+        size_t at = 0;
+        for (size_t k = 0; k < G; ++k) {
+            const size_t i = order[k], rows = static_cast<size_t>(len[i]) + 1, from = static_cast<size_t>(row0[i]);
+            if (from + rows > R || at + rows > R) throw AzError(AZ_ERR_STATE, "az_selfplay_drain: the finished store is inconsistent");
+            out->slot[k] = slot[i]; out->length[k] = len[i]; out->winner[k] = win[i];
+            out->finish_ply[k] = fply[i]; out->row_start[k] = static_cast<int64_t>(at);
+            std::copy_n(&b0[from], rows, out->bb_p1 + at); std::copy_n(&b1[from], rows, out->bb_p2 + at);
+            std::copy_n(&tn[from], rows, out->turn + at);
+            std::copy_n(&pr[from * A], rows * A, out->prob + at * A); std::copy_n(&wd[from * 3], rows * 3, out->wdl + at * 3);
+            std::copy_n(&mk[from * A], rows * A, out->mask + at * A);
+            at += rows;
+        }
+        sp->dropped = d;
+        HIP_OK(hipMemset(sp->alloc.p, 0, 2 * sizeof(unsigned long long)));
+    });
+}
+
+int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c, uint64_t seed,
+                       uint64_t call, int32_t *actions, int64_t n, void *stream)
+{
+    return guarded([&] {
+        require(game == AZ_GAME_CONNECT4 || game == AZ_GAME_OTHELLO, "az_selfplay_sample: unknown game");
+        require(counts != nullptr && ply != nullptr && c != nullptr && actions != nullptr && n >= 0, "az_selfplay_sample: bad argument");
+        az::SpPick p{};
+        p.counts = counts; p.ply = ply; p.actions = actions;
+        p.temperature = c->temperature; p.temp_endgame = c->temp_endgame; p.temp_decay_moves = c->temp_decay_moves;
+        p.seed = seed; p.call = call; p.n = n;
+        az::launch_sp_pick(game, p, false, static_cast<hipStream_t>(stream));
+    });
 }
 
 }  // extern "C"

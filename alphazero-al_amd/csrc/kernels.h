@@ -155,4 +155,56 @@ void launch_tt_refresh_gather(int game, TtTable t, uint64_t e0, int n, uint64_t 
 void launch_tt_refresh_store(int game, TtTable t, uint64_t e0, int n, const int32_t *rows, const int64_t *count, const uint64_t *keys,
                              const float *probs, const float *wdl, const float *ml, hipStream_t s);
 
+// ---- native self-play driver (selfplay_kernels.hip) ------------------------------------------------
+// Trajectory rows, structure of arrays: row r of a store (the games in progress: slot * rows_per_game + ply;
+// the finished store: packed, a game's rows 0..len are adjacent)
+struct SpRows {
+    uint64_t *bb0, *bb1;
+    int8_t   *turn;
+    float    *prob;      // [rows][A]
+    float    *wdl;       // [rows][3]
+    uint8_t  *mask;      // [rows][A]
+};
+
+struct SpPick {
+    const int32_t *counts;   // [n][A] root visit counts
+    const float   *stats;    // [n][STATS] root statistics (recording only)
+    const int32_t *ply;      // [n]
+    const uint8_t *dead;     // [n] or nullptr: slots whose game is over (action -1)
+    const int32_t *tape;     // [n] or nullptr: this ply's actions, read instead of drawn
+    int32_t       *actions;  // [n]
+    const uint64_t *bb0, *bb1;   // positions (recording only)
+    const int32_t *turn, *aux;
+    SpRows  rec;
+    int     rows_per_game;
+    float   temperature, temp_endgame;
+    int     temp_decay_moves;
+    uint64_t seed, call;     // generator key: the engine's seed and the driver's ply counter
+    int64_t n;
+};
+
+struct SpAdvance {
+    uint64_t *bb0, *bb1;
+    int32_t  *turn, *aux, *ply;
+    uint8_t  *dead;
+    const uint8_t *done;
+    const int32_t *winner;
+    int64_t  n;
+    int      refill, record;
+    SpRows   rec, fin;
+    int      rows_per_game;
+    int32_t *fin_slot, *fin_len, *fin_winner;
+    int64_t *fin_ply, *fin_row0;
+    unsigned long long *n_alloc, *n_rows;    // games asked for (may pass `capacity`: those were dropped), rows handed out
+    int64_t  capacity;                       // games the finished store holds
+    int64_t  driver_ply;
+    float   *eps;                            // per-game noise epsilon of the next ply, or nullptr
+    int      noise_steps;
+    double   noise_eps_init, noise_eps_min;
+    unsigned long long *totals;              // positions, games, p1 wins, p2 wins, draws
+};
+
+void launch_sp_pick(int game, SpPick a, bool record, hipStream_t s);
+void launch_sp_advance(int game, SpAdvance a, hipStream_t s);
+
 }  // namespace az

@@ -24,6 +24,7 @@
 
 #include <cstdlib>
 
+#include "dev_rng.h"
 #include "games.h"
 
 namespace az {
@@ -46,46 +47,6 @@ __device__ __forceinline__ float mean_m(int n, float msum)
 {
     return n == 0 ? 0.0f : msum / static_cast<float>(n);   // MCTSNode.h:131-133
 }
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-// counter-based generator of the dev_* entry points
-struct DevRng {
-    uint64_t s;
-    __device__ DevRng(uint64_t seed, uint64_t call, uint64_t a, uint64_t b)
-        : s(mix64(seed ^ mix64(call + 0x9E3779B97F4A7C15ull * (a + 1)) ^ (b << 32))) {}
-    __device__ uint32_t next() { s += 0x9E3779B97F4A7C15ull; return static_cast<uint32_t>(mix64(s) >> 32); }
-    __device__ float uniform() { return (static_cast<float>(next() >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-    __device__ float normal()
-    {
-        const float u1 = uniform(), u2 = uniform();
-        return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530718f * u2);
-    }
-    __device__ float gamma(float alpha)   // Marsaglia-Tsang, boosted for alpha < 1
-    {
-        const float a = alpha < 1.0f ? alpha + 1.0f : alpha;
-        const float d = a - 1.0f / 3.0f, c = 1.0f / sqrtf(9.0f * d);
-        float v = 1.0f, x, u;
-        for (int it = 0; it < 64; ++it) {
-            x = normal();
-            v = 1.0f + c * x;
-            if (v <= 0.0f) continue;
-            v = v * v * v;
-            u = uniform();
-            if (u < 1.0f - 0.0331f * x * x * x * x) break;
-            if (logf(u) < 0.5f * x * x + d * (1.0f - v + logf(v))) break;
-        }
-        float g = d * v;
-        if (alpha < 1.0f) g *= powf(uniform(), 1.0f / alpha);
-        return g;
-    }
-};
 
 // Work counters: CNT_STRIPES copies of the CNT_N counters, one 64-byte line each; a workgroup
 // adds to the copy picked by its index, the host sums the copies.  A single copy made a thousand

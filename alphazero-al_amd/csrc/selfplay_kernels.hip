@@ -1,0 +1,266 @@
+// selfplay_kernels.hip - the ply tail of the native self-play driver (az_selfplay_* in az_mcts.h),
+// instantiated per game like the tree kernels.
+//
+//   k_sp_pick     root visit counts -> the move of every game (player.py:348-371 with the temperature
+//                 schedule of game.py:55-63) and, when recording, this ply's row of the game's
+//                 trajectory (game.py:97-108).  One lane group per game as in kernels.hip (Connect4: 8
+//                 lanes, 8 games per wavefront; Othello: a wavefront): lane e owns action e, Othello's
+//                 65th action (pass) rides with lane 0.
+//   k_sp_advance  after the re-rooting and the game step: ply counters, finished games' rows into the
+//                 finished store, refill, next ply's noise epsilon (game.py:87-91), running totals.
+//                 One lane per game for the bookkeeping; a wavefront then copies the rows of ITS
+//                 finished games together - bytes moved follow the games that ended, not slots x plies.
+//
+// Plain C++ and vector stores only.  Store rows are handed out per WAVEFRONT: a ballot counts the
+// finished games, one lane adds the wave's figures to the two counters (games, rows), ranks come from
+// the ballot and a wave-wide prefix sum - two atomics per wavefront that has a finished game, none else.
+#include "kernels.h"
+
+#include "dev_rng.h"
+#include "games.h"
+
+namespace az {
+namespace {
+
+constexpr int WAVE = 64;
+
+template <int L>
+__device__ __forceinline__ unsigned long long group_ballot(bool pred, int lane)
+{
+    const unsigned long long bal = __ballot(pred);
+    constexpr unsigned long long mask = L >= 64 ? ~0ull : ((1ull << (L & 63)) - 1ull);
+    return (bal >> (lane - lane % L)) & mask;
+}
+
+template <int L, class T>
+__device__ __forceinline__ T group_max(T v)
+{
+#pragma unroll
+    for (int o = L / 2; o > 0; o >>= 1) {
+        const T w = __shfl_xor(v, o, L);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+template <int L>
+__device__ __forceinline__ long long group_sum(long long v)
+{
+#pragma unroll
+    for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
+    return v;
+}
+
+// inclusive prefix sum over the lane group, in lane order
+template <int L>
+__device__ __forceinline__ float group_scan(float v, int sub)
+{
+#pragma unroll
+    for (int o = 1; o < L; o <<= 1) {
+        const float w = __shfl_up(v, o, L);
+        if (sub >= o) v += w;
+    }
+    return v;
+}
+
+template <class G, bool RECORD>
+__global__ void __launch_bounds__(WAVE) k_sp_pick(SpPick a)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    constexpr bool TWO = A > L;                       // a second action per lane (Othello: lane 0, the pass)
+    const int lane = threadIdx.x, sub = lane % L;
+    const int64_t game = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
+    const bool live = game < a.n;
+    const int64_t g = live ? game : 0;
+    const int32_t *cnt = a.counts + g * A;
+    const bool has0 = live && sub < A, has1 = TWO && live && sub + L < A;
+    const int n0 = has0 ? max(cnt[sub], 0) : 0;
+    const int n1 = has1 ? max(cnt[sub + L], 0) : 0;
+    const int ply = a.ply[g];
+    const bool dead = a.dead != nullptr && a.dead[g] != 0;
+    const long long total = group_sum<L>(static_cast<long long>(n0) + n1);
+
+    // game.py:55-63
+    const float temp = (a.temp_decay_moves <= 0 || ply < a.temp_decay_moves) ? a.temperature : a.temp_endgame;
+    int action;
+    if (a.tape != nullptr) {
+        action = a.tape[g];
+    } else if (total == 0) {
+        action = 0;                                    // player.py:355-358
+    } else if (!(temp > 1e-6f)) {
+        // the FIRST maximal count (np.argmax): largest (count, -action)
+        long long key = has0 ? ((static_cast<long long>(n0) << 8) | (255 - sub)) : -1;
+        if (has1) { const long long k1 = (static_cast<long long>(n1) << 8) | (255 - (sub + L)); key = k1 > key ? k1 : key; }
+        key = group_max<L>(key);
+        action = 255 - static_cast<int>(key & 255);
+    } else {
+        // player.py:365-368: weights exp((log N - max log N) / T) over the actions with N > 0, ascending;
+        // one uniform, inverse CDF
+        const float ninf = -__builtin_inff();
+        const float l0 = n0 > 0 ? logf(static_cast<float>(n0)) : ninf;
+        const float l1 = n1 > 0 ? logf(static_cast<float>(n1)) : ninf;
+        const float mx = group_max<L>(l0 > l1 ? l0 : l1);
+        const float w0 = n0 > 0 ? expf((l0 - mx) / temp) : 0.0f;
+        const float w1 = n1 > 0 ? expf((l1 - mx) / temp) : 0.0f;
+        const float c0 = group_scan<L>(w0, sub);
+        const float tot0 = __shfl(c0, L - 1, L);
+        float c1 = 0.0f, tot = tot0;
+        if (TWO) {
+            c1 = tot0 + group_scan<L>(w1, sub);
+            tot = __shfl(c1, L - 1, L);
+        }
+        DevRng rng(a.seed, a.call, static_cast<uint64_t>(g), SP_STREAM);
+        const float target = rng.uniform() * tot;
+        const unsigned long long v0 = group_ballot<L>(n0 > 0, lane), v1 = group_ballot<L>(n1 > 0, lane);
+        const unsigned long long h0 = group_ballot<L>(n0 > 0 && c0 > target, lane);
+        const unsigned long long h1 = group_ballot<L>(n1 > 0 && c1 > target, lane);
+        if (h0) action = __ffsll(static_cast<long long>(h0)) - 1;
+        else if (h1) action = L + __ffsll(static_cast<long long>(h1)) - 1;
+        else if (v1) action = L + 63 - __clzll(static_cast<long long>(v1));     // rounding left the target at the total
+        else action = 63 - __clzll(static_cast<long long>(v0));
+    }
+    if (dead) action = -1;
+    if (live && sub == 0) a.actions[g] = action;
+
+    if (RECORD) {
+        if (!live || dead || ply < 0 || ply >= a.rows_per_game) return;
+        const size_t r = static_cast<size_t>(g) * a.rows_per_game + ply;
+        GameState s;
+        s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g];
+        if (sub == 0) {
+            a.rec.bb0[r] = s.bb0; a.rec.bb1[r] = s.bb1; a.rec.turn[r] = static_cast<int8_t>(s.turn);
+            const float *st = a.stats + g * G::STATS;
+            a.rec.wdl[r * 3 + 0] = st[3]; a.rec.wdl[r * 3 + 1] = st[4]; a.rec.wdl[r * 3 + 2] = st[5];
+        }
+        // player.py:356: int / int in double, rounded once to f32
+        const double den = static_cast<double>(total);
+        if (has0) {
+            a.rec.prob[r * A + sub] = total > 0 ? static_cast<float>(static_cast<double>(n0) / den) : 0.0f;
+            a.rec.mask[r * A + sub] = G::valid_in_frame(s, 0, sub) ? 1 : 0;
+        }
+        if (has1) {
+            a.rec.prob[r * A + sub + L] = total > 0 ? static_cast<float>(static_cast<double>(n1) / den) : 0.0f;
+            a.rec.mask[r * A + sub + L] = G::valid_in_frame(s, 0, sub + L) ? 1 : 0;
+        }
+    }
+}
+
+template <class G>
+__global__ void __launch_bounds__(WAVE) k_sp_advance(SpAdvance a)
+{
+    constexpr int A = G::ACTIONS;
+    const int lane = threadIdx.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * WAVE + lane;
+    const bool live = i < a.n;
+    const int64_t g = live ? i : 0;
+    const bool was_dead = a.dead[g] != 0;
+    const bool fin = live && a.done[g] != 0;          // a dead slot played action -1: done == 0
+    const int win = a.winner[g];
+    int ply = a.ply[g];
+    if (!was_dead) ply += 1;
+    GameState s;
+    s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g];
+
+    const unsigned long long fin_mask = __ballot(fin);
+    if (fin_mask != 0 && a.record) {
+        const int n_fin = __popcll(fin_mask);
+        const int rank = __popcll(fin_mask & ((1ull << lane) - 1ull));
+        unsigned long long base_g = 0;
+        if (lane == 0) base_g = atomicAdd(a.n_alloc, static_cast<unsigned long long>(n_fin));
+        base_g = __shfl(base_g, 0, WAVE);
+        // a full store drops the game (the host counts n_alloc - capacity as dropped)
+        const bool keep = fin && base_g + rank < static_cast<unsigned long long>(a.capacity);
+        const int T = ply < a.rows_per_game ? ply : a.rows_per_game;      // rows the game recorded
+        const int my_rows = keep ? T + 1 : 0;                             // + the end state
+        int incl = my_rows;
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int w = __shfl_up(incl, o, WAVE);
+            if (lane >= o) incl += w;
+        }
+        const int wave_rows = __shfl(incl, WAVE - 1, WAVE);
+        unsigned long long base_r = 0;
+        if (lane == 0 && wave_rows) base_r = atomicAdd(a.n_rows, static_cast<unsigned long long>(wave_rows));
+        base_r = __shfl(base_r, 0, WAVE);
+        const size_t row0 = static_cast<size_t>(base_r) + incl - my_rows;
+        if (keep) {
+            const size_t gi = static_cast<size_t>(base_g) + rank;
+            a.fin_slot[gi] = static_cast<int32_t>(g); a.fin_len[gi] = T; a.fin_winner[gi] = win;
+            a.fin_ply[gi] = a.driver_ply; a.fin_row0[gi] = static_cast<int64_t>(row0);
+            a.fin.bb0[row0 + T] = s.bb0; a.fin.bb1[row0 + T] = s.bb1; a.fin.turn[row0 + T] = static_cast<int8_t>(s.turn);
+        }
+        // the wavefront moves the rows of its finished games, one game after the other
+        for (unsigned long long m = __ballot(keep); m; m &= m - 1) {
+            const int src = __ffsll(static_cast<long long>(m)) - 1;
+            const size_t from = static_cast<size_t>(__shfl(static_cast<int>(g), src, WAVE)) * a.rows_per_game;
+            const int Ts = __shfl(T, src, WAVE);
+            const size_t to = static_cast<size_t>(__shfl(static_cast<long long>(row0), src, WAVE));
+            for (int e = lane; e < Ts; e += WAVE) {
+                a.fin.bb0[to + e] = a.rec.bb0[from + e]; a.fin.bb1[to + e] = a.rec.bb1[from + e];
+                a.fin.turn[to + e] = a.rec.turn[from + e];
+            }
+            for (int e = lane; e < (Ts + 1) * 3; e += WAVE) a.fin.wdl[to * 3 + e] = e < Ts * 3 ? a.rec.wdl[from * 3 + e] : 0.0f;
+            for (int e = lane; e < (Ts + 1) * A; e += WAVE) {
+                const bool in = e < Ts * A;
+                a.fin.prob[to * A + e] = in ? a.rec.prob[from * A + e] : 0.0f;
+                a.fin.mask[to * A + e] = in ? a.rec.mask[from * A + e] : 0;
+            }
+        }
+    }
+
+    if (fin) {
+        if (a.refill) {
+            G::start(s);
+            a.bb0[g] = s.bb0; a.bb1[g] = s.bb1; a.turn[g] = s.turn; a.aux[g] = 0;
+            ply = 0;
+        } else {
+            a.dead[g] = 1;
+        }
+    }
+    if (live) {
+        a.ply[g] = ply;
+        if (a.eps != nullptr) {
+            // game.py:87-91 in double, then one rounding
+            const double decay = fmax(0.0, 1.0 - static_cast<double>(ply) / static_cast<double>(a.noise_steps));
+            a.eps[g] = static_cast<float>(a.noise_eps_min + (a.noise_eps_init - a.noise_eps_min) * decay);
+        }
+    }
+    if (lane == 0) {
+        if (blockIdx.x == 0) atomicAdd(&a.totals[0], static_cast<unsigned long long>(a.n));
+        if (fin_mask) {
+            atomicAdd(&a.totals[1], static_cast<unsigned long long>(__popcll(fin_mask)));
+        }
+    }
+    const unsigned long long w1 = __ballot(fin && win == 1), w2 = __ballot(fin && win == -1), w0 = __ballot(fin && win == 0);
+    if (lane == 0) {
+        if (w1) atomicAdd(&a.totals[2], static_cast<unsigned long long>(__popcll(w1)));
+        if (w2) atomicAdd(&a.totals[3], static_cast<unsigned long long>(__popcll(w2)));
+        if (w0) atomicAdd(&a.totals[4], static_cast<unsigned long long>(__popcll(w0)));
+    }
+}
+
+}  // namespace
+
+#define AZ_SP_DISPATCH(game, ...)                                                  \
+    do {                                                                           \
+        if ((game) == Connect4Dev::GAME_ID) { using G = Connect4Dev; __VA_ARGS__; } \
+        else { using G = OthelloDev; __VA_ARGS__; }                                 \
+    } while (0)
+
+void launch_sp_pick(int game, SpPick a, bool record, hipStream_t s)
+{
+    if (a.n <= 0) return;
+    AZ_SP_DISPATCH(game, {
+        const unsigned grid = static_cast<unsigned>((a.n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
+        if (record) hipLaunchKernelGGL((k_sp_pick<G, true>), dim3(grid), dim3(WAVE), 0, s, a);
+        else hipLaunchKernelGGL((k_sp_pick<G, false>), dim3(grid), dim3(WAVE), 0, s, a);
+    });
+}
+
+void launch_sp_advance(int game, SpAdvance a, hipStream_t s)
+{
+    if (a.n <= 0) return;
+    AZ_SP_DISPATCH(game, hipLaunchKernelGGL(k_sp_advance<G>, dim3(static_cast<unsigned>((a.n + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a));
+}
+
+}  // namespace az

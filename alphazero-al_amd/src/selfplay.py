@@ -25,13 +25,65 @@ reference harness, which carries finished games to the end and samples with nump
 `sampler="reference"` draws the moves on the host with the reference's procedure and numpy's
 global generator (player.py:348-371).  The noise-epsilon decay over the plies of a game
 (game.py:87-91, `noise_steps`) is per game here (fixture G14 pins the lockstep case).
+
+`NativeSelfPlay` is the same driver with the whole ply issued from native code (az_selfplay_* in
+include/az_mcts.h): the move, the recording, refill, epsilon decay and totals are two HIP kernels
+(csrc/selfplay_kernels.hip) instead of torch calls, and a step with a native evaluator model is one
+call into the library.  `DeviceSelfPlay` stays what bench.py times.
 """
+
+import ctypes as C
 
 import numpy as np
 import torch
 
 from src import fused as F
 from src.MCTS_cpp import BatchedMCTS
+
+
+def _setup_search(self, net, n_games, n_playout, vl_batch, c_init, c_base, alpha, noise_epsilon, fpu_reduction,
+                  use_symmetry, mlh_slope, mlh_cap, value_decay, temperature, temp_decay_moves, temp_endgame, seed,
+                  table_log2, game, score_utility_factor, score_scale):
+    """Engine, evaluator binding and geometry of a driver (both driver classes)."""
+    self.B = int(n_games)
+    self.n_playout = int(n_playout)
+    self.vl_batch = int(vl_batch)
+    self.temperature, self.temp_decay_moves, self.temp_endgame = temperature, temp_decay_moves, temp_endgame
+    if c_base is None:
+        c_base = 5 * n_playout                  # server.py:135 (c_base_factor 5)
+    assert game in ("Connect4", "Othello")
+    self.game = game
+    self.game_id = 0 if game == "Connect4" else 1                # AZ_GAME_*
+    # the longest game in plies: 42 stones; Othello: 60 stones + passes (never two in a row
+    # before the end, so < 120)
+    self.MAX_PLIES = 42 if game == "Connect4" else 126
+    self.search = BatchedMCTS(self.B, c_init=c_init, c_base=c_base, alpha=alpha, n_playout=n_playout,
+                              game_name=game, noise_epsilon=noise_epsilon,
+                              fpu_reduction=fpu_reduction, use_symmetry=use_symmetry,
+                              mlh_slope=mlh_slope, mlh_cap=mlh_cap, value_decay=value_decay,
+                              score_utility_factor=score_utility_factor, score_scale=score_scale)
+    self.search.seed(seed)
+    self.fused = F.FusedSearch(self.search, net)
+    if table_log2:
+        self.fused.enable_table(table_log2)         # the reference's cache_size (src/Cache.py), in HBM
+    self.h = self.fused.h
+    dev = self.fused.device
+    self.device = dev
+
+
+def _reserve_arenas(self, reserve_slots):
+    if reserve_slots is None:
+        # A re-rooting copies the kept subtree into the tree's other arena half (k_prune), so a tree
+        # occupies what is reachable from its root: the carried subtree plus one ply's growth of at
+        # most n_playout * actions records, not a whole game's worth.  Reserve six plies' worst-case
+        # growth per half: a tree is compacted once it could not take two more plies where it is, i.e.
+        # every few plies; the engine checks the bound every ply from the occupancy the prune kernel
+        # reports and grows the arenas if a tree ever needs more (a device-wide stop and a copy).
+        want = 6 * self.n_playout * (7 if self.game == "Connect4" else 33)      # 33: most legal moves an Othello position has
+        free_bytes, _ = torch.cuda.mem_get_info(self.device)
+        reserve_slots = min(want, int(free_bytes // 2) // (self.B * 2 * 48))
+    if reserve_slots and int(reserve_slots) > 4096:
+        F.check(F.lib().az_mcts_reserve(self.h, int(reserve_slots)))
 
 
 class DeviceSelfPlay:
@@ -41,30 +93,10 @@ class DeviceSelfPlay:
                  reserve_slots=None, record=False, td_steps=0, refill=True, sampler="device",
                  max_finished_games=None, table_log2=0, game="Connect4", score_utility_factor=0.0, score_scale=8.0,
                  noise_steps=0, noise_eps_min=0.1):
-        self.B = int(n_games)
-        self.n_playout = int(n_playout)
-        self.vl_batch = int(vl_batch)
-        self.temperature, self.temp_decay_moves, self.temp_endgame = temperature, temp_decay_moves, temp_endgame
-        if c_base is None:
-            c_base = 5 * n_playout                  # server.py:135 (c_base_factor 5)
-        assert game in ("Connect4", "Othello")
-        self.game = game
-        self.game_id = 0 if game == "Connect4" else 1                # AZ_GAME_*
-        # the longest game in plies: 42 stones; Othello: 60 stones + passes (never two in a row
-        # before the end, so < 120)
-        self.MAX_PLIES = 42 if game == "Connect4" else 126
-        self.search = BatchedMCTS(self.B, c_init=c_init, c_base=c_base, alpha=alpha, n_playout=n_playout,
-                                  game_name=game, noise_epsilon=noise_epsilon,
-                                  fpu_reduction=fpu_reduction, use_symmetry=use_symmetry,
-                                  mlh_slope=mlh_slope, mlh_cap=mlh_cap, value_decay=value_decay,
-                                  score_utility_factor=score_utility_factor, score_scale=score_scale)
-        self.search.seed(seed)
-        self.fused = F.FusedSearch(self.search, net)
-        if table_log2:
-            self.fused.enable_table(table_log2)         # the reference's cache_size (src/Cache.py), in HBM
-        self.h = self.fused.h
-        dev = self.fused.device
-        self.device = dev
+        _setup_search(self, net, n_games, n_playout, vl_batch, c_init, c_base, alpha, noise_epsilon, fpu_reduction,
+                      use_symmetry, mlh_slope, mlh_cap, value_decay, temperature, temp_decay_moves, temp_endgame, seed,
+                      table_log2, game, score_utility_factor, score_scale)
+        dev = self.device
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(int(seed))
         z = dict(device=dev)
@@ -82,18 +114,7 @@ class DeviceSelfPlay:
         self.winner = torch.zeros(self.B, dtype=torch.int32, **z)
         # running totals kept on the device: positions, games, p1 wins, p2 wins, draws
         self.totals = torch.zeros(5, dtype=torch.int64, **z)
-        if reserve_slots is None:
-            # A re-rooting copies the kept subtree into the tree's other arena half (k_prune), so a tree
-            # occupies what is reachable from its root: the carried subtree plus one ply's growth of at
-            # most n_playout * actions records, not a whole game's worth.  Reserve six plies' worst-case
-            # growth per half: a tree is compacted once it could not take two more plies where it is, i.e.
-            # every few plies; the engine checks the bound every ply from the occupancy the prune kernel
-            # reports and grows the arenas if a tree ever needs more (a device-wide stop and a copy).
-            want = 6 * self.n_playout * (7 if game == "Connect4" else 33)      # 33: most legal moves an Othello position has
-            free_bytes, _ = torch.cuda.mem_get_info(dev)
-            reserve_slots = min(want, int(free_bytes // 2) // (self.B * 2 * 48))
-        if reserve_slots and int(reserve_slots) > 4096:
-            F.check(F.lib().az_mcts_reserve(self.h, int(reserve_slots)))
+        _reserve_arenas(self, reserve_slots)
         assert sampler in ("device", "reference")
         self.sampler, self.refill, self.record, self.td_steps = sampler, bool(refill), bool(record), int(td_steps)
         self.dead = torch.zeros(self.B, dtype=torch.bool, **z)        # refill=False: slots whose game is over
@@ -275,38 +296,8 @@ class DeviceSelfPlay:
         winners = self.fin_winner[:n].cpu().numpy()
         slots = self.fin_slot[:n].cpu().numpy()
         self.n_finished.zero_()
-        games = []
-        k = self.td_steps
-        for g in range(n):
-            T = int(lens[g])
-            winner = int(winners[g])
-            states = planes_from_bitboards(host["bb1"][g, :T + 1], host["bb2"][g, :T + 1], host["turn"][g, :T + 1], self.game)
-            winner_z = np.full(T, winner, dtype=np.int32)
-            steps_to_end = np.arange(T, 0, -1, dtype=np.int32)
-            if self.game == "Othello":                               # game.py:17-30: final disc difference, mover's view
-                diff = int(bin(int(host["bb1"][g, T]) & (2 ** 64 - 1)).count("1")) - int(bin(int(host["bb2"][g, T]) & (2 ** 64 - 1)).count("1"))
-                aux = diff * np.asarray(host["turn"][g, :T], dtype=np.int32)
-                terminal_aux = diff * int(host["turn"][g, T])
-            else:
-                aux = steps_to_end                                   # Connect4: moves left
-                terminal_aux = 0
-            probs, masks = host["prob"][g], host["mask"][g]
-            # object identities as in game.py:121-157 (one root-WDL object per ply, reused by the
-            # td-step column; one zero vector per game): pickle writes shared objects once, so
-            # the upload below is byte-identical to the reference client's only if they match
-            root_wdls = [host["wdl"][g][t] for t in range(T)]
-            zero_wdl = np.zeros(3, dtype=np.float32)
-            cols = [[states[t] for t in range(T)], [probs[t] for t in range(T)], winner_z, steps_to_end, aux,
-                    root_wdls, [masks[t] for t in range(T)]]
-            if k > 0:
-                cols.append([root_wdls[t + k] if t + k < T else zero_wdl for t in range(T)])
-            play = list(zip(*cols))
-            terminal = [states[T], np.zeros_like(probs[0]), winner, 0, terminal_aux, zero_wdl, np.ones_like(masks[0])]
-            if k > 0:
-                terminal.append(zero_wdl)
-            play.append(tuple(terminal))
-            games.append((winner, tuple(play), int(slots[g])))
-        return games
+        return assemble_games(self.game, self.td_steps, lens, winners, slots,
+                              lambda g: tuple(host[k][g] for k in ("bb1", "bb2", "turn", "prob", "wdl", "mask")))
 
     def read_totals(self):
         t = self.totals.cpu().tolist()          # synchronises
@@ -316,9 +307,158 @@ class DeviceSelfPlay:
         return F.counters(self.h)
 
 
+class SelfPlayConfig(C.Structure):
+    """az_selfplay_config (include/az_mcts.h)."""
+    _fields_ = [("temperature", C.c_float), ("temp_endgame", C.c_float), ("temp_decay_moves", C.c_int32),
+                ("refill", C.c_int32), ("record", C.c_int32), ("noise_steps", C.c_int32),
+                ("max_finished_games", C.c_int64), ("noise_eps_init", C.c_double), ("noise_eps_min", C.c_double)]
+
+
+class SelfPlayGames(C.Structure):
+    """az_selfplay_games (include/az_mcts.h): host arrays az_selfplay_drain fills."""
+    _fields_ = [(n, C.c_void_p) for n in ("slot", "length", "winner", "finish_ply", "row_start", "bb_p1", "bb_p2",
+                                          "turn", "prob", "wdl", "mask")]
+
+
+def selfplay_lib():
+    """The engine library with the az_selfplay_* prototypes set."""
+    L = F.lib()
+    if not getattr(L, "_az_selfplay_ready", False):
+        vp, i32, i64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
+        L.az_selfplay_create.argtypes = [vp, C.POINTER(SelfPlayConfig), C.POINTER(vp)]
+        L.az_selfplay_destroy.argtypes = [vp]
+        L.az_selfplay_destroy.restype = None
+        L.az_selfplay_step.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        L.az_selfplay_begin_ply.argtypes = [vp, vp]
+        L.az_selfplay_finish_ply.argtypes = [vp, vp]
+        L.az_selfplay_set_action_tape.argtypes = [vp, vp, i64]
+        L.az_selfplay_totals.argtypes = [vp, C.POINTER(i64 * 5)]
+        L.az_selfplay_positions.argtypes = [vp, vp, vp, vp, vp]
+        L.az_selfplay_finished.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.az_selfplay_drain.argtypes = [vp, C.POINTER(SelfPlayGames), i64, i64]
+        L.az_selfplay_sample.argtypes = [i32, vp, vp, C.POINTER(SelfPlayConfig), u64, u64, vp, i64, vp]
+        L._az_selfplay_ready = True
+    return L
+
+
+def drain_native(L, handle, action_size):
+    """az_selfplay_finished + az_selfplay_drain into numpy arrays: (dict of per-game arrays, dict of per-row arrays)."""
+    n, rows, dropped = C.c_int64(), C.c_int64(), C.c_int64()
+    F.check(L.az_selfplay_finished(handle, C.byref(n), C.byref(rows), C.byref(dropped)))
+    n, rows, A = n.value, rows.value, int(action_size)
+    per_game = dict(slot=np.zeros(n, np.int32), length=np.zeros(n, np.int32), winner=np.zeros(n, np.int32),
+                    finish_ply=np.zeros(n, np.int64), row_start=np.zeros(n, np.int64))
+    per_row = dict(bb_p1=np.zeros(rows, np.uint64), bb_p2=np.zeros(rows, np.uint64), turn=np.zeros(rows, np.int8),
+                   prob=np.zeros((rows, A), np.float32), wdl=np.zeros((rows, 3), np.float32), mask=np.zeros((rows, A), np.uint8))
+    out = SelfPlayGames(**{k: v.ctypes.data for k, v in list(per_game.items()) + list(per_row.items())})
+    F.check(L.az_selfplay_drain(handle, C.byref(out), n, rows))
+    return per_game, per_row
+
+
+class NativeSelfPlay:
+    """DeviceSelfPlay with the ply issued from native code (az_selfplay_*, include/az_mcts.h): same
+    constructor arguments, `step(n)`, `drain()`, `read_totals()`, `engine_counters()`.  The engine calls
+    and their order are DeviceSelfPlay's, so the engine's generator hands both drivers the same noise and
+    symmetry ids; the moves come from the driver's own stream of the device generator (k_sp_pick), not
+    from torch's.  `sampler="tape"` with `set_action_tape()` plays recorded moves (parity tests; takes
+    the place of `sampler="reference"`)."""
+
+    def __init__(self, net, n_games, n_playout=200, vl_batch=4, c_init=1.4, c_base=None, alpha=0.3,
+                 noise_epsilon=0.25, fpu_reduction=0.2, use_symmetry=True, mlh_slope=0.1, mlh_cap=0.2,
+                 value_decay=1.0, temperature=1.0, temp_decay_moves=20, temp_endgame=0.0, seed=0,
+                 reserve_slots=None, record=False, td_steps=0, refill=True, sampler="device",
+                 max_finished_games=None, table_log2=0, game="Connect4", score_utility_factor=0.0, score_scale=8.0,
+                 noise_steps=0, noise_eps_min=0.1):
+        self._sp = None
+        _setup_search(self, net, n_games, n_playout, vl_batch, c_init, c_base, alpha, noise_epsilon, fpu_reduction,
+                      use_symmetry, mlh_slope, mlh_cap, value_decay, temperature, temp_decay_moves, temp_endgame, seed,
+                      table_log2, game, score_utility_factor, score_scale)
+        assert sampler in ("device", "tape")
+        self.sampler, self.refill, self.record, self.td_steps = sampler, bool(refill), bool(record), int(td_steps)
+        _reserve_arenas(self, reserve_slots)
+        self.L = selfplay_lib()
+        self.config = SelfPlayConfig(float(temperature), float(temp_endgame), int(temp_decay_moves), int(self.refill),
+                                     int(self.record), int(noise_steps), int(max_finished_games or 0),
+                                     float(noise_epsilon), float(noise_eps_min))
+        sp = C.c_void_p()
+        with torch.cuda.device(self.device):
+            F.check(self.L.az_selfplay_create(self.h, C.byref(self.config), C.byref(sp)))
+        self._sp = sp
+        self._tape = None
+
+    def __del__(self):
+        try:
+            if self.__dict__.get("_sp") is not None:         # before the engine it borrows
+                sp, self._sp = self._sp, None
+                self.L.az_selfplay_destroy(sp)
+        except Exception:
+            pass
+
+    def set_action_tape(self, actions):
+        """actions: (n_plies, n_games) integers, -1 where a game is over; None ends the tape."""
+        assert self.sampler == "tape"
+        if actions is None:
+            self._tape = None
+            F.check(self.L.az_selfplay_set_action_tape(self._sp, None, 0))
+            return
+        t = torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(self.device).contiguous()
+        assert t.dim() == 2 and t.shape[1] == self.B
+        torch.cuda.current_stream().synchronize()
+        self._tape = t                                        # read by the kernels: kept alive here
+        F.check(self.L.az_selfplay_set_action_tape(self._sp, t.data_ptr(), t.shape[0]))
+
+    def step(self, n=1):
+        """n plies in every game."""
+        assert self.sampler != "tape" or self._tape is not None, "sampler='tape' needs set_action_tape()"
+        self.fused._sync_fast_net()
+        model = self.fused._native_model()
+        s = F._stream()
+        if model is not None:
+            F.check(self.L.az_selfplay_step(self._sp, model, self.n_playout, max(1, self.vl_batch),
+                                            1 if self.fused.table_log2 else 0, int(n), s))
+            return
+        for _ in range(int(n)):
+            F.check(self.L.az_selfplay_begin_ply(self._sp, s))
+            self.fused.search(self.n_playout, self.vl_batch)
+            F.check(self.L.az_selfplay_finish_ply(self._sp, s))
+
+    def finished(self):
+        """(games in the store, their rows, games dropped so far); synchronises."""
+        n, rows, dropped = C.c_int64(), C.c_int64(), C.c_int64()
+        F.check(self.L.az_selfplay_finished(self._sp, C.byref(n), C.byref(rows), C.byref(dropped)))
+        return n.value, rows.value, dropped.value
+
+    def positions(self):
+        """The games in progress as numpy arrays (synchronises)."""
+        out = dict(bb_p1=np.zeros(self.B, np.uint64), bb_p2=np.zeros(self.B, np.uint64), turn=np.zeros(self.B, np.int32),
+                   ply=np.zeros(self.B, np.int32))
+        F.check(self.L.az_selfplay_positions(self._sp, *(out[k].ctypes.data for k in ("bb_p1", "bb_p2", "turn", "ply"))))
+        return out
+
+    def drain(self):
+        """As DeviceSelfPlay.drain(): finished games since the last call, in the order (finishing ply, slot)."""
+        assert self.record
+        g, r = drain_native(self.L, self._sp, self.search.action_size)
+        mask = r["mask"].view(np.bool_)
+        bb1, bb2 = r["bb_p1"].view(np.int64), r["bb_p2"].view(np.int64)
+
+        def rows_of(i):
+            a, b = int(g["row_start"][i]), int(g["row_start"][i]) + int(g["length"][i]) + 1
+            return bb1[a:b], bb2[a:b], r["turn"][a:b], r["prob"][a:b], r["wdl"][a:b], mask[a:b]
+        return assemble_games(self.game, self.td_steps, g["length"], g["winner"], g["slot"], rows_of)
+
+    def read_totals(self):
+        t = (C.c_int64 * 5)()
+        F.check(self.L.az_selfplay_totals(self._sp, C.byref(t)))         # synchronises
+        return dict(positions=t[0], games=t[1], p1_wins=t[2], p2_wins=t[3], draws=t[4])
+
+    def engine_counters(self):
+        return F.counters(self.h)
+
+
 class StreamedSelfPlay:
-    """`n_games` games as `streams` independent DeviceSelfPlay drivers, each with its own engine,
-    HIP stream and host thread.
+    """`n_games` games as `streams` independent DeviceSelfPlay drivers (`driver="native"`: NativeSelfPlay),
+    each with its own engine, HIP stream and host thread.
 
     One driver's selection and backup kernels keep one wavefront per SIMD busy and end when the
     deepest tree of the batch is done - most of the chip idles under them; the evaluator kernels
@@ -334,7 +474,7 @@ class StreamedSelfPlay:
     `synchronize()` for that.  `drain()`, `read_totals()`, `engine_counters()` aggregate over the
     drivers; slot numbers are global (driver offset + local slot)."""
 
-    def __init__(self, net, n_games, streams=2, seed=0, **kw):
+    def __init__(self, net, n_games, streams=2, seed=0, driver="device", **kw):
         from concurrent.futures import ThreadPoolExecutor
         p = next(net.parameters(), None)
         self.device = p.device if p is not None else torch.device("cuda", torch.cuda.current_device())
@@ -347,15 +487,21 @@ class StreamedSelfPlay:
         self.offsets = [sum(self.sizes[:i]) for i in range(streams)]
         self.B = int(n_games)
         self.streams = [torch.cuda.Stream(self.device) for _ in range(streams)]
+        assert driver in ("device", "native")
+        self.driver = driver
+        make = NativeSelfPlay if driver == "native" else DeviceSelfPlay
         self.parts = []
         for i, st in enumerate(self.streams):
             with torch.cuda.stream(st):
-                self.parts.append(DeviceSelfPlay(net, self.sizes[i], seed=int(seed) * streams + i, **kw))
+                self.parts.append(make(net, self.sizes[i], seed=int(seed) * streams + i, **kw))
         self.synchronize()
         self._pool = ThreadPoolExecutor(max_workers=streams, thread_name_prefix="az-selfplay")
 
     def _run(self, i, n):
         with torch.cuda.device(self.device), torch.cuda.stream(self.streams[i]):
+            if self.driver == "native":
+                self.parts[i].step(n)
+                return
             for _ in range(n):
                 self.parts[i].step()
 
@@ -406,6 +552,46 @@ class StreamedSelfPlay:
 
     def close(self):
         self._pool.shutdown(wait=True)
+
+
+def assemble_games(game, td_steps, lens, winners, slots, rows_of):
+    """Host-side assembly of drained games into the reference's `play_data` (game.py:110-157), for both
+    drivers.  lens / winners / slots: per game; rows_of(g) -> (bb1, bb2, turn, prob, wdl, mask) of game g,
+    arrays with at least lens[g] + 1 rows (positions before every move, then the end state; only the
+    boards and the side to move of the end-state row are read; mask is boolean).  Returns a list of
+    (winner, play_data, slot)."""
+    games = []
+    k = td_steps
+    for g in range(len(lens)):
+        T = int(lens[g])
+        winner = int(winners[g])
+        bb1, bb2, turn, probs, wdls, masks = rows_of(g)
+        states = planes_from_bitboards(bb1[:T + 1], bb2[:T + 1], turn[:T + 1], game)
+        winner_z = np.full(T, winner, dtype=np.int32)
+        steps_to_end = np.arange(T, 0, -1, dtype=np.int32)
+        if game == "Othello":                               # game.py:17-30: final disc difference, mover's view
+            diff = int(bin(int(bb1[T]) & (2 ** 64 - 1)).count("1")) - int(bin(int(bb2[T]) & (2 ** 64 - 1)).count("1"))
+            aux = diff * np.asarray(turn[:T], dtype=np.int32)
+            terminal_aux = diff * int(turn[T])
+        else:
+            aux = steps_to_end                                   # Connect4: moves left
+            terminal_aux = 0
+        # object identities as in game.py:121-157 (one root-WDL object per ply, reused by the
+        # td-step column; one zero vector per game): pickle writes shared objects once, so
+        # the upload below is byte-identical to the reference client's only if they match
+        root_wdls = [wdls[t] for t in range(T)]
+        zero_wdl = np.zeros(3, dtype=np.float32)
+        cols = [[states[t] for t in range(T)], [probs[t] for t in range(T)], winner_z, steps_to_end, aux,
+                root_wdls, [masks[t] for t in range(T)]]
+        if k > 0:
+            cols.append([root_wdls[t + k] if t + k < T else zero_wdl for t in range(T)])
+        play = list(zip(*cols))
+        terminal = [states[T], np.zeros_like(probs[0]), winner, 0, terminal_aux, zero_wdl, np.ones_like(masks[0])]
+        if k > 0:
+            terminal.append(zero_wdl)
+        play.append(tuple(terminal))
+        games.append((winner, tuple(play), int(slots[g])))
+    return games
 
 
 def pack_upload(games):

@@ -249,6 +249,93 @@ int az_mcts_dev_search(az_mcts *m, const struct az_nn_model *model, int n_playou
 int az_mcts_dev_search_more(az_mcts *m, const struct az_nn_model *model, int n_sims, int K, int use_table,
                             void *stream);
 
+/* ---- self-play from C: whole plies, recording included (alphazero-al_amd/csrc/selfplay_kernels.hip) -------
+ * The reference's driver is Python per game and per ply (src/game.py:65-164 with src/player.py:333-375);
+ * here a driver object owns the positions, ply counters, trajectories and the store of finished games in
+ * HBM, and a ply outside the search is: root counts / statistics, k_sp_pick (the move, this ply's
+ * trajectory row), the re-rooting, the game step, the tree resets, k_sp_advance (finished games' rows into
+ * the store, refill, next epsilon, totals).  The driver borrows the engine: destroy it BEFORE the engine,
+ * use one driver per engine, and make every call of a driver on ONE stream and from one thread at a time
+ * (drivers on different engines, streams and host threads run side by side).  With noise_steps > 0 the
+ * driver installs its per-game epsilons with az_mcts_dev_set_noise_epsilons.
+ *
+ * Fields: temperature while a game's ply < temp_decay_moves, temp_endgame after, constant `temperature`
+ * when temp_decay_moves <= 0 (game.py:55-63); T <= 1e-6 plays the first most visited move, else the move
+ * is drawn with probability N^(1/T) (player.py:362-371) from the device generator (stream of its own,
+ * keyed by the engine's seed, the driver's ply counter and the game).  refill: a finished game restarts
+ * at once in its slot; otherwise the slot is dead (action -1) from then on.  record: keep what
+ * game.py:97-108 keeps per ply and move finished games to a store of max_finished_games games
+ * (<= 0: max(4 n_envs, 1024)); games that end while it is full are dropped and counted.  noise_steps > 0:
+ * epsilon of a game at ply p = eps_min + (eps_init - eps_min) * max(0, 1 - p / noise_steps), in double and
+ * rounded once (game.py:87-91) - the two are doubles because the reference's are Python floats. */
+typedef struct az_selfplay_config {
+    float   temperature;
+    float   temp_endgame;
+    int32_t temp_decay_moves;
+    int32_t refill;
+    int32_t record;
+    int32_t noise_steps;
+    int64_t max_finished_games;
+    double  noise_eps_init;
+    double  noise_eps_min;
+} az_selfplay_config;
+#define AZ_SELFPLAY_CONFIG_BYTES 48
+#ifdef __cplusplus
+static_assert(sizeof(az_selfplay_config) == AZ_SELFPLAY_CONFIG_BYTES, "az_selfplay_config layout");
+#else
+_Static_assert(sizeof(az_selfplay_config) == AZ_SELFPLAY_CONFIG_BYTES, "az_selfplay_config layout");
+#endif
+
+typedef struct az_selfplay az_selfplay;
+
+/* Every game at its initial position, ply 0, every tree of the engine reset (synchronises). */
+int  az_selfplay_create(az_mcts *m, const az_selfplay_config *c, az_selfplay **out);
+void az_selfplay_destroy(az_selfplay *sp);
+/* n_plies whole plies on `stream`: per ply az_mcts_dev_set_roots, az_mcts_dev_search(model, n_playout, K,
+ * use_table), then the tail above and az_mcts_dev_check.  Nothing but enqueues unless the engine's buffers
+ * must grow; the host runs at most one ply ahead of the device (it waits for the event behind the ply
+ * before the previous one, never for the device).  AZ_ERR_CAPACITY as az_mcts_dev_check reports it. */
+int az_selfplay_step(az_selfplay *sp, const struct az_nn_model *model, int n_playout, int K, int use_table,
+                     int n_plies, void *stream);
+/* The two halves of a ply on their own, for an evaluator that is not an az_nn_model: begin_ply puts the
+ * positions into the engine as roots; the caller searches (az_mcts_dev_prepare_stream and the select /
+ * backprop calls, or alphazero-al_amd/src/fused.py); finish_ply is everything after the search. */
+int az_selfplay_begin_ply(az_selfplay *sp, void *stream);
+int az_selfplay_finish_ply(az_selfplay *sp, void *stream);
+/* Test hook - recorded moves instead of the sampler: actions int32 [n_plies][n_envs] in DEVICE memory, kept
+ * alive by the caller; the p-th ply after this call plays actions[p] (-1: the slot does not move; no draw is
+ * made).  Running past the tape is AZ_ERR_STATE, as with az_mcts_dev_replay.  NULL ends it. */
+int az_selfplay_set_action_tape(az_selfplay *sp, const int32_t *actions, int64_t n_plies);
+/* Running totals: [0] positions played [1] games finished [2] won by player +1 [3] by player -1 [4] drawn
+ * (synchronises). */
+int az_selfplay_totals(az_selfplay *sp, int64_t out[5]);
+/* The games in progress, to HOST arrays of n_envs entries, any of them NULL (synchronises). */
+int az_selfplay_positions(az_selfplay *sp, uint64_t *bb_p1, uint64_t *bb_p2, int32_t *turns, int32_t *ply);
+/* What the finished store holds: games, trajectory rows (a game of L moves has L + 1: one per position
+ * before a move, then the end state), and the games dropped since creation (synchronises). */
+int az_selfplay_finished(az_selfplay *sp, int64_t *n_games, int64_t *n_rows, int64_t *n_dropped);
+/* HOST arrays sized from az_selfplay_finished.  Game g: the slot it was played in, its moves, the winner
+ * (+1 / -1 / 0), the driver ply it ended on, and its first row; rows row_start[g] .. row_start[g] + length[g]:
+ * both bitboards and the side to move (end state included), and for the rows before the end the visit
+ * distribution N / sum N (double division, rounded once: player.py:356), the root's [draw, p1, p2] and the
+ * legal-move mask (zeros in the end-state row). */
+typedef struct az_selfplay_games {
+    int32_t  *slot, *length, *winner;      /* [n_games] */
+    int64_t  *finish_ply, *row_start;      /* [n_games] */
+    uint64_t *bb_p1, *bb_p2;               /* [n_rows] */
+    int8_t   *turn;                        /* [n_rows] */
+    float    *prob;                        /* [n_rows][A] */
+    float    *wdl;                         /* [n_rows][3] */
+    uint8_t  *mask;                        /* [n_rows][A] */
+} az_selfplay_games;
+/* Copies the store out in the order (finishing ply, slot) and empties it (synchronises); n_games and
+ * n_rows must be what az_selfplay_finished just reported. */
+int az_selfplay_drain(az_selfplay *sp, const az_selfplay_games *out, int64_t n_games, int64_t n_rows);
+/* k_sp_pick on caller-supplied counts, for tests: counts int32 [n][A] and ply int32 [n] in DEVICE memory
+ * -> actions int32 [n]; draws are keyed by (seed, call, row).  Only the temperature fields of `c` are read. */
+int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c,
+                       uint64_t seed, uint64_t call, int32_t *actions, int64_t n, void *stream);
+
 /* ---- device transposition table of evaluator outputs (both games) ------------------------
  * Replaces, for the device loop, the LRU table of the reference's wrapper (src/Cache.py:5-58 used
  * by src/MCTS_cpp.py:146-189 and 298-339): key = the symmetrised leaf position + side to move,

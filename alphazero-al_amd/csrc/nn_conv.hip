@@ -25,14 +25,11 @@
 // VALU work overlaps the other's MFMA phase; workgroups are persistent over tiles and fetch
 // the next tile's activations while the current one is multiplied.  HBM traffic per block:
 // read x once, write y once (the residual is re-read from an LDS copy of the raw tile).
-#include <hip/hip_bf16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
 #include "az_nn.h"
+#include "nn_common.h"
 
 namespace {
 
@@ -45,41 +42,6 @@ constexpr int TS = 4;                          // samples per tile = wavefronts 
 constexpr int COUT = 64;
 constexpr int CELLB = 128;                     // bytes per image cell (C_in 32 uses half of it)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct alignas(16) V8 { uint32_t w[4]; };
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-// one v_cvt_pk_bf16_f32 (round to nearest even, NaN preserving)
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(pk_f32x2{a, b}, pk_bf16x2));
-}
-// wave-wide sum on the DPP network (the adds carry the lane movement as an operand modifier):
-// 8 VALU instructions and a readlane, against 6 x (ds_bpermute + address + add) for xor-shuffles
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_mov(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += dpp_mov<0xB1>(v);           // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);           // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);          // row_half_mirror
-    v += dpp_mov<0x140>(v);          // row_mirror: every lane of a 16-lane row holds the row sum
-    v += dpp_mov<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3
-    v += dpp_mov<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3: lane 63 holds the total
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// packed-f32 arithmetic (v_pk_mul/add/fma_f32): two elements per VALU instruction
-__device__ __forceinline__ f32x2 unpack2(uint32_t w) { return f32x2{bf_lo(w), bf_hi(w)}; }
 // 16 bytes per lane from global memory straight into LDS at (wave-uniform) lds_off + lane * 16.
 // Written as inline assembly on purpose: when the compiler knows that a global_load_lds is in
 // flight it puts s_waitcnt vmcnt(0) in front of every later LDS read that might alias it, i.e.
@@ -521,19 +483,16 @@ int launch(const void *x, const void *w, const void *bias, const void *gamma, co
 {
     constexpr size_t smem = static_cast<size_t>(TS) * PCELLS * CELLB + 2 * static_cast<size_t>(TS) * CELLS * CIN * 2 +
                             (RESID ? 0 : static_cast<size_t>(TS) * CELLS * COUT * 2) + 2 * CIN * sizeof(float) + 512;
-    static bool attr_set = false;
     auto kern = k_conv_block<CIN, NORM, RESID, EMBED>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(smem)) != hipSuccess)
-            return 2;
-        attr_set = true;
-        if (getenv("AZ_NN_VERBOSE") != nullptr) {
-            int per_cu = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, smem);
-            fprintf(stderr, "[az_nn] conv block C_in=%d: %zu B LDS, %d workgroups per CU\n", CIN, smem, per_cu);
-        }
-    }
+    static DeviceSetup setup;
+    if (setup.cus({reinterpret_cast<const void *>(kern)}, static_cast<int>(smem), [&] {
+            if (getenv("AZ_NN_VERBOSE") != nullptr) {
+                int per_cu = 0;
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, smem);
+                fprintf(stderr, "[az_nn] conv block C_in=%d: %zu B LDS, %d workgroups per CU\n", CIN, smem, per_cu);
+            }
+        }) == 0)
+        return 2;
     // issue priority of the matrix phase over the other workgroup's load / store phases (s_setprio 0..3; AZ_NN_CONV_PRIO)
     static const int prio = [] { const char *e = getenv("AZ_NN_CONV_PRIO"); const int v = e ? atoi(e) : 1; return v < 0 || v > 3 ? 1 : v; }();
     const int64_t ntiles = (B + TS - 1) / TS;

@@ -25,15 +25,12 @@
 //     bank slots per 16-lane group of ds_read_b128, a step to the next row flips one address bit, and a step to
 //     the next token tile (a multiple of 16 cells) is a constant in the read's offset field.
 // Two barriers per 4-sample tile.  HBM traffic: x read once, y written once.
-#include <hip/hip_bf16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 #include "az_nn.h"
+#include "nn_common.h"
 
 namespace {
 
@@ -51,11 +48,7 @@ static_assert(L_TOTAL <= 160 * 1024, "LDS budget of one workgroup per CU");
 static_assert(L_IN == 0, "the images sit at LDS address 0: every B-fragment read is register + immediate");
 constexpr float L2E = 1.44269504f;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-struct alignas(16) V8 { uint32_t w[4]; };
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int I, int N, class F>
@@ -67,17 +60,6 @@ __device__ __forceinline__ void static_for(F &&f)
     }
 }
 
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(pk_f32x2{a, b}, pk_bf16x2));
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_mov(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
 // 16 bytes per lane from global memory straight into LDS at (wave-uniform) lds_off + lane * 16 (see nn_conv.hip:
 // inline assembly so that the compiler does not serialise later LDS reads behind the transfer)
 __device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_off)
@@ -553,25 +535,18 @@ extern "C" int az_nn_conv_block2(const void *x, const void *weight_folded_ohwi, 
                                  int64_t batch, float eps, const int64_t *batch_dev, void *stream)
 {
     if (batch <= 0 || !x || !weight_folded_ohwi || !t1 || !t2_scaled || !y) return 1;
-    static bool attr_set = false;
-    static int n_cu = 256;
-    if (!attr_set) {
-        for (const void *f : {reinterpret_cast<const void *>(k_conv2<0>), reinterpret_cast<const void *>(k_conv2<1>),
+    static DeviceSetup setup;
+    const int cus = setup.cus({reinterpret_cast<const void *>(k_conv2<0>), reinterpret_cast<const void *>(k_conv2<1>),
                               reinterpret_cast<const void *>(k_conv2<2>), reinterpret_cast<const void *>(k_conv2<3>),
                               reinterpret_cast<const void *>(k_conv2<6>), reinterpret_cast<const void *>(k_conv2<10>),
                               reinterpret_cast<const void *>(k_conv2<14>), reinterpret_cast<const void *>(k_conv2<19>),
                               reinterpret_cast<const void *>(k_conv2<35>), reinterpret_cast<const void *>(k_conv2<67>),
                               reinterpret_cast<const void *>(k_conv2<64>), reinterpret_cast<const void *>(k_conv2<131>), reinterpret_cast<const void *>(k_conv2<387>),
-                              reinterpret_cast<const void *>(k_conv2<259>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, L_TOTAL) != hipSuccess) return 2;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cu = v;
-        }
-        if (const char *e = getenv("AZ_NN_CONV2_GRID")) n_cu = atoi(e) > 0 ? atoi(e) : n_cu;
-        attr_set = true;
-    }
+                              reinterpret_cast<const void *>(k_conv2<259>)}, L_TOTAL);
+    if (cus == 0) return 2;
+    // one workgroup per CU (AZ_NN_CONV2_GRID: another number of them)
+    static const int grid_env = getenv("AZ_NN_CONV2_GRID") ? atoi(getenv("AZ_NN_CONV2_GRID")) : 0;
+    const int n_cu = grid_env > 0 ? grid_env : cus;
     const int64_t ntiles = (batch + TS - 1) / TS;
     const unsigned grid = static_cast<unsigned>(ntiles < n_cu ? ntiles : n_cu);
     static const int dbg = getenv("AZ_NN_CONV2_DBG") ? atoi(getenv("AZ_NN_CONV2_DBG")) & 511 : 0;

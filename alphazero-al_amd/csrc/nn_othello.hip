@@ -25,31 +25,17 @@
 //               pass that adds the residual, applies SiLU and writes whole 16-byte vectors.
 // Two workgroups share a CU (73.7 KB of LDS each), so one's copy / epilogue phases overlap the
 // other's MFMA phase.
-#include <hip/hip_bf16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
 #include "az_nn.h"
+#include "nn_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int COUT = 256;
 constexpr int ROWB = COUT * 2;            // bytes of one output token
 
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
 __device__ __forceinline__ float round_bf(float v) { return bf_lo(pack2(v, 0.0f) & 0xffffu); }
 // v * sigmoid(v) as v_mul, v_exp, v_add, v_rcp, v_mul (the IEEE division __fdividef compiles to without fast-math is
 // ten instructions per element; the result is rounded to bf16 right after)
@@ -300,17 +286,15 @@ int launch(const void *x, const void *wp, const float *pre_s, const float *pre_b
     constexpr int IMG = PW * ROWP, STAGE = HO * HO * ROWB;
     constexpr int SMEM = IMG > STAGE ? IMG : STAGE;
     auto kern = k_oth_conv<CIN, HI, PAD, PRE, RES, SILU>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-            return 2;
-        attr_set = true;
-        if (getenv("AZ_NN_VERBOSE") != nullptr) {
-            int per_cu = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, SMEM);
-            fprintf(stderr, "[az_nn] othello conv C_in=%d H=%d pad=%d: %d B LDS, %d workgroups per CU\n", CIN, HI, PAD, SMEM, per_cu);
-        }
-    }
+    static DeviceSetup setup;
+    if (setup.cus({reinterpret_cast<const void *>(kern)}, SMEM, [&] {
+            if (getenv("AZ_NN_VERBOSE") != nullptr) {
+                int per_cu = 0;
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, SMEM);
+                fprintf(stderr, "[az_nn] othello conv C_in=%d H=%d pad=%d: %d B LDS, %d workgroups per CU\n", CIN, HI, PAD, SMEM, per_cu);
+            }
+        }) == 0)
+        return 2;
     static const int dbg = getenv("AZ_OTH_DEBUG") ? atoi(getenv("AZ_OTH_DEBUG")) : 0;
     static const int64_t max_grid = getenv("AZ_OTH_GRID") ? atoll(getenv("AZ_OTH_GRID")) : 512;   // two workgroups per CU, persistent over samples
     const unsigned grid = static_cast<unsigned>(B < max_grid ? B : max_grid);
@@ -417,12 +401,8 @@ extern "C" int az_nn_othello_conv_narrow(const void *x, const void *w_packed16, 
     if (batch <= 0 || x == nullptr || w_packed16 == nullptr || y == nullptr || post_scale16 == nullptr || post_shift16 == nullptr)
         return 1;
     constexpr int SMEM = 100 * 512;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_oth_conv_narrow), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-            return 2;
-        attr_set = true;
-    }
+    static DeviceSetup setup;
+    if (setup.cus({reinterpret_cast<const void *>(k_oth_conv_narrow)}, SMEM) == 0) return 2;
     const unsigned grid = static_cast<unsigned>(batch < 768 ? batch : 768);       // three workgroups per CU
     hipLaunchKernelGGL(k_oth_conv_narrow, dim3(grid), dim3(256), SMEM, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(w_packed16), post_scale16, post_shift16,

@@ -23,34 +23,13 @@
 // The next sample's bitboards are requested before the current one is computed (two dependent loads: the compact
 // row index, then the position); the accumulators live in VGPRs (-amdgpu-mfma-vgpr-form, build.py: in AGPRs every
 // element costs a v_accvgpr_read before the SiLU can touch it).
-#include <hip/hip_bf16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
 #include "az_nn.h"
+#include "nn_common.h"
 
 namespace {
 
 constexpr int CELLS = 42, COLS = 7, COUT = 64;
 constexpr int PROWS = 48, PROW = 68;           // P in LDS: 48 token rows (42 used, the rest zero) of 68 floats (64 used)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-// v * sigmoid(v) on two elements: packed multiplies and add around the hardware exp2 / reciprocal
-__device__ __forceinline__ f32x2 silu2(f32x2 v)
-{
-    const f32x2 t = v * f32x2{-1.4426950408889634f, -1.4426950408889634f};
-    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + f32x2{1.0f, 1.0f};
-    return v * f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-}
 
 struct StemIn {
     const float    *features;          // (rows, 3, 6, 7) relative planes, or nullptr: positions

@@ -3,6 +3,8 @@
     python tools/probe_nn.py                  # all kernels, HIP-event timings at 32768 leaves
     python tools/probe_nn.py conv 0 5         # only the residual conv block, debug mode 0, 5 launches
                                               # (the form to put under rocprofv3 --pmc ...)
+    python tools/probe_nn.py dump DIR         # outputs of az_nn_attn_block / az_nn_heads / az_nn_attn_heads on seeded
+                                              # inputs as DIR/*.npy: two builds of the library must agree bit for bit
 Debug modes of the conv block (az_nn_debug): 1 skips the MFMA phase and its epilogue, 2 skips the
 epilogue and the stores, 3 both: what is left is staging + GroupNorm.
 """
@@ -18,6 +20,69 @@ from src.az_net import Connect4Net  # noqa: E402
 
 L = glue()
 L.az_nn_debug.argtypes = [C.c_int]
+
+
+def dump(outdir):
+    """The three kernels that end the evaluator on the inputs of tests/test_attn_heads_gpu.py (checkpoint weights and
+    the q-norm weight x 40, with and without a mask, compact lists): every output array, NaN canaries included, as
+    raw bits.  The kernels have no atomics, so the files of two builds are equal byte for byte or arithmetic moved."""
+    import numpy as np
+    from src import az_net
+    os.makedirs(outdir, exist_ok=True)
+    wts = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                               "g7_checkpoint_weights.npz"))
+    mod = az_net.Connect4Net(device="cuda").eval()
+    az_net.load_reference_weights(mod, {k: wts[k] for k in wts.files})
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run(tag, fast, x, mask, B, rows=None, n_rows=None):
+        mp = None if mask is None else mask.data_ptr()
+        rp = None if rows is None else rows.data_ptr()
+        npp = None if n_rows is None else n_rows.data_ptr()
+        att = (fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(), fast.kn_w.data_ptr(), fast.o_w.data_ptr())
+        y = torch.full(x.shape, float("nan"), device="cuda", dtype=x.dtype)
+        assert L.az_nn_attn_block(x.data_ptr(), *att, y.data_ptr(), B, 1e-5, npp, s) == 0
+        np.save(os.path.join(outdir, tag + "_attn_y.npy"), y.view(torch.int16).cpu().numpy())
+        y = torch.nan_to_num(y)          # rows past a compact count: the heads never read them, keep them defined
+        for name in ("heads", "attn_heads"):
+            out = [torch.full(shape, float("nan"), device="cuda") for shape in ((B, 7), (B, 3), (B,))]
+            ptrs = [t.data_ptr() for t in out]
+            if name == "heads":
+                assert L.az_nn_heads(y.data_ptr(), C.byref(fast._heads_w), mp, *ptrs, B, 1e-5, rp, npp, s) == 0
+            else:
+                assert L.az_nn_attn_heads(x.data_ptr(), *att, C.byref(fast._heads_w), mp, *ptrs, B, 1e-5, rp, npp, s) == 0
+            torch.cuda.synchronize()
+            for t, what in zip(out, ("probs", "wdl", "ml")):
+                np.save(os.path.join(outdir, "%s_%s_%s.npy" % (tag, name, what)), t.view(torch.int32).cpu().numpy())
+
+    for sharp in (False, True):
+        fast = FastConnect4Net.from_module(mod)
+        if sharp:       # scores outside the bound: the max-subtracting branch of the attention's softmax runs
+            fast.qn_w = (fast.qn_w.float() * 40.0).to(fast.qn_w.dtype).contiguous()
+        gen = torch.Generator(device="cuda").manual_seed(11)
+        for B in (1, 3, 777, 4099, 26368):
+            x = (torch.randn((B, 42, 64), device="cuda", generator=gen) * 1.5).to(torch.bfloat16)
+            mask = torch.rand((B, 7), device="cuda", generator=gen) > 0.25
+            mask[:, 3] = True
+            m8 = mask.to(torch.uint8).contiguous()
+            for mk in (m8, None):
+                run("b%d_sharp%d_mask%d" % (B, sharp, mk is not None), fast, x, mk, B)
+    fast = FastConnect4Net.from_module(mod)
+    gen = torch.Generator(device="cuda").manual_seed(12)
+    for B, live in ((9, 5), (4099, 3001), (26368, 20000)):
+        x = (torch.randn((B, 42, 64), device="cuda", generator=gen) * 1.5).to(torch.bfloat16)
+        rows = torch.randperm(B, device="cuda", generator=gen).to(torch.int32).contiguous()
+        mask = torch.rand((B, 7), device="cuda", generator=gen) > 0.25
+        mask[:, 0] = True
+        n_rows = torch.tensor([live], dtype=torch.int64, device="cuda")
+        run("compact%d_%d" % (B, live), fast, x, mask.to(torch.uint8).contiguous(), B, rows, n_rows)
+    print("dumped %d arrays to %s" % (len(os.listdir(outdir)), outdir))
+
+
+if len(sys.argv) > 2 and sys.argv[1] == "dump":
+    dump(sys.argv[2])
+    sys.exit(0)
+
 B = int(os.environ.get("PROBE_B", 32768))
 bf = torch.bfloat16
 dev = "cuda"

@@ -20,6 +20,7 @@
 struct az_nn_model {
     int kind = AZ_NN_KIND_CONNECT4_CNN;
     bool attn_heads_fused = true;        // az_nn_attn_heads in place of az_nn_attn_block + az_nn_heads
+    bool stem_fused = true;              // az_nn_stem_conv_block_positions in place of the folded stem + the first residual block
     az_nn_model_weights w{};
     az_nn_othello_weights ow{};
 };
@@ -184,6 +185,9 @@ int az_nn_model_create(const az_nn_model_weights *w, az_nn_model **out)
     // AZ_ATTN_HEADS_FUSED=0: the attention block and the heads as two launches (A/B of the fused kernel in one process)
     const char *fused = getenv("AZ_ATTN_HEADS_FUSED");
     m->attn_heads_fused = fused == nullptr || strcmp(fused, "0") != 0;
+    // AZ_STEM_FUSED=0: the folded stem and the first residual block as two launches (likewise)
+    const char *stem = getenv("AZ_STEM_FUSED");
+    m->stem_fused = stem == nullptr || strcmp(stem, "0") != 0;
     *out = m;
     return 0;
 }
@@ -326,18 +330,27 @@ static int forward_impl(const az_nn_model *m, const float *features, const az_nn
     }
     auto begin = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.start[kd][slot[kd]], hs); };
     auto end = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.stop[kd][slot[kd]], hs); };
-    begin(AZ_NN_PROFILE_STEM);
     int rc;
-    if (w.stem_frag != nullptr && w.stem_pmap != nullptr)
-        rc = positions != nullptr
-            ? az_nn_stem_folded_positions(positions, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream)
-            : az_nn_stem_folded(features, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream);
-    else
-        rc = positions != nullptr
-            ? az_nn_stem_embed_positions(positions, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream)
-            : az_nn_stem_embed(features, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream);
-    end(AZ_NN_PROFILE_STEM);
-    for (int i = 0; rc == 0 && i < w.n_blocks; ++i) {
+    int first = 0;                                        // the first residual block still to run
+    // the folded stem from positions and the first residual block as one launch (a call that carries event pairs
+    // runs the two, so that the STEM and CONV rings keep timing the kernels they are named after)
+    if (m->stem_fused && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr && w.n_blocks >= 1) {
+        rc = az_nn_stem_conv_block_positions(positions, w.stem_frag, w.stem_pmap, w.block_w[0], w.block_b[0], w.block_gamma[0],
+                                             w.block_beta[0], a, batch, w.eps, rows, n_rows, stream);
+        first = 1;
+    } else {
+        begin(AZ_NN_PROFILE_STEM);
+        if (w.stem_frag != nullptr && w.stem_pmap != nullptr)
+            rc = positions != nullptr
+                ? az_nn_stem_folded_positions(positions, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream)
+                : az_nn_stem_folded(features, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream);
+        else
+            rc = positions != nullptr
+                ? az_nn_stem_embed_positions(positions, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream)
+                : az_nn_stem_embed(features, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream);
+        end(AZ_NN_PROFILE_STEM);
+    }
+    for (int i = first; rc == 0 && i < w.n_blocks; ++i) {
         if (i == 0) begin(AZ_NN_PROFILE_CONV);
         rc = az_nn_conv_block(a, 64, w.block_w[i], w.block_b[i], w.block_gamma[i], w.block_beta[i], 1, b, batch,
                               w.eps, n_rows, stream);

@@ -51,6 +51,7 @@ def glue():
                                            vp, vp]
             L.az_nn_stem_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
             L.az_nn_stem_folded.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+            L.az_nn_stem_conv_block_positions.argtypes = [C.POINTER(Positions), vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, vp]
             L.az_nn_model_create.argtypes = [C.POINTER(ModelWeights), C.POINTER(vp)]
             L.az_nn_model_destroy.argtypes = [vp]
             L.az_nn_model_destroy.restype = None
@@ -112,6 +113,11 @@ def fold_stem(weight, bias, emb_own, emb_opp, pos_map):
     pmap = torch.zeros((48, 68), dtype=torch.float32, device=w.device)
     pmap[:CELLS, :out_c] = pm.reshape(out_c, CELLS).t()
     return frag, pmap.contiguous()
+
+
+class Positions(C.Structure):
+    """az_nn_positions of include/az_nn.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("bb_p1", "bb_p2", "turn", "sym")]
 
 
 class HeadsWeights(C.Structure):

@@ -89,6 +89,14 @@ int az_nn_stem_folded(const float *features, const void *w_frag, const float *pm
                       const int32_t *gather, const int64_t *batch_dev, void *stream);
 int az_nn_stem_folded_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap, void *y,
                                 int64_t batch, const int32_t *gather, const int64_t *batch_dev, void *stream);
+/* az_nn_stem_folded_positions followed by the first residual block - az_nn_conv_block(c_in 64, gamma, beta, residual 1) -
+ * as ONE kernel (nn_conv.hip): each wavefront computes the stem's output of its sample from the leaf's position into
+ * the tile in LDS the block would have staged from HBM, so the (batch, 42, 64) stem output is neither written nor read
+ * back.  Arguments: those of the two calls (w_frag, pmap: the stem's tables; weight_ohwi .. beta: the block's).  The
+ * arithmetic and the rounding points are those of the two kernels: y is byte-identical to the two launches. */
+int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap,
+                                    const void *weight_ohwi, const void *bias, const void *gamma, const void *beta, void *y,
+                                    int64_t batch, float eps, const int32_t *gather, const int64_t *batch_dev, void *stream);
 /* The whole gated attention block as a single MFMA kernel (nn_attn.hip):
  *   y = x + o_proj(sigmoid(gate) * softmax(qnorm(Q) knorm(K)^T / 4) V),  [Q|K|V|gate] = qkvg(RMSNorm(x))
  * (Network.py:51-93).  x, y (batch, 42, 64); qkvg_w (196, 64) row-major [out][in] with rows
@@ -98,8 +106,8 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
                      void *stream);
 /* timing experiments on az_nn_conv_block: bit 0 skips its MFMA phase, bit 1 its epilogue and
  * stores, bit 4 records per-wavefront cycle totals of its phases (az_nn_conv_profile: 8 values
- * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store - for the first
- * n / 8 wavefronts of the last launch). */
+ * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store, and for
+ * az_nn_stem_conv_block_positions the stem phase - for the first n / 8 wavefronts of the last launch). */
 int az_nn_debug(int flags);
 int az_nn_conv_profile(unsigned long long *out, int n);
 /* nn.RMSNorm over the last dimension of 64 */
@@ -151,6 +159,9 @@ int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, c
  * may be used from several host threads / streams at once; each call brings its own `scratch`
  * (device memory, az_nn_model_scratch_bytes(batch) bytes: two activation tensors).
  * rows / n_rows: the compact form described at the top (both NULL = every row 0..batch-1). */
+/* A model with the folded stem (stem_frag / stem_pmap) and n_blocks >= 1 that is given POSITIONS runs the stem and the
+ * first residual block as one launch, az_nn_stem_conv_block_positions (AZ_STEM_FUSED=0 in the environment when the
+ * object is created: the two launches; same bits either way). */
 #define AZ_NN_MAX_BLOCKS 8
 typedef struct az_nn_model_weights {
     const void *emb_own, *emb_opp, *pos;                    /* as az_nn_stem_embed */
@@ -196,7 +207,8 @@ int az_nn_model_profile_read(double *out_ms, int64_t *out_launches);
 /* The same for every kernel kind of the forward pass: the stem, the first residual block, the attention
  * block, the heads (an event pair around each on every n-th call): summed milliseconds and launches
  * per kind, in the order of AZ_NN_PROFILE_*.  A call that carries event pairs runs az_nn_attn_block and
- * az_nn_heads as two launches (the fused az_nn_attn_heads has no split to time).  Reading empties the rings. */
+ * az_nn_heads as two launches (the fused az_nn_attn_heads has no split to time), and likewise the stem and the first
+ * residual block as two (az_nn_stem_conv_block_positions has none either).  Reading empties the rings. */
 #define AZ_NN_PROFILE_STEM  0
 #define AZ_NN_PROFILE_CONV  1
 #define AZ_NN_PROFILE_ATTN  2

@@ -5,6 +5,7 @@
                                               # (the form to put under rocprofv3 --pmc ...)
     python tools/probe_nn.py dump DIR         # outputs of az_nn_attn_block / az_nn_heads / az_nn_attn_heads on seeded
                                               # inputs as DIR/*.npy: two builds of the library must agree bit for bit
+    python tools/probe_nn.py stem_conv        # the fused stem + first block against its two launches (PROBE_B leaves)
 Debug modes of the conv block (az_nn_debug): 1 skips the MFMA phase and its epilogue, 2 skips the
 epilogue and the stores, 3 both: what is left is staging + GroupNorm.
 """
@@ -15,11 +16,30 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "alphazero-al_amd"))
-from src.fast_net import FastConnect4Net, glue  # noqa: E402
+from src.fast_net import FastConnect4Net, Positions, glue  # noqa: E402
 from src.az_net import Connect4Net  # noqa: E402
 
 L = glue()
 L.az_nn_debug.argtypes = [C.c_int]
+L.az_nn_stem_folded_positions.argtypes = [C.POINTER(Positions)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3
+
+
+def random_positions(B, gen):
+    """B positions as az_nn_positions: random column heights and colours (not necessarily reachable), either side to
+    move, either symmetry id; the tensors are returned with the structure to keep them alive"""
+    h = torch.randint(0, 7, (B, 7), device="cuda", generator=gen)
+    colour = torch.randint(0, 2, (B, 7, 6), device="cuda", generator=gen)
+    bb1 = torch.zeros(B, dtype=torch.int64, device="cuda")
+    bb2 = torch.zeros_like(bb1)
+    for c in range(7):
+        for k in range(6):
+            on = h[:, c] > k
+            bb1 |= (on & (colour[:, c, k] == 1)).long() << (7 * c + k)
+            bb2 |= (on & (colour[:, c, k] == 0)).long() << (7 * c + k)
+    turn = (torch.randint(0, 2, (B,), device="cuda", generator=gen) * 2 - 1).int()
+    sym = torch.randint(0, 2, (B,), device="cuda", generator=gen).int()
+    keep = (bb1, bb2, turn, sym)
+    return Positions(*[t.data_ptr() for t in keep]), keep
 
 
 def dump(outdir):
@@ -67,7 +87,26 @@ def dump(outdir):
             m8 = mask.to(torch.uint8).contiguous()
             for mk in (m8, None):
                 run("b%d_sharp%d_mask%d" % (B, sharp, mk is not None), fast, x, mk, B)
+    # the fused stem + first residual block and the two launches it replaces: y, NaN canary behind a compact count
     fast = FastConnect4Net.from_module(mod)
+    gen = torch.Generator(device="cuda").manual_seed(14)
+    blk = [getattr(fast, n).data_ptr() for n in fast.res[0]]
+    tabs = (fast.stem_frag.data_ptr(), fast.stem_pmap.data_ptr())
+    for B, live in ((1, None), (3, None), (777, None), (4099, None), (26368, None), (9, 5), (4099, 3001), (26368, 20000)):
+        pos, keep = random_positions(B, gen)
+        rows = n_rows = rp = npp = None
+        if live is not None:
+            rows = torch.randperm(B, device="cuda", generator=gen).to(torch.int32).contiguous()
+            n_rows = torch.tensor([live], dtype=torch.int64, device="cuda")
+            rp, npp = rows.data_ptr(), n_rows.data_ptr()
+        ys = [torch.full((B, 42, 64), float("nan"), device="cuda", dtype=torch.bfloat16) for _ in range(3)]
+        assert L.az_nn_stem_conv_block_positions(C.byref(pos), *tabs, *blk, ys[0].data_ptr(), B, 1e-5, rp, npp, s) == 0
+        assert L.az_nn_stem_folded_positions(C.byref(pos), *tabs, ys[1].data_ptr(), B, rp, npp, s) == 0
+        assert L.az_nn_conv_block(ys[1].data_ptr(), 64, *blk, 1, ys[2].data_ptr(), B, 1e-5, npp, s) == 0
+        torch.cuda.synchronize()
+        tag = "b%d" % B if live is None else "compact%d_%d" % (B, live)
+        np.save(os.path.join(outdir, tag + "_stem_conv_y.npy"), ys[0].view(torch.int16).cpu().numpy())
+        np.save(os.path.join(outdir, tag + "_stem_then_conv_y.npy"), ys[2].view(torch.int16).cpu().numpy())
     gen = torch.Generator(device="cuda").manual_seed(12)
     for B, live in ((9, 5), (4099, 3001), (26368, 20000)):
         x = (torch.randn((B, 42, 64), device="cuda", generator=gen) * 1.5).to(torch.bfloat16)
@@ -139,7 +178,24 @@ def attn_heads():
                        ml.data_ptr(), B, 1e-5, None, None, s)
 
 
-KERNELS = {"conv": conv, "stem": stem, "stem_embed": stem_embed, "stem_folded": stem_folded, "attn": attn, "heads": heads,
+pos_c, pos_keep = random_positions(B, torch.Generator(device="cuda").manual_seed(5))
+
+
+def stem_pos():
+    L.az_nn_stem_folded_positions(C.byref(pos_c), net.stem_frag.data_ptr(), net.stem_pmap.data_ptr(), x.data_ptr(), B, None, None, s)
+
+
+def stem_then_conv():
+    stem_pos()
+    conv()
+
+
+def stem_conv():
+    L.az_nn_stem_conv_block_positions(C.byref(pos_c), net.stem_frag.data_ptr(), net.stem_pmap.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                      g.data_ptr(), be.data_ptr(), y.data_ptr(), B, 1e-5, None, None, s)
+
+
+KERNELS = {"stem_pos": stem_pos, "stem_then_conv": stem_then_conv, "stem_conv": stem_conv, "conv": conv, "stem": stem, "stem_embed": stem_embed, "stem_folded": stem_folded, "attn": attn, "heads": heads,
            "attn_heads": attn_heads}
 
 
@@ -156,7 +212,30 @@ def timed(fn, n=20):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-if len(sys.argv) > 1:
+def stem_conv_report():
+    """the fused kernel against the two launches it replaces, and where its cycles go (az_nn_debug bit 4)"""
+    import numpy as np
+    L.az_nn_debug(0)
+    t = {k: timed(KERNELS[k]) for k in ("stem_pos", "conv", "stem_then_conv", "stem_conv")}
+    print("at %d leaves: stem (positions) %.1f us, block %.1f us, both %.1f us; fused %.1f us"
+          % (B, t["stem_pos"], t["conv"], t["stem_then_conv"], t["stem_conv"]))
+    L.az_nn_debug(16)
+    stem_conv()
+    torch.cuda.synchronize()
+    buf = np.zeros(2048 * 8, dtype=np.uint64)
+    L.az_nn_conv_profile.argtypes = [C.c_void_p, C.c_int]
+    L.az_nn_conv_profile(buf.ctypes.data, buf.size)
+    L.az_nn_debug(0)
+    ph = buf.reshape(2048, 8)[:, :7].astype(np.float64)
+    names = ("P1 norm->img", "barrier 1", "MFMA+epilogue", "wait staged tile", "barrier 2", "P3 store", "P0 stem")
+    for k, nm in enumerate(names):
+        print("   fused %-18s mean %9.0f ticks/wave (%4.1f%%)" % (nm, ph[:, k].mean(), 100 * ph[:, k].mean() / ph.sum(1).mean()))
+    return t
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "stem_conv" and len(sys.argv) == 2:
+    stem_conv_report()
+elif len(sys.argv) > 1:
     fn = KERNELS[sys.argv[1]]
     L.az_nn_debug(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
     for _ in range(int(sys.argv[3]) if len(sys.argv) > 3 else 5):
@@ -183,3 +262,4 @@ else:
     L.az_nn_debug(0)
     for name in ("stem", "stem_embed", "attn", "heads"):
         print("%-27s %7.1f us" % (name, timed(KERNELS[name])))
+    stem_conv_report()

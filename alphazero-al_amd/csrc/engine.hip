@@ -1504,6 +1504,9 @@ struct az_selfplay {
     } rec, fin;
     DevBuf<int32_t> fin_slot, fin_len, fin_winner;
     DevBuf<int64_t> fin_ply, fin_row0;
+    // az_selfplay_export: the games' figures in export order, as the kernel reads them
+    DevBuf<int32_t> exp_len, exp_winner;
+    DevBuf<int64_t> exp_src, exp_dst;
     int64_t capacity = 0;
     int64_t driver_ply = 0;        // plies finished: the sampler's call counter
     int64_t dropped = 0;           // games dropped before the last drain
@@ -1631,6 +1634,7 @@ int az_selfplay_create(az_mcts *m, const az_selfplay_config *c, az_selfplay **ou
             sp->fin.ensure(static_cast<size_t>(sp->capacity) * (sp->rows_per_game + 1), sp->A);
             const size_t G = static_cast<size_t>(sp->capacity);
             sp->fin_slot.ensure(G); sp->fin_len.ensure(G); sp->fin_winner.ensure(G); sp->fin_ply.ensure(G); sp->fin_row0.ensure(G);
+            sp->exp_len.ensure(G); sp->exp_winner.ensure(G); sp->exp_src.ensure(G); sp->exp_dst.ensure(G);
         }
         for (auto &e : sp->ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         // the games start over: so do the trees (flushed by the first search's az_mcts_dev_prepare)
@@ -1771,6 +1775,104 @@ int az_selfplay_drain(az_selfplay *sp, const az_selfplay_games *out, int64_t n_g
         }
         sp->dropped = d;
         HIP_OK(hipMemset(sp->alloc.p, 0, 2 * sizeof(unsigned long long)));
+    });
+}
+
+namespace {
+az::SpExport export_args(const az_replay_tensors *dst, int64_t ptr, int td_steps, const char *who)
+{
+    const std::string w(who);
+    require(dst != nullptr, w + ": null tensors");
+    require(dst->capacity > 0, w + ": capacity must be positive");
+    require(ptr >= 0 && td_steps >= 0, w + ": ptr and td_steps must not be negative");
+    const void *t[8] = {dst->state, dst->prob, dst->winner, dst->steps_to_end, dst->aux_target, dst->root_wdl,
+                        dst->valid_mask, dst->future_root_wdl};
+    for (const void *q : t) {
+        require(q != nullptr, w + ": a null tensor");
+        require(reinterpret_cast<uintptr_t>(q) % 16 == 0, w + ": a tensor is not 16-byte aligned");
+    }
+    az::SpExport a{};
+    a.state = dst->state; a.prob = dst->prob; a.out_winner = dst->winner; a.steps_to_end = dst->steps_to_end;
+    a.aux_target = dst->aux_target; a.root_wdl = dst->root_wdl; a.valid_mask = dst->valid_mask;
+    a.future_root_wdl = dst->future_root_wdl; a.capacity = dst->capacity; a.ptr = ptr; a.td_steps = td_steps;
+    return a;
+}
+}  // namespace
+
+int az_selfplay_export(az_selfplay *sp, const az_replay_tensors *dst, int64_t ptr, int td_steps, int64_t n_games,
+                       int64_t n_rows, const az_selfplay_export_info *info, int64_t *new_ptr, void *stream)
+{
+    return guarded([&] {
+        require(sp != nullptr, "az_selfplay_export: null driver");
+        require(sp->c.record != 0, "az_selfplay_export: the driver does not record");
+        az::SpExport a = export_args(dst, ptr, td_steps, "az_selfplay_export");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        HIP_OK(hipSetDevice(sp->m->device));
+        HIP_OK(hipDeviceSynchronize());
+        int64_t g, r, d;
+        sp->store_figures(g, r, d);
+        require(g == n_games && r == n_rows, "az_selfplay_export: sizes differ from what az_selfplay_finished reports");
+        const size_t G = static_cast<size_t>(g);
+        // per-game figures only: the rows stay where they are
+        std::vector<int32_t> slot, len, win;
+        std::vector<int64_t> fply, row0;
+        fetch(slot, sp->fin_slot.p, G); fetch(len, sp->fin_len.p, G); fetch(win, sp->fin_winner.p, G);
+        fetch(fply, sp->fin_ply.p, G); fetch(row0, sp->fin_row0.p, G);
+        std::vector<size_t> order(G);
+        for (size_t i = 0; i < G; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+            return fply[x] != fply[y] ? fply[x] < fply[y] : slot[x] < slot[y];
+        });
+        std::vector<int32_t> e_len(G), e_win(G);
+        std::vector<int64_t> e_src(G), e_dst(G);
+        int64_t at = 0;
+        for (size_t k = 0; k < G; ++k) {
+            const size_t i = order[k];
+            const int64_t rows = static_cast<int64_t>(len[i]) + 1;
+            if (len[i] < 0 || row0[i] < 0 || row0[i] + rows > r || at + rows > r)
+                throw AzError(AZ_ERR_STATE, "az_selfplay_export: the finished store is inconsistent");
+            e_len[k] = len[i]; e_win[k] = win[i]; e_src[k] = row0[i]; e_dst[k] = at;
+            if (info != nullptr) {
+                if (info->slot) info->slot[k] = slot[i];
+                if (info->length) info->length[k] = len[i];
+                if (info->winner) info->winner[k] = win[i];
+                if (info->finish_ply) info->finish_ply[k] = fply[i];
+            }
+            at += rows;
+        }
+        if (at != r) throw AzError(AZ_ERR_STATE, "az_selfplay_export: the finished store is inconsistent");
+        if (G) {
+            // the device is idle (waited for above): plain copies, nothing of the driver's reads these buffers now
+            HIP_OK(hipMemcpy(sp->exp_len.p, e_len.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(sp->exp_winner.p, e_win.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(sp->exp_src.p, e_src.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(sp->exp_dst.p, e_dst.data(), G * sizeof(int64_t), hipMemcpyHostToDevice));
+            a.fin = sp->fin.view();
+            a.len = sp->exp_len.p; a.winner = sp->exp_winner.p; a.src_row0 = sp->exp_src.p; a.dst_row0 = sp->exp_dst.p;
+            a.n_games = g;
+            az::launch_sp_export(sp->m->game, a, s);
+        }
+        // the store empties BEHIND the kernel on the caller's stream: the next ply's k_sp_advance, enqueued after
+        // this call on that stream, hands out rows from 0 again only once the kernel has read them
+        HIP_OK(hipMemsetAsync(sp->alloc.p, 0, 2 * sizeof(unsigned long long), s));
+        sp->dropped = d;
+        if (new_ptr) *new_ptr = ptr + r;
+    });
+}
+
+int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int64_t *src_row0, const int64_t *dst_row0,
+                        int64_t n_games, const az_replay_tensors *dst, int64_t ptr, int td_steps, void *stream)
+{
+    return guarded([&] {
+        require(game == AZ_GAME_CONNECT4 || game == AZ_GAME_OTHELLO, "az_replay_dev_store: unknown game");
+        require(games_dev != nullptr && src_row0 != nullptr && dst_row0 != nullptr && n_games >= 0, "az_replay_dev_store: bad argument");
+        require(games_dev->length && games_dev->winner && games_dev->bb_p1 && games_dev->bb_p2 && games_dev->turn &&
+                games_dev->prob && games_dev->wdl && games_dev->mask, "az_replay_dev_store: a null array");
+        az::SpExport a = export_args(dst, ptr, td_steps, "az_replay_dev_store");
+        a.fin = az::SpRows{games_dev->bb_p1, games_dev->bb_p2, games_dev->turn, games_dev->prob, games_dev->wdl, games_dev->mask};
+        a.len = games_dev->length; a.winner = games_dev->winner; a.src_row0 = src_row0; a.dst_row0 = dst_row0;
+        a.n_games = n_games;
+        az::launch_sp_export(game, a, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -207,4 +207,24 @@ struct SpAdvance {
 void launch_sp_pick(int game, SpPick a, bool record, hipStream_t s);
 void launch_sp_advance(int game, SpAdvance a, hipStream_t s);
 
+// Packed games -> replay-buffer rows in a ring (k_sp_export; az_replay_tensors in az_mcts.h).  Game g: rows
+// src_row0[g] .. src_row0[g] + len[g] of `fin`, written to the ring slots (ptr + dst_row0[g] + t) % capacity.
+// dst_row0 ascends and is packed: the call carries dst_row0[n-1] + len[n-1] + 1 rows.
+struct SpExport {
+    SpRows fin;                              // read only
+    const int32_t *len, *winner;             // [n_games]
+    const int64_t *src_row0, *dst_row0;      // [n_games]
+    int64_t  n_games;
+    int8_t  *state;                          // [capacity][3][ROWS][COLS]
+    float   *prob;                           // [capacity][A]
+    int8_t  *out_winner;                     // [capacity]
+    int16_t *steps_to_end, *aux_target;      // [capacity]
+    float   *root_wdl, *future_root_wdl;     // [capacity][3]
+    uint8_t *valid_mask;                     // [capacity][A]
+    int64_t  capacity, ptr;
+    int      td_steps;
+};
+
+void launch_sp_export(int game, SpExport a, hipStream_t s);
+
 }  // namespace az

@@ -10,6 +10,11 @@
 //                 finished store, refill, next ply's noise epsilon (game.py:87-91), running totals.
 //                 One lane per game for the bookkeeping; a wavefront then copies the rows of ITS
 //                 finished games together - bytes moved follow the games that ended, not slots x plies.
+//   k_sp_export   the packed store of finished games -> the learner's replay-buffer rows, written in place
+//                 into a ring in HBM: what game.py:110-157 (winner per row, steps to the end, the auxiliary
+//                 target, the td-step column, the end-state row) followed by ReplayBuffer.py:92-123 (`store`,
+//                 row by row, index _ptr % capacity) leaves there.  One workgroup per game; consecutive
+//                 lanes write consecutive bytes of consecutive ring rows.
 //
 // Plain C++ and vector stores only.  Store rows are handed out per WAVEFRONT: a ballot counts the
 // finished games, one lane adds the wave's figures to the two counters (games, rows), ranks come from
@@ -239,6 +244,107 @@ __global__ void __launch_bounds__(WAVE) k_sp_advance(SpAdvance a)
     }
 }
 
+// ---- k_sp_export --------------------------------------------------------------------------------------
+// The bit of a cell of the [ROWS][COLS] planes (env_common.h:93-119): Connect4 keeps bit 7 * col + height and
+// draws row 0 at the top; Othello keeps bit 8 * row + col.
+template <class G>
+__device__ __forceinline__ int cell_bit(int cell)
+{
+    if (G::GAME_ID == Connect4Dev::GAME_ID) return 7 * (cell % G::COLS) + (G::ROWS - 1 - cell / G::COLS);
+    return cell;
+}
+
+// byte k of a state row: plane 0 the stones of the side to move, plane 1 the opponent's, plane 2 the turn sign
+template <class G>
+__device__ __forceinline__ uint32_t state_byte(uint64_t own, uint64_t opp, int turn, int k)
+{
+    const int plane = k / G::CELLS, cell = k % G::CELLS;
+    if (plane == 2) return static_cast<uint8_t>(static_cast<int8_t>(turn));
+    return static_cast<uint32_t>(((plane == 0 ? own : opp) >> cell_bit<G>(cell)) & 1ull);
+}
+
+// A state row in units of one store: Connect4's 126-byte rows keep consecutive rows 2-byte aligned (63 stores of
+// 2 bytes), Othello's 192-byte rows 16-byte aligned (12 stores of 16 bytes).
+template <class G> struct StateUnit { using type = uint16_t; };
+template <> struct StateUnit<OthelloDev> { using type = uint4; };
+
+template <class G>
+__device__ __forceinline__ void state_unit(uint64_t own, uint64_t opp, int turn, int u, uint16_t &out)
+{
+    out = static_cast<uint16_t>(state_byte<G>(own, opp, turn, 2 * u) | (state_byte<G>(own, opp, turn, 2 * u + 1) << 8));
+}
+
+template <class G>
+__device__ __forceinline__ void state_unit(uint64_t own, uint64_t opp, int turn, int u, uint4 &out)
+{
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        w[i] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[i] |= state_byte<G>(own, opp, turn, 16 * u + 4 * i + j) << (8 * j);
+    }
+    out = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+constexpr int EXPORT_THREADS = 256;
+
+template <class G>
+__global__ void __launch_bounds__(EXPORT_THREADS) k_sp_export(SpExport a)
+{
+    using Unit = typename StateUnit<G>::type;
+    constexpr int A = G::ACTIONS;
+    constexpr int UNITS = 3 * G::CELLS / static_cast<int>(sizeof(Unit));
+    static_assert(UNITS * sizeof(Unit) == 3 * G::CELLS, "a state row is a whole number of stores");
+    const int tid = threadIdx.x;
+    const int64_t g = blockIdx.x;
+    const int T = a.len[g], win = a.winner[g];
+    const int64_t src = a.src_row0[g], dst = a.dst_row0[g], cap = a.capacity;
+    // ring rule: of a call with more rows than the ring has slots only the last `capacity` rows are written -
+    // what row-by-row stores would leave, and no two rows of one call share a slot
+    const int64_t total = a.dst_row0[a.n_games - 1] + a.len[a.n_games - 1] + 1;
+    const int64_t skip = total > cap ? total - cap : 0;
+    const int t0 = dst >= skip ? 0 : static_cast<int>(skip - dst < T + 1 ? skip - dst : T + 1);
+    const int n = T + 1 - t0;                                  // rows of this game that are written: <= capacity
+    if (n <= 0) return;
+    const int64_t base = (a.ptr + dst + t0) % cap;             // the modulo once per game, the wrap per row
+    auto slot = [&](int j) { const int64_t i = base + j; return static_cast<size_t>(i >= cap ? i - cap : i); };
+
+    const uint64_t end0 = a.fin.bb0[src + T], end1 = a.fin.bb1[src + T];
+    const int diff = __popcll(end0) - __popcll(end1);          // game.py:17-30: discs of player +1 minus player -1
+
+    Unit *state = reinterpret_cast<Unit *>(a.state);
+    for (int e = tid; e < n * UNITS; e += EXPORT_THREADS) {
+        const int j = e / UNITS, u = e % UNITS;
+        const size_t r = static_cast<size_t>(src) + t0 + j;
+        const int turn = a.fin.turn[r];
+        const uint64_t p1 = a.fin.bb0[r], p2 = a.fin.bb1[r];
+        Unit v;
+        state_unit<G>(turn > 0 ? p1 : p2, turn > 0 ? p2 : p1, turn, u, v);
+        state[slot(j) * UNITS + u] = v;
+    }
+    for (int e = tid; e < n * A; e += EXPORT_THREADS) {
+        const int j = e / A, c = e % A, t = t0 + j;
+        const size_t from = (static_cast<size_t>(src) + t) * A + c, to = slot(j) * A + c;
+        a.prob[to] = t < T ? a.fin.prob[from] : 0.0f;
+        a.valid_mask[to] = t < T ? (a.fin.mask[from] != 0 ? 1 : 0) : 1;
+    }
+    for (int e = tid; e < n * 3; e += EXPORT_THREADS) {
+        const int j = e / 3, c = e % 3, t = t0 + j;
+        const size_t from = (static_cast<size_t>(src) + t) * 3 + c, to = slot(j) * 3 + c;
+        a.root_wdl[to] = t < T ? a.fin.wdl[from] : 0.0f;
+        a.future_root_wdl[to] = (a.td_steps > 0 && a.td_steps < T - t) ? a.fin.wdl[from + static_cast<size_t>(a.td_steps) * 3] : 0.0f;
+    }
+    for (int j = tid; j < n; j += EXPORT_THREADS) {
+        const int t = t0 + j;
+        const size_t to = slot(j);
+        a.out_winner[to] = static_cast<int8_t>(win);
+        a.steps_to_end[to] = static_cast<int16_t>(T - t);
+        if (G::GAME_ID == OthelloDev::GAME_ID) a.aux_target[to] = static_cast<int16_t>(diff * a.fin.turn[static_cast<size_t>(src) + t]);
+        else a.aux_target[to] = static_cast<int16_t>(T - t);
+    }
+}
+
 }  // namespace
 
 #define AZ_SP_DISPATCH(game, ...)                                                  \
@@ -261,6 +367,12 @@ void launch_sp_advance(int game, SpAdvance a, hipStream_t s)
 {
     if (a.n <= 0) return;
     AZ_SP_DISPATCH(game, hipLaunchKernelGGL(k_sp_advance<G>, dim3(static_cast<unsigned>((a.n + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a));
+}
+
+void launch_sp_export(int game, SpExport a, hipStream_t s)
+{
+    if (a.n_games <= 0) return;
+    AZ_SP_DISPATCH(game, hipLaunchKernelGGL(k_sp_export<G>, dim3(static_cast<unsigned>(a.n_games)), dim3(EXPORT_THREADS), 0, s, a));
 }
 
 }  // namespace az

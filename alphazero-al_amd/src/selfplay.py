@@ -30,6 +30,12 @@ global generator (player.py:348-371).  The noise-epsilon decay over the plies of
 include/az_mcts.h): the move, the recording, refill, epsilon decay and totals are two HIP kernels
 (csrc/selfplay_kernels.hip) instead of torch calls, and a step with a native evaluator model is one
 call into the library.  `DeviceSelfPlay` stays what bench.py times.
+
+For a learner on the same GPU the finished games need not leave HBM at all: `ReplayTensors` is the reference
+learner's dense buffer layout (ReplayBuffer.py:11-23), `NativeSelfPlay.export(buffer)` writes the finished
+store into it as replay rows with one kernel (k_sp_export through az_selfplay_export: what game.py:110-157
+followed by ReplayBuffer.py:92-123 would leave there), and `ReplayTensors.store_games(drain())` is the same
+thing by the host route, for any driver.
 """
 
 import ctypes as C
@@ -320,6 +326,17 @@ class SelfPlayGames(C.Structure):
                                           "turn", "prob", "wdl", "mask")]
 
 
+class ReplayTensorsC(C.Structure):
+    """az_replay_tensors (include/az_mcts.h): device pointers of a replay buffer's tensors and its capacity."""
+    _fields_ = [(n, C.c_void_p) for n in ("state", "prob", "winner", "steps_to_end", "aux_target", "root_wdl",
+                                          "valid_mask", "future_root_wdl")] + [("capacity", C.c_int64)]
+
+
+class SelfPlayExportInfo(C.Structure):
+    """az_selfplay_export_info (include/az_mcts.h): host arrays az_selfplay_export fills."""
+    _fields_ = [(n, C.c_void_p) for n in ("slot", "length", "winner", "finish_ply")]
+
+
 def selfplay_lib():
     """The engine library with the az_selfplay_* prototypes set."""
     L = F.lib()
@@ -337,6 +354,9 @@ def selfplay_lib():
         L.az_selfplay_finished.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.az_selfplay_drain.argtypes = [vp, C.POINTER(SelfPlayGames), i64, i64]
         L.az_selfplay_sample.argtypes = [i32, vp, vp, C.POINTER(SelfPlayConfig), u64, u64, vp, i64, vp]
+        L.az_selfplay_export.argtypes = [vp, C.POINTER(ReplayTensorsC), i64, i32, i64, i64, C.POINTER(SelfPlayExportInfo),
+                                         C.POINTER(i64), vp]
+        L.az_replay_dev_store.argtypes = [i32, C.POINTER(SelfPlayGames), vp, vp, i64, C.POINTER(ReplayTensorsC), i64, i32, vp]
         L._az_selfplay_ready = True
     return L
 
@@ -353,6 +373,106 @@ def drain_native(L, handle, action_size):
     out = SelfPlayGames(**{k: v.ctypes.data for k, v in list(per_game.items()) + list(per_row.items())})
     F.check(L.az_selfplay_drain(handle, C.byref(out), n, rows))
     return per_game, per_row
+
+
+REPLAY_GEOMETRY = {"Connect4": (7, 6, 7), "Othello": (65, 8, 8)}       # actions, rows, columns
+
+
+class ReplayTensors:
+    """The dense tensors the reference's learner keeps its positions in (ReplayBuffer.py:11-23), as a plain
+    container: same attribute names, dtypes and shapes, the ring rule of `store` (ReplayBuffer.py:92-123: row
+    number `_ptr` goes to index `_ptr % current_capacity`), `__len__` and `get`.  Sampling, persistence and the
+    replay ratio are the learner's and are not here.  `state` and `prob`, which the reference leaves
+    uninitialised, start as zeros; the rest starts as the reference's does.
+
+    Rows arrive from `NativeSelfPlay.export(self)` (on the device, no host copy) or `store_games(drain())` (any
+    driver, any device, the CPU included)."""
+
+    def __init__(self, game, capacity, device="cpu"):
+        assert game in REPLAY_GEOMETRY and int(capacity) > 0
+        A, R, Cc = REPLAY_GEOMETRY[game]
+        cap = int(capacity)
+        self.game = game
+        self.device = torch.device(device)
+        z = dict(device=self.device)
+        self.state = torch.zeros((cap, 3, R, Cc), dtype=torch.int8, **z)
+        self.prob = torch.zeros((cap, A), dtype=torch.float32, **z)
+        self.winner = torch.zeros((cap, 1), dtype=torch.int8, **z)
+        self.steps_to_end = torch.zeros((cap, 1), dtype=torch.int16, **z)
+        self.aux_target = torch.zeros((cap, 1), dtype=torch.int16, **z)
+        self.root_wdl = torch.zeros((cap, 3), dtype=torch.float32, **z)
+        self.future_root_wdl = torch.zeros((cap, 3), dtype=torch.float32, **z)
+        self.valid_mask = torch.ones((cap, A), dtype=torch.bool, **z)
+        self.current_capacity = cap
+        self._ptr = 0
+
+    TENSORS = ("state", "prob", "winner", "steps_to_end", "aux_target", "root_wdl", "valid_mask", "future_root_wdl")
+
+    def __len__(self):
+        return min(self._ptr, len(self.state))
+
+    def get(self, indices):
+        return (self.state[indices].float(), self.prob[indices], self.winner[indices], self.steps_to_end[indices],
+                self.aux_target[indices], self.root_wdl[indices], self.valid_mask[indices], self.future_root_wdl[indices])
+
+    def store_games(self, games):
+        """The host route: `games` as any driver's `drain()` returns them, a list of (winner, play_data, slot);
+        every tuple of every play_data becomes one row, in order, as `buffer.store(*data)` per tuple would
+        (server.py:300-302).  One indexed assignment per column and game.  Returns the rows stored."""
+        cap = self.current_capacity
+        n_rows = 0
+        for _winner, play, *_ in games:
+            n = len(play)
+            cols = list(zip(*play))
+            keep = slice(max(0, n - cap), n)              # a game longer than the ring: its last rows survive
+            idx = torch.from_numpy(((self._ptr + np.arange(n, dtype=np.int64)) % cap)[keep]).to(self.device)
+
+            def put(dst, col, dtype):
+                a = np.ascontiguousarray(np.stack([np.asarray(x) for x in col[keep]]).astype(dtype, copy=False))
+                dst[idx] = torch.from_numpy(a).to(self.device).reshape((len(a),) + tuple(dst.shape[1:]))
+            put(self.state, cols[0], np.int8)
+            put(self.prob, cols[1], np.float32)
+            put(self.winner, cols[2], np.int8)
+            put(self.steps_to_end, cols[3], np.int16)
+            put(self.aux_target, cols[4], np.int16)
+            put(self.root_wdl, cols[5], np.float32)
+            put(self.valid_mask, cols[6], np.bool_)
+            if len(cols) > 7:
+                put(self.future_root_wdl, cols[7], np.float32)
+            else:
+                self.future_root_wdl[idx] = 0
+            self._ptr += n
+            n_rows += n
+        return n_rows
+
+
+def replay_tensors_c(buffer, game, device):
+    """az_replay_tensors of `buffer` (a ReplayTensors or anything with its attributes, the reference's
+    ReplayBuffer included) after checking that k_sp_export may write it: ValueError otherwise."""
+    A, R, Cc = REPLAY_GEOMETRY[game]
+    try:
+        cap = int(buffer.current_capacity)
+        tensors = {n: getattr(buffer, n) for n in ReplayTensors.TENSORS}
+        int(buffer._ptr)
+    except AttributeError as e:
+        raise ValueError("export: the buffer lacks %s" % e)
+    if cap <= 0:
+        raise ValueError("export: the buffer's capacity must be positive")
+    want = dict(state=(torch.int8, (3, R, Cc)), prob=(torch.float32, (A,)), winner=(torch.int8, (1,)),
+                steps_to_end=(torch.int16, (1,)), aux_target=(torch.int16, (1,)), root_wdl=(torch.float32, (3,)),
+                valid_mask=(torch.bool, (A,)), future_root_wdl=(torch.float32, (3,)))
+    dev = torch.device(device)
+    for n, t in tensors.items():
+        dtype, tail = want[n]
+        if not isinstance(t, torch.Tensor) or t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+            raise ValueError("export: buffer.%s is not a tensor on %s" % (n, dev))
+        if t.dtype != dtype or tuple(t.shape[1:]) != tail:
+            raise ValueError("export: buffer.%s must be %s [capacity]%s, not %s %s" % (n, dtype, list(tail), t.dtype, list(t.shape)))
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("export: buffer.%s must be contiguous and 16-byte aligned" % n)
+        if t.shape[0] < cap:
+            raise ValueError("export: buffer.%s has %d rows, fewer than current_capacity %d" % (n, t.shape[0], cap))
+    return ReplayTensorsC(*(tensors[n].data_ptr() for n in ReplayTensors.TENSORS), cap)
 
 
 class NativeSelfPlay:
@@ -447,6 +567,24 @@ class NativeSelfPlay:
             return bb1[a:b], bb2[a:b], r["turn"][a:b], r["prob"][a:b], r["wdl"][a:b], mask[a:b]
         return assemble_games(self.game, self.td_steps, g["length"], g["winner"], g["slot"], rows_of)
 
+    def export(self, buffer):
+        """The finished store into `buffer` (a ReplayTensors on this driver's device, or any object with its
+        attributes there - the reference's ReplayBuffer qualifies) as replay rows, in drain()'s game order and
+        with this driver's td_steps: k_sp_export, no row crosses to the host.  Advances `buffer._ptr`, empties
+        the store; returns the exported games' slot / length / winner / finish_ply as numpy arrays."""
+        assert self.record
+        dst = replay_tensors_c(buffer, self.game, self.device)
+        n, rows, _ = self.finished()
+        info = dict(slot=np.zeros(n, np.int32), length=np.zeros(n, np.int32), winner=np.zeros(n, np.int32),
+                    finish_ply=np.zeros(n, np.int64))
+        c_info = SelfPlayExportInfo(**{k: v.ctypes.data for k, v in info.items()})
+        new_ptr = C.c_int64()
+        with torch.cuda.device(self.device):
+            F.check(self.L.az_selfplay_export(self._sp, C.byref(dst), int(buffer._ptr), self.td_steps, n, rows,
+                                              C.byref(c_info), C.byref(new_ptr), F._stream()))
+        buffer._ptr = new_ptr.value
+        return info
+
     def read_totals(self):
         t = (C.c_int64 * 5)()
         F.check(self.L.az_selfplay_totals(self._sp, C.byref(t)))         # synchronises
@@ -522,6 +660,20 @@ class StreamedSelfPlay:
             with torch.cuda.stream(st):
                 games += [(w, play, slot + off) for (w, play, slot) in part.drain()]
         return games
+
+    def export(self, buffer):
+        """`driver="native"`: every driver's finished store into `buffer`, one driver after the other in
+        drain()'s group order; the returned slots are global.  The buffer is complete after `synchronize()`."""
+        assert self.driver == "native", "StreamedSelfPlay.export needs driver='native'"
+        self.synchronize()
+        out = {}
+        for off, part, st in zip(self.offsets, self.parts, self.streams):
+            with torch.cuda.stream(st):
+                info = part.export(buffer)
+            info["slot"] = info["slot"] + np.int32(off)
+            for k, v in info.items():
+                out[k] = np.concatenate([out[k], v]) if k in out else v
+        return out
 
     def read_totals(self):
         self.synchronize()

@@ -331,6 +331,70 @@ typedef struct az_selfplay_games {
 /* Copies the store out in the order (finishing ply, slot) and empties it (synchronises); n_games and
  * n_rows must be what az_selfplay_finished just reported. */
 int az_selfplay_drain(az_selfplay *sp, const az_selfplay_games *out, int64_t n_games, int64_t n_rows);
+
+/* ---- finished games as replay-buffer rows, on the device (k_sp_export) -----------------------------------
+ * The reference's learner keeps every position in dense tensors (src/ReplayBuffer.py:11-23) and fills them
+ * row by row: `store` (ReplayBuffer.py:92-123) writes row number _ptr to index _ptr % capacity, and a game
+ * arrives as the tuples of src/game.py:110-157.  az_replay_tensors names such tensors in DEVICE memory, all
+ * contiguous and 16-byte aligned, `capacity` rows each; A = 7 and R x C = 6 x 7 (Connect4), A = 65 and 8 x 8
+ * (Othello).  A game of T moves is T + 1 rows; row t (0 <= t <= T, t = T the end state) holds
+ *   state            the position as three planes: stones of the side to move, stones of the opponent, the
+ *                    turn sign (+1 / -1) in every cell; Connect4: cell (r, c) is bit 7 c + (5 - r) of a
+ *                    bitboard (row 0 is the top), Othello: bit 8 r + c
+ *   prob             t < T: the visit distribution of the row; end state: zeros
+ *   winner           the game's winner (+1 / -1 / 0) in every row
+ *   steps_to_end     T - t
+ *   aux_target       Connect4: T - t.  Othello: (discs of player +1 - discs of player -1 in the END state)
+ *                    x the side to move of row t
+ *   root_wdl         t < T: the root's [draw, p1, p2] of the row; end state: zeros
+ *   valid_mask       t < T: the legal-move mask of the row (bytes 0 / 1); end state: all ones
+ *   future_root_wdl  root_wdl of row t + td_steps of the same game if td_steps > 0 and t + td_steps < T,
+ *                    zeros otherwise
+ * Floats are copied bit for bit.  Row number r of a call (its games in order, rows in order) goes to index
+ * (ptr + r) % capacity; of a call that carries more rows than `capacity` only the last `capacity` rows are
+ * written, which is what storing them one by one would leave. */
+typedef struct az_replay_tensors {
+    int8_t  *state;             /* [capacity][3][R][C] */
+    float   *prob;              /* [capacity][A] */
+    int8_t  *winner;            /* [capacity] */
+    int16_t *steps_to_end;      /* [capacity] */
+    int16_t *aux_target;        /* [capacity] */
+    float   *root_wdl;          /* [capacity][3] */
+    uint8_t *valid_mask;        /* [capacity][A], one byte per entry */
+    float   *future_root_wdl;   /* [capacity][3] */
+    int64_t  capacity;
+} az_replay_tensors;
+#define AZ_REPLAY_TENSORS_BYTES 72
+#ifdef __cplusplus
+static_assert(sizeof(az_replay_tensors) == AZ_REPLAY_TENSORS_BYTES, "az_replay_tensors layout");
+#else
+_Static_assert(sizeof(az_replay_tensors) == AZ_REPLAY_TENSORS_BYTES, "az_replay_tensors layout");
+#endif
+/* HOST arrays of n_games entries each, filled in export order, any of them NULL: what a caller's statistics
+ * need of the exported games (server.py:304 keeps the episode lengths). */
+typedef struct az_selfplay_export_info {
+    int32_t *slot, *length, *winner;
+    int64_t *finish_ply;
+} az_selfplay_export_info;
+/* Moves the whole finished store into `dst` as rows ptr .. ptr + n_rows - 1, the games in az_selfplay_drain's
+ * order (finishing ply, then slot), and empties the store as az_selfplay_drain does; *new_ptr = ptr + n_rows
+ * (new_ptr may be NULL).  n_games and n_rows must be what az_selfplay_finished just reported, ptr >= 0,
+ * 0 <= td_steps.  Only the per-game figures (slot, length, winner, finishing ply, first row) cross to the host,
+ * which sorts them and hands the kernel the games' source and destination rows; the rows themselves never leave
+ * the device.  The call waits for the device before it reads those figures, then ONLY enqueues on `stream`: the
+ * kernel, and behind it the reset of the store's counters - so an az_selfplay_step issued after it on the same
+ * stream is correct without a wait in between, and `dst` is complete once `stream` reaches that point.
+ * `info` is optional.  AZ_ERR_ARG: the driver does not record, sizes differ from what az_selfplay_finished
+ * reported, capacity <= 0, a null or misaligned tensor. */
+int az_selfplay_export(az_selfplay *sp, const az_replay_tensors *dst, int64_t ptr, int td_steps, int64_t n_games,
+                       int64_t n_rows, const az_selfplay_export_info *info, int64_t *new_ptr, void *stream);
+/* The same kernel on packed games a caller keeps itself, every array in DEVICE memory: of `games_dev` the
+ * fields length, winner, bb_p1, bb_p2, turn, prob, wdl and mask are read (laid out as az_selfplay_drain fills
+ * them); game g occupies the source rows src_row0[g] .. src_row0[g] + length[g] and becomes the call's rows
+ * dst_row0[g] .. dst_row0[g] + length[g].  dst_row0 starts at 0 and is packed in game order (dst_row0[g + 1] =
+ * dst_row0[g] + length[g] + 1): the kernel takes the call's row count from its last entry.  Only enqueues. */
+int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int64_t *src_row0, const int64_t *dst_row0,
+                        int64_t n_games, const az_replay_tensors *dst, int64_t ptr, int td_steps, void *stream);
 /* k_sp_pick on caller-supplied counts, for tests: counts int32 [n][A] and ply int32 [n] in DEVICE memory
  * -> actions int32 [n]; draws are keyed by (seed, call, row).  Only the temperature fields of `c` are read. */
 int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c,

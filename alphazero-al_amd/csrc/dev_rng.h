@@ -2,7 +2,8 @@
 // (kernels.hip: symmetry ids, Dirichlet noise, random playouts) and the self-play driver's move
 // sampler (selfplay_kernels.hip).  A stream is named by (seed, call, a, b): the engine's seed, a
 // counter that moves per use, an index (tree, leaf, game) and a small constant per purpose - streams
-// in use: b = 3 playouts, 7 symmetry ids, 16.. and 128.. root noise, SP_STREAM the driver's moves.
+// in use: b = 3 playouts, 7 symmetry ids, 16.. and 128.. root noise, SP_STREAM the driver's moves,
+// REPLAY_STREAM the replay sampler's ring indices (replay_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@ struct DevRng {
     }
 };
 
-constexpr uint64_t SP_STREAM = 0x5350;   // the self-play driver's move draws
+constexpr uint64_t SP_STREAM = 0x5350;       // the self-play driver's move draws
+constexpr uint64_t REPLAY_STREAM = 0x5242;   // ring indices of a training sample (k_replay_indices)
 
 }  // namespace az

@@ -1876,6 +1876,47 @@ int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int6
     });
 }
 
+int az_game_num_augment(int game) { return known_game(game) ? az::replay_num_augment(game) : -1; }
+
+int az_replay_dev_batch(int game, const az_replay_tensors *src, const int64_t *idx, const int64_t *order, int64_t first,
+                        int64_t B, const az_replay_batch *out, void *stream)
+{
+    return guarded([&] {
+        const std::string w("az_replay_dev_batch");
+        require(game == AZ_GAME_CONNECT4 || game == AZ_GAME_OTHELLO, w + ": unknown game");
+        require(src != nullptr && out != nullptr && idx != nullptr, w + ": null argument");
+        require(B > 0 && B <= (int64_t(1) << 30), w + ": B must be positive (and at most 2^30)");
+        require(first >= 0, w + ": first must not be negative");
+        require(src->capacity > 0, w + ": capacity must be positive");
+        const void *t[16] = {src->state, src->prob, src->winner, src->steps_to_end, src->aux_target, src->root_wdl,
+                             src->valid_mask, src->future_root_wdl, out->state, out->prob, out->winner, out->steps_to_end,
+                             out->aux_target, out->root_wdl, out->valid_mask, out->future_root_wdl};
+        for (const void *q : t) {
+            require(q != nullptr, w + ": a null tensor");
+            require(reinterpret_cast<uintptr_t>(q) % 16 == 0, w + ": a tensor is not 16-byte aligned");
+        }
+        az::ReplayBatch a{};
+        a.state = src->state; a.prob = src->prob; a.winner = src->winner; a.steps_to_end = src->steps_to_end;
+        a.aux_target = src->aux_target; a.root_wdl = src->root_wdl; a.future_root_wdl = src->future_root_wdl;
+        a.valid_mask = src->valid_mask; a.capacity = src->capacity;
+        a.idx = idx; a.order = order; a.first = first; a.B = B;
+        a.o_state = out->state; a.o_prob = out->prob; a.o_winner = out->winner; a.o_steps_to_end = out->steps_to_end;
+        a.o_aux_target = out->aux_target; a.o_root_wdl = out->root_wdl; a.o_future_root_wdl = out->future_root_wdl;
+        a.o_valid_mask = out->valid_mask;
+        az::launch_replay_batch(game, a, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_replay_dev_sample_indices(uint64_t seed, uint64_t call, int64_t n_valid, int64_t *idx, int64_t n, void *stream)
+{
+    return guarded([&] {
+        require(n_valid > 0, "az_replay_dev_sample_indices: n_valid must be positive");
+        require(n >= 0, "az_replay_dev_sample_indices: n must not be negative");
+        require(idx != nullptr || n == 0, "az_replay_dev_sample_indices: null idx");
+        az::launch_replay_indices(seed, call, n_valid, idx, n, static_cast<hipStream_t>(stream));
+    });
+}
+
 int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c, uint64_t seed,
                        uint64_t call, int32_t *actions, int64_t n, void *stream)
 {

@@ -227,4 +227,33 @@ struct SpExport {
 
 void launch_sp_export(int game, SpExport a, hipStream_t s);
 
+// ---- training batches from the replay ring (replay_kernels.hip) -------------------------------------
+// Ring rows -> one augmented batch (k_replay_batch; az_replay_batch in az_mcts.h).  Sample b of the batch is the
+// ring row idx[order ? order[first + b] : first + b]; it becomes the output rows s * B + b, s = 0 .. S - 1, one
+// per board symmetry of the game.  A row number outside [0, capacity) gives zero rows and reads nothing.
+struct ReplayBatch {
+    // the ring, read only
+    const int8_t  *state;                    // [capacity][3][ROWS][COLS]
+    const float   *prob;                     // [capacity][A]
+    const int8_t  *winner;                   // [capacity]
+    const int16_t *steps_to_end, *aux_target;
+    const float   *root_wdl, *future_root_wdl;   // [capacity][3]
+    const uint8_t *valid_mask;               // [capacity][A]
+    int64_t capacity;
+    const int64_t *idx, *order;              // order may be nullptr
+    int64_t first, B;
+    // the batch, [S * B] rows each
+    float   *o_state;                        // [S*B][3][ROWS][COLS]
+    float   *o_prob;                         // [S*B][A]
+    int8_t  *o_winner;
+    int16_t *o_steps_to_end, *o_aux_target;
+    float   *o_root_wdl, *o_future_root_wdl;
+    uint8_t *o_valid_mask;                   // [S*B][A]
+};
+
+int  replay_num_augment(int game);           // S: 2 (Connect4), 4 (Othello)
+void launch_replay_batch(int game, ReplayBatch a, hipStream_t s);
+// n indices uniform in [0, n_valid), element e from the generator stream (seed, call, e, REPLAY_STREAM)
+void launch_replay_indices(uint64_t seed, uint64_t call, int64_t n_valid, int64_t *idx, int64_t n, hipStream_t s);
+
 }  // namespace az

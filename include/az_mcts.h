@@ -400,6 +400,54 @@ int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int6
 int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c,
                        uint64_t seed, uint64_t call, int32_t *actions, int64_t n, void *stream);
 
+/* ---- augmented training batches out of the replay tensors, on the device (k_replay_batch) ----------------
+ * The reference's learner draws a sample on the host (src/ReplayBuffer.py:130-145: np.random.randint, `get`, a
+ * TensorDataset behind a shuffling DataLoader that collates sample by sample) and passes every batch through the
+ * game's `augment` (src/environments/Connect4/utils.py:50-67, src/environments/Othello/utils.py:65-91).  Here a
+ * batch is one launch: B ring rows named by index become S * B rows, S = az_game_num_augment(game), laid out
+ * symmetry-major - output row s * B + b is sample b under symmetry s, which is what `augment(get(idx))` returns.
+ *   Connect4, S = 2   identity; the column mirror c -> 6 - c (action a -> 6 - a)
+ *   Othello,  S = 4   identity; (r, c) -> (7 - r, 7 - c); (r, c) -> (c, r); (r, c) -> (7 - c, 7 - r) - the
+ *                     reference's ids 0, 2, 6, 7; the pass (action 64) stays in place
+ * state: the int8 planes as float32, planes 0 and 1 permuted, plane 2 (the turn sign) as it is.  prob and
+ * valid_mask: the board actions permuted the same way, floats bit for bit, mask bytes 0 / 1.  winner,
+ * steps_to_end, aux_target, root_wdl, future_root_wdl: repeated S times bit for bit.  az_replay_batch names the
+ * batch's tensors in DEVICE memory, all contiguous and 16-byte aligned, S * B rows each. */
+typedef struct az_replay_batch {
+    float   *state;             /* [S*B][3][R][C] */
+    float   *prob;              /* [S*B][A] */
+    int8_t  *winner;            /* [S*B] */
+    int16_t *steps_to_end;      /* [S*B] */
+    int16_t *aux_target;        /* [S*B] */
+    float   *root_wdl;          /* [S*B][3] */
+    uint8_t *valid_mask;        /* [S*B][A], one byte per entry */
+    float   *future_root_wdl;   /* [S*B][3] */
+} az_replay_batch;
+#define AZ_REPLAY_BATCH_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(az_replay_batch) == AZ_REPLAY_BATCH_BYTES, "az_replay_batch layout");
+#else
+_Static_assert(sizeof(az_replay_batch) == AZ_REPLAY_BATCH_BYTES, "az_replay_batch layout");
+#endif
+/* Board symmetries a batch is augmented with: 2 (Connect4), 4 (Othello); -1 for an unknown game. */
+int az_game_num_augment(int game);
+/* Sample b (0 <= b < B) of the batch is the ring row idx[order ? order[first + b] : first + b]: `idx` is a sample
+ * (int64, DEVICE memory) and `order`, optional, a permutation of its positions (int64, DEVICE memory) - an epoch's
+ * shuffle needs no gather pass of its own, a batch is a window [first, first + B) of it.  The caller keeps first + B
+ * within the arrays and the entries of `order` within `idx`.  A ring row outside [0, capacity) is never read: it
+ * gives all-zero output rows in every tensor (the kernel cannot report to the host without a wait).  Replaces
+ * ReplayBuffer.py:144-145 (dataset, loader, per-sample collation) and the `augment` call of the training step.
+ * Only enqueues on `stream`.  AZ_ERR_ARG: unknown game, B <= 0 (or beyond 2^30), first < 0, capacity <= 0, a null
+ * or misaligned tensor (both structs: 16 bytes), a null `src`, `idx` or `out`. */
+int az_replay_dev_batch(int game, const az_replay_tensors *src, const int64_t *idx, const int64_t *order, int64_t first,
+                        int64_t B, const az_replay_batch *out, void *stream);
+/* n ring indices uniform in [0, n_valid) into idx (int64 [n], DEVICE memory), element e from the device
+ * generator's stream (seed, call, e): the same (seed, call) gives the same indices whatever n is, another `call`
+ * gives others.  Each is the high half of a 64-bit draw times n_valid, so the bias is below n_valid / 2^64.
+ * Replaces np.random.randint(0, len(buffer), sample_size) of ReplayBuffer.py:142.  Only enqueues on `stream`.
+ * AZ_ERR_ARG: n_valid <= 0, n < 0, a null idx with n > 0. */
+int az_replay_dev_sample_indices(uint64_t seed, uint64_t call, int64_t n_valid, int64_t *idx, int64_t n, void *stream);
+
 /* ---- device transposition table of evaluator outputs (both games) ------------------------
  * Replaces, for the device loop, the LRU table of the reference's wrapper (src/Cache.py:5-58 used
  * by src/MCTS_cpp.py:146-189 and 298-339): key = the symmetrised leaf position + side to move,

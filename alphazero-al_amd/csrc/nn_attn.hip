@@ -9,8 +9,9 @@
 // 196-wide GEMM + split/normalise + SDPA + gate + out-projection (six kernels, 1.8 ms per 32768-leaf iteration in
 // the first profile).
 //
-// Three workgroups of four wavefronts per CU (three wavefronts per SIMD): 168 registers, the per-sample constants and
-// the gates in LDS (46 KB per workgroup).
+// Three workgroups of four wavefronts per CU (three wavefronts per SIMD): 158 registers, the per-sample constants and
+// the gates in LDS (37 KB per workgroup).  k_attn_block<true> is the earlier gate arrangement (attn::attn_sample's
+// GATE4; 46 KB), launched when az_nn_debug bit 8 is set: same bytes, for A/B runs and as the tests' oracle.
 #include "az_nn.h"
 #include "nn_attn_core.h"
 
@@ -18,6 +19,7 @@ namespace {
 
 using namespace attn;
 
+template <bool GATE4>
 __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg,
                                                        const uint16_t *qn_w, const uint16_t *kn_w, const uint16_t *o_w,
                                                        uint16_t *y, int64_t B, float eps, const int64_t *batch_dev)
@@ -29,10 +31,10 @@ __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const 
 
     __shared__ V8 s_w32[W32_N];
     __shared__ V4 s_w16[W16_N];
-    __shared__ f32x4 s_gate[4 * GATE_N];                    // [wave][token tile][lane]
+    __shared__ f32x4 s_gate[GATE4 ? 4 * GATE_N : GATE_N];   // [wave]: GATE_N floats (GATE4: f32x4)
     __shared__ float s_pw[C];
     __shared__ float s_qk[2 * HD];
-    stage_weights(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
+    stage_weights<GATE4>(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
     __syncthreads();
     const bool bounded = scores_bounded(s_qk, l4);
 
@@ -40,8 +42,8 @@ __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const 
     for (int64_t b = static_cast<int64_t>(blockIdx.x) * 4 + wave; b < B; b += stride) {
         const uint16_t *xs = x + b * (CELLS * C);
         f32x4 out[4][TT];
-        attn_sample(xs, s_w32, s_w16, s_pw, s_qk, s_gate + wave * GATE_N, bounded, eps, lane, l15, l4, out);
-
+        attn_sample<GATE4>(xs, s_w32, s_w16, s_pw, s_qk, s_gate + wave * (GATE4 ? GATE_N : GATE_N / 4), bounded, eps, lane, l15, l4,
+                           out);
 
         // ---- y = out + x : lane holds 4 consecutive output channels of token qt*16 + lane&15
         uint16_t *ys = y + b * (CELLS * C);
@@ -75,7 +77,8 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
     const int64_t wgs = (batch + 3) / 4;
     const unsigned cap = 256u * 3u * 2u;       // two rounds of resident workgroups
     const unsigned grid = static_cast<unsigned>(wgs < cap ? wgs : cap);
-    hipLaunchKernelGGL(k_attn_block, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+    const auto kern = (az_nn_debug_flags() & AZ_NN_DEBUG_LEGACY_TAIL) ? k_attn_block<true> : k_attn_block<false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(prenorm_w),
                        static_cast<const uint16_t *>(qkvg_w), static_cast<const uint16_t *>(q_norm_w),
                        static_cast<const uint16_t *>(k_norm_w), static_cast<const uint16_t *>(o_w),

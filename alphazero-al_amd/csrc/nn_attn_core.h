@@ -20,6 +20,12 @@
 // as A operand (H): the element sets coincide.  The weights (26 KB + 8 KB) sit in LDS in operand-fragment order; what
 // a wavefront would otherwise hold across a whole sample - the sigmoid gates of every (token, head), the pre-norm
 // weight, the q / k norm weights - lives in LDS too (36 registers: three wavefronts then share a SIMD).
+//
+// The gate tile has 4 distinct rows (one per head) on a 16-row MFMA.  Staged as row 4 g + r = head g, lane group g
+// ends up with head g of its token in every accumulator register: it computes ONE sigmoid and stores one float, and
+// the head loop reads gate (token tile, head h, token l15) from the slot lane group h wrote.  GATE4 = true is the
+// earlier arrangement (row 4 g + r = head r: every lane computes all four sigmoids and reads back its own), kept as
+// a second instantiation for A/B runs; the dot products, and so the bits, are the same.
 #pragma once
 
 #include "nn_common.h"
@@ -31,13 +37,14 @@ namespace attn {
 constexpr int CELLS = 42, C = 64, HEADS = 4, HD = 16, TT = 3;     // 3 token tiles of 16
 constexpr int W32_N = (3 * HEADS * 2 + 2) * 64;                    // V8: wq, wk, wv [h][s], wg [s]
 constexpr int W16_N = 4 * HEADS * 64;                              // V4: wo [ot][h]
-constexpr int GATE_N = TT * 64;                                    // f32x4 per wavefront: [token tile][lane], heads 0..3
+constexpr int GATE_N = TT * 64;                                    // per wavefront: float [token tile][head][token] (GATE4: f32x4 [token tile][lane])
 constexpr float QSCALE = 0.25f * 1.44269504f;     // 1/sqrt(16) of the scores and log2(e) of their softmax ride on q
 
 // The weights, staged once per workgroup into LDS in exactly the order the lanes read them (fragment f, lane l ->
 // 16 or 8 contiguous bytes at f*64+l), so every operand fetch is one conflict-free ds_read.  The caller's
 // __syncthreads() follows.  qkvg: (196, 64) row-major [out][in]: rows 0-63 Q, 64-127 K, 128-191 V, 192-195 gate.
 // s_pw [64]: pre-norm weight; s_qk [32]: q norm weight x QSCALE, k norm weight.
+template <bool GATE4 = false>
 __device__ __forceinline__ void stage_weights(const uint16_t *qkvg, const uint16_t *o_w, const uint16_t *pre_w,
                                               const uint16_t *qn_w, const uint16_t *kn_w, V8 *s_w32, V4 *s_w16, float *s_pw,
                                               float *s_qk)
@@ -49,9 +56,9 @@ __device__ __forceinline__ void stage_weights(const uint16_t *qkvg, const uint16
             const int part = f / (HEADS * 2), h = (f >> 1) % HEADS, sk = f & 1;
             v = *reinterpret_cast<const V8 *>(qkvg + (part * C + h * HD + ll15) * C + 32 * sk + 8 * ll4);
         } else {
-            // the 4 gate rows, repeated four times over the tile's 16 rows: accumulator register r of
-            // EVERY lane group is then head r of the lane's token - no lane has to ask another for it
-            v = *reinterpret_cast<const V8 *>(qkvg + (3 * C + (ll15 & 3)) * C + 32 * (f & 1) + 8 * ll4);
+            // the 4 gate rows over the tile's 16 rows: row 4 g + r = head g, so every accumulator register of lane
+            // group g is head g of the lane's token (GATE4: head r, the same four in every lane group)
+            v = *reinterpret_cast<const V8 *>(qkvg + (3 * C + (GATE4 ? ll15 & 3 : ll15 >> 2)) * C + 32 * (f & 1) + 8 * ll4);
         }
         s_w32[i] = v;
     }
@@ -80,7 +87,9 @@ __device__ __forceinline__ bool scores_bounded(const float *s_qk, int l4)
 }
 
 // One sample: xs = its 42 x 64 residual-stream rows (bf16), out = out^T in the MFMA C layout (lane holds channels
-// 16 ot + 4 l4 + r of token qt*16 + l15).  s_gate: this wavefront's GATE_N f32x4 of LDS, written and read here.
+// 16 ot + 4 l4 + r of token qt*16 + l15).  s_gate: this wavefront's gate store (GATE_N floats; GATE4: GATE_N f32x4),
+// written and read here.
+template <bool GATE4 = false>
 __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32, const V4 *s_w16, const float *s_pw,
                                             const float *s_qk, f32x4 *s_gate, bool bounded, float eps, int lane, int l15,
                                             int l4, f32x4 (&out)[4][TT])
@@ -124,16 +133,22 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             hf[tt][s] = as_bf16x8(o);
         }
     }
-    // ---- sigmoid gates of every token (gate tile rows 4q + h = head h: register h of every lane)
+    // ---- sigmoid gates of every token: lane group l4 holds head l4 (GATE4: register h of every lane is head h)
+    float *s_gate1 = reinterpret_cast<float *>(s_gate);
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
         f32x4 g = MFMA32(frag32(24), hf[tt][0], zero);
         g = MFMA32(frag32(25), hf[tt][1], g);
-        f32x4 gs;
+        if constexpr (GATE4) {
+            f32x4 gs;
 #pragma unroll
-        for (int h = 0; h < HEADS; ++h) gs[h] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[h]));
-        s_gate[tt * 64 + lane] = gs;
+            for (int h = 0; h < HEADS; ++h) gs[h] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[h]));
+            s_gate[tt * 64 + lane] = gs;
+        } else {
+            s_gate1[tt * 64 + lane] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[0]));
+        }
     }
+    if constexpr (!GATE4) wave_lds_sync();          // a gate is read by the lanes of other lane groups
 
 #pragma unroll
     for (int ot = 0; ot < 4; ++ot)
@@ -216,7 +231,7 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
                 den = col_sum(den2.x + den2.y);
             }
             // normalise after the product: O^T = (V^T . E^T) / den, one scale per output element
-            const float gq = reinterpret_cast<const float *>(&s_gate[qt * 64 + lane])[h];
+            const float gq = GATE4 ? reinterpret_cast<const float *>(&s_gate[qt * 64 + lane])[h] : s_gate1[qt * 64 + h * 16 + l15];
             const float scale = __builtin_amdgcn_rcpf(den) * gq;
             f32x4 o = zero;                                  // O^T rows = d, column = query
 #pragma unroll

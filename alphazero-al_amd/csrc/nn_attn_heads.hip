@@ -7,16 +7,27 @@
 // sums over a lane's 16 values plus col_sum, the token mean is a sum over the 16 lanes of a row (DPP).  The
 // rounded output y = bf16(x + o_proj(...)) never leaves the registers; only the normalised tokens go to a
 // per-wave LDS image, for the policy pooling over the 6 rows of each column (tokens 7 apart live in
-// different lanes).  From there on the code is the one k_heads runs (nn_heads_core.h): a wavefront fills the
-// 16-column B operand with two samples (its own two consecutive samples of the grid-stride list) and runs the 64x64
-// linears and the epilogues once per pair.
+// different lanes).  From there on the code is the one k_heads runs (nn_heads_core.h).  The POLICY runs per pair: a
+// wavefront fills the 16-column B operand with the pooled columns of two samples (its own two consecutive samples of
+// the grid-stride list) and runs the 64x64 linear and the masked softmax once per pair.  The VALUE / moves-left head is
+// deferred: per sample only the bf16 token mean is parked in one of 16 slots of the wavefront; after its last sample
+// (and whenever the 16 slots are full: more than 16 samples per wavefront, i.e. batches above 16 x 12 x CUs) the
+// wavefront makes pool_norm(mean) of every slot one column of the B operand - in the MFMA C layout with column = slot a
+// lane holds channels 16 ot + 4 l4 + r, the channel set the token pass had, so the statistics are summed in the same
+// order - and runs value_tail() once on up to 16 live columns.  At a search iteration's ~26 k leaves that is one value
+// tail per wavefront where the per-pair form ran four or five with 2 live columns of 16.  The value head's 18 A
+// fragments are read from the weights (L2) in that one pass; their 18 KB of LDS hold the mean slots instead.
+//
+// LEGACY = true is the earlier form (value head once per pair, in columns 7 and 15 next to the policy columns; gates
+// as attn::attn_sample's GATE4), launched when az_nn_debug bit 8 is set: same bytes, for A/B runs and as the tests'
+// oracle.
 //
 // Rounding points are those of k_attn_block followed by k_heads: results differ from the two launches only
 // through f32 summation order (token mean, RMS statistics) - the two token passes are the only code not shared.
 //
 // Shape: one 12-wavefront workgroup per CU (three per SIMD, the attention kernel's occupancy): one copy of
-// the attention weights (35 KB) and of the heads' weights (28 KB), and 7.9 KB per wavefront (normalised
-// tokens, which double as the attention's gate store, the B operand, scores and means): 158 KB of LDS.
+// the attention weights (35 KB) and of the policy's (10 KB), and 9.4 KB per wavefront (normalised tokens, which double
+// as the attention's gate store, the B operand, scores and the 16 mean slots): 158 KB of LDS.
 #include "az_nn.h"
 #include "nn_attn_core.h"
 #include "nn_heads_core.h"
@@ -30,25 +41,36 @@ constexpr int WPB = 12;         // wavefronts per workgroup: one workgroup per C
 constexpr int VS = 64;          // bf16 row stride of the B-operand buffer
 
 // dynamic LDS layout (bytes)
-constexpr int L_W32 = 0;                                 // V8 [attn::W32_N]
-constexpr int L_W16 = L_W32 + attn::W32_N * 16;          // V4 [attn::W16_N]
-constexpr int L_A = L_W16 + attn::W16_N * 8;             // V8 [A_N]: heads' A fragments
-constexpr int L_C = L_A + A_N * 16;                      // float [K_N][64]
-constexpr int L_PW = L_C + K_N * C * 4;                  // float [64]: attention pre-norm weight
-constexpr int L_QK = L_PW + C * 4;                       // float [32]: q norm weight x QSCALE, k norm weight
-constexpr int L_PN = L_QK + 2 * attn::HD * 4;            // per wave: u16 [42*64] normalised tokens | f32x4 [3*64] gates
-constexpr int L_VEC = L_PN + WPB * CELLS * C * 2;        // per wave: u16 [16*VS] B operand, row n = column n of V^T
-constexpr int L_SCORE = L_VEC + WPB * 16 * VS * 2;       // per wave: float [48] row-gate scores, then weights
-constexpr int L_MEAN = L_SCORE + WPB * 48 * 4;           // per wave: float [2][64] token means of the pair
-constexpr int L_TOTAL = L_MEAN + WPB * 2 * C * 4;
+template <bool LEGACY>
+struct Lds {
+    static constexpr int A_FRAGS = LEGACY ? 26 : 8;                  // heads' A fragments kept in LDS: all, or the policy's
+    static constexpr int MEAN_B = LEGACY ? 2 * C * 4 : 16 * C * 2;   // per wave: float [2][64] means of the pair, or bf16 [16][64] slots
+    static constexpr int L_W32 = 0;                                 // V8 [attn::W32_N]
+    static constexpr int L_W16 = L_W32 + attn::W32_N * 16;          // V4 [attn::W16_N]
+    static constexpr int L_A = L_W16 + attn::W16_N * 8;             // V8 [A_FRAGS * 64]
+    static constexpr int L_C = L_A + A_FRAGS * 64 * 16;             // float [K_N][64]
+    static constexpr int L_PW = L_C + K_N * C * 4;                  // float [64]: attention pre-norm weight
+    static constexpr int L_QK = L_PW + C * 4;                       // float [32]: q norm weight x QSCALE, k norm weight
+    static constexpr int L_PN = L_QK + 2 * attn::HD * 4;            // per wave: u16 [42*64] normalised tokens | the attention's gates
+    static constexpr int L_VEC = L_PN + WPB * CELLS * C * 2;        // per wave: u16 [16*VS] B operand, row n = column n of V^T
+    static constexpr int L_SCORE = L_VEC + WPB * 16 * VS * 2;       // per wave: float [48] row-gate scores, then weights
+    static constexpr int L_MEAN = L_SCORE + WPB * 48 * 4;           // per wave: MEAN_B
+    static constexpr int L_TOTAL = L_MEAN + WPB * MEAN_B;
+    static_assert(L_TOTAL <= 160 * 1024, "LDS of one CU");
+};
 static_assert(CELLS * C * 2 >= attn::GATE_N * 16, "the gate store fits in the token image");
-static_assert(L_TOTAL <= 160 * 1024, "LDS of one CU");
+static_assert(Lds<true>::L_TOTAL == Lds<false>::L_TOTAL, "one dynamic-LDS size for both forms");
+constexpr int L_TOTAL = Lds<false>::L_TOTAL;
 
+template <bool LEGACY>
 __global__ void __launch_bounds__(64 * WPB, 1)
 k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, const uint16_t *qn_w, const uint16_t *kn_w,
              const uint16_t *o_w, az_nn_heads_weights w, const uint8_t *mask, float *probs, float *wdl, float *moves_left,
              int64_t B, float eps, const int32_t *scatter, const int64_t *batch_dev)
 {
+    using L = Lds<LEGACY>;
+    constexpr int L_W32 = L::L_W32, L_W16 = L::L_W16, L_A = L::L_A, L_C = L::L_C, L_PW = L::L_PW, L_QK = L::L_QK, L_PN = L::L_PN,
+                  L_VEC = L::L_VEC, L_SCORE = L::L_SCORE, L_MEAN = L::L_MEAN;
     const int64_t rows_total = B;                 // rows of mask / outputs: a compact list may name any of them
     if (batch_dev != nullptr && *batch_dev < B) B = *batch_dev;
     extern __shared__ __align__(16) uint8_t smem[];
@@ -72,11 +94,12 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
     f32x4 *s_gate = reinterpret_cast<f32x4 *>(smem + L_PN + wave * CELLS * C * 2);      // [token tile][lane], attention only
     uint16_t *s_vec = reinterpret_cast<uint16_t *>(smem + L_VEC + wave * 16 * VS * 2);
     float *s_score = reinterpret_cast<float *>(smem + L_SCORE + wave * 48 * 4);
-    float *s_mean = reinterpret_cast<float *>(smem + L_MEAN + wave * 2 * C * 4);
+    float *s_mean = reinterpret_cast<float *>(smem + L_MEAN + wave * L::MEAN_B);             // LEGACY
+    uint16_t *s_slot = reinterpret_cast<uint16_t *>(smem + L_MEAN + wave * L::MEAN_B);       // bf16 [16][64]
 
     // ---- weights, staged once per workgroup in fragment order
-    attn::stage_weights(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
-    stage_weights(w, s_a, s_c);
+    attn::stage_weights<LEGACY>(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
+    stage_weights<L::A_FRAGS>(w, s_a, s_c);
     if (threadIdx.x < C) {
         const int i = threadIdx.x;
         const float nw = bf1(static_cast<const uint16_t *>(w.p_norm) + i);
@@ -88,94 +111,159 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
     auto cvec4 = [&](int which, int ot) { return *reinterpret_cast<const f32x4 *>(&s_c[which][16 * ot + 4 * l4]); };
     const bool bounded = attn::scores_bounded(s_qk, l4);
 
-    // a wavefront's samples: b0, b0 + S, b0 + 2S, ... (S = wavefronts in the grid), taken two at a time
+    // a wavefront's samples: b0, b0 + S, b0 + 2S, ... (S = wavefronts in the grid), taken two at a time.  nslot of them
+    // wait for their value tail, in slots 0 .. nslot - 1: samples fbase, fbase + S, ...
     const int64_t S = static_cast<int64_t>(gridDim.x) * WPB;
-    for (int64_t b0 = static_cast<int64_t>(blockIdx.x) * WPB + wave; b0 < B; b0 += 2 * S) {
-        const int64_t b1 = b0 + S;
+    int nslot = 0;
+    int64_t fbase = static_cast<int64_t>(blockIdx.x) * WPB + wave;
+    for (int64_t b0 = fbase;; b0 += 2 * S) {
+        const bool more = b0 < B;
+        if (more) {
+            const int64_t b1 = b0 + S;
 #pragma unroll 1
-        for (int hs = 0; hs < 2; ++hs) {
-            const int64_t bs = hs == 0 ? b0 : b1;
-            if (bs >= B) break;
-            refresh_lane();
-            const uint16_t *xs = x + bs * (CELLS * C);
+            for (int hs = 0; hs < 2; ++hs) {
+                const int64_t bs = hs == 0 ? b0 : b1;
+                if (bs >= B) break;
+                refresh_lane();
+                const uint16_t *xs = x + bs * (CELLS * C);
 
-            f32x4 out[4][TT];
-            attn::attn_sample(xs, s_w32, s_w16, s_pw, s_qk, s_gate, bounded, eps, lane, l15, l4, out);
-            wave_lds_sync();                     // the gates are read: the token image may overwrite them
+                f32x4 out[4][TT];
+                attn::attn_sample<LEGACY>(xs, s_w32, s_w16, s_pw, s_qk, s_gate, bounded, eps, lane, l15, l4, out);
+                wave_lds_sync();                     // the gates are read: the token image may overwrite them
 
-            // ======== token pass on y = bf16(x + out): lane = token qt*16 + l15, channels 16 ot + 4 l4 + r ========
-            f32x2 msum[4][2];
+                // ======== token pass on y = bf16(x + out): lane = token qt*16 + l15, channels 16 ot + 4 l4 + r ========
+                f32x2 msum[4][2];
 #pragma unroll
-            for (int ot = 0; ot < 4; ++ot) msum[ot][0] = msum[ot][1] = f32x2{0.0f, 0.0f};
+                for (int ot = 0; ot < 4; ++ot) msum[ot][0] = msum[ot][1] = f32x2{0.0f, 0.0f};
 #pragma unroll
-            for (int qt = 0; qt < TT; ++qt) {
-                const int tok = qt * 16 + l15;
-                const bool live = tok < CELLS;
-                f32x2 f[4][2], ss2 = {0.0f, 0.0f}, sc2 = {0.0f, 0.0f};
-#pragma unroll
-                for (int ot = 0; ot < 4; ++ot) {
-                    V4 xr; xr.w[0] = xr.w[1] = 0;
-                    if (live) xr = *reinterpret_cast<const V4 *>(xs + tok * C + ot * 16 + 4 * l4);
-                    const f32x4 ngw = cvec4(K_PNGW, ot);
-                    f[ot][0] = unpack2(pack2(out[ot][qt][0] + bf_lo(xr.w[0]), out[ot][qt][1] + bf_hi(xr.w[0])));
-                    f[ot][1] = unpack2(pack2(out[ot][qt][2] + bf_lo(xr.w[1]), out[ot][qt][3] + bf_hi(xr.w[1])));
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        ss2 = __builtin_elementwise_fma(f[ot][j], f[ot][j], ss2);
-                        sc2 = __builtin_elementwise_fma(f[ot][j], f32x2{ngw[2 * j], ngw[2 * j + 1]}, sc2);
-                        if (live) msum[ot][j] += f[ot][j];
-                    }
-                }
-                const float ss = col_sum(ss2.x + ss2.y), sc = col_sum(sc2.x + sc2.y);
-                const float r = rsqrtf(ss * (1.0f / C) + eps);
-                if (live) {
+                for (int qt = 0; qt < TT; ++qt) {
+                    const int tok = qt * 16 + l15;
+                    const bool live = tok < CELLS;
+                    f32x2 f[4][2], ss2 = {0.0f, 0.0f}, sc2 = {0.0f, 0.0f};
 #pragma unroll
                     for (int ot = 0; ot < 4; ++ot) {
-                        const f32x4 nw = cvec4(K_PNORM, ot);
-                        const f32x2 p0 = f[ot][0] * f32x2{r, r} * f32x2{nw[0], nw[1]};
-                        const f32x2 p1 = f[ot][1] * f32x2{r, r} * f32x2{nw[2], nw[3]};
-                        V4 o;
-                        o.w[0] = pack2(p0.x, p0.y);
-                        o.w[1] = pack2(p1.x, p1.y);
-                        *reinterpret_cast<V4 *>(&s_pn[tok * C + ot * 16 + 4 * l4]) = o;
+                        V4 xr; xr.w[0] = xr.w[1] = 0;
+                        if (live) xr = *reinterpret_cast<const V4 *>(xs + tok * C + ot * 16 + 4 * l4);
+                        const f32x4 ngw = cvec4(K_PNGW, ot);
+                        f[ot][0] = unpack2(pack2(out[ot][qt][0] + bf_lo(xr.w[0]), out[ot][qt][1] + bf_hi(xr.w[0])));
+                        f[ot][1] = unpack2(pack2(out[ot][qt][2] + bf_lo(xr.w[1]), out[ot][qt][3] + bf_hi(xr.w[1])));
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            ss2 = __builtin_elementwise_fma(f[ot][j], f[ot][j], ss2);
+                            sc2 = __builtin_elementwise_fma(f[ot][j], f32x2{ngw[2 * j], ngw[2 * j + 1]}, sc2);
+                            if (live) msum[ot][j] += f[ot][j];
+                        }
                     }
-                    if (l4 == 0) s_score[tok] = sc * r + w.p_gate_b;
+                    const float ss = col_sum(ss2.x + ss2.y), sc = col_sum(sc2.x + sc2.y);
+                    const float r = rsqrtf(ss * (1.0f / C) + eps);
+                    if (live) {
+#pragma unroll
+                        for (int ot = 0; ot < 4; ++ot) {
+                            const f32x4 nw = cvec4(K_PNORM, ot);
+                            const f32x2 p0 = f[ot][0] * f32x2{r, r} * f32x2{nw[0], nw[1]};
+                            const f32x2 p1 = f[ot][1] * f32x2{r, r} * f32x2{nw[2], nw[3]};
+                            V4 o;
+                            o.w[0] = pack2(p0.x, p0.y);
+                            o.w[1] = pack2(p1.x, p1.y);
+                            *reinterpret_cast<V4 *>(&s_pn[tok * C + ot * 16 + 4 * l4]) = o;
+                        }
+                        if (l4 == 0) s_score[tok] = sc * r + w.p_gate_b;
+                    }
                 }
+                // ---- token mean (bf16, like the reference's mean of a bf16 tensor): sums over the 16 lanes of a row
+                if constexpr (LEGACY) {
+                    // kept for the residual, and its pool_norm goes to this sample's value column 8 hs + 7
+                    f32x2 g0[4][2], q2 = {0.0f, 0.0f};
+#pragma unroll
+                    for (int ot = 0; ot < 4; ++ot)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const f32x2 m = {sum16(msum[ot][j].x), sum16(msum[ot][j].y)};
+                            g0[ot][j] = rbf2(m * f32x2{1.0f / CELLS, 1.0f / CELLS});
+                            q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
+                        }
+                    const float rn = rsqrtf(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
+                    if (l15 == 0) {
+#pragma unroll
+                        for (int ot = 0; ot < 4; ++ot) {
+                            *reinterpret_cast<f32x4 *>(&s_mean[hs * C + 16 * ot + 4 * l4]) = f32x4{g0[ot][0].x, g0[ot][0].y, g0[ot][1].x, g0[ot][1].y};
+                            const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
+                            const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
+                            const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
+                            V4 o;
+                            o.w[0] = pack2(v0.x, v0.y);
+                            o.w[1] = pack2(v1.x, v1.y);
+                            *reinterpret_cast<V4 *>(&s_vec[(8 * hs + 7) * VS + 16 * ot + 4 * l4]) = o;
+                        }
+                    }
+                } else {
+                    // parked in the sample's slot; everything else about the value head waits for the flush
+#pragma unroll
+                    for (int ot = 0; ot < 4; ++ot) {
+                        V4 o;
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const f32x2 m = f32x2{sum16(msum[ot][j].x), sum16(msum[ot][j].y)} * f32x2{1.0f / CELLS, 1.0f / CELLS};
+                            o.w[j] = pack2(m.x, m.y);
+                        }
+                        if (l15 == 0) *reinterpret_cast<V4 *>(&s_slot[(nslot + hs) * C + 16 * ot + 4 * l4]) = o;
+                    }
+                }
+                wave_lds_sync();
+                pool_columns<VS>(s_score, s_pn, s_vec, hs, lane);
             }
-            // ---- token mean (bf16, like the reference's mean of a bf16 tensor): sums over the 16 lanes of a row;
-            // kept for the residual, and its pool_norm goes to this sample's value column 8 hs + 7
-            {
+
+            refresh_lane();
+            if constexpr (LEGACY) {
+                heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, b0, b1, B, rows_total, scatter, eps,
+                                    lane, l15, l4);
+            } else {
+                policy_tail<VS>(s_a, s_c, s_vec, w, mask, probs, b0, b1, B, rows_total, scatter, lane, l15, l4);
+                nslot += b1 < B ? 2 : 1;
+            }
+        }
+        if constexpr (!LEGACY) {
+            // ======== value tail of the parked samples: the slots are full, or this was the last pair ========
+            if (nslot == 16 || (!more && nslot > 0)) {
+                refresh_lane();
+                // Columns nslot .. 15 are dead: they read slot bytes nobody wrote and carry that garbage (NaN included)
+                // through the MFMAs on purpose - a column never meets another one (MFMA columns are independent, col_sum
+                // stays inside a column) and every store below is guarded by col_live.  Keep it so: no reduction ACROSS
+                // columns belongs in this block.
+                const bool col_live = l15 < nslot;
+                const int64_t bc = fbase + l15 * S;        // column = slot: the slot's sample (< B where the column is live)
+                const int64_t b = (col_live && scatter != nullptr) ? scatter[bc] : bc;
+                const bool real = col_live && b >= 0 && b < rows_total;
+                // pool_norm of the slot's mean -> row l15 of the B operand (s_vec is free: the policy tail has read it)
                 f32x2 g0[4][2], q2 = {0.0f, 0.0f};
 #pragma unroll
-                for (int ot = 0; ot < 4; ++ot)
+                for (int ot = 0; ot < 4; ++ot) {
+                    const V4 mv = *reinterpret_cast<const V4 *>(&s_slot[l15 * C + 16 * ot + 4 * l4]);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        const f32x2 m = {sum16(msum[ot][j].x), sum16(msum[ot][j].y)};
-                        g0[ot][j] = rbf2(m * f32x2{1.0f / CELLS, 1.0f / CELLS});
+                        g0[ot][j] = unpack2(mv.w[j]);
                         q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
                     }
-                const float rn = rsqrtf(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
-                if (l15 == 0) {
-#pragma unroll
-                    for (int ot = 0; ot < 4; ++ot) {
-                        *reinterpret_cast<f32x4 *>(&s_mean[hs * C + 16 * ot + 4 * l4]) = f32x4{g0[ot][0].x, g0[ot][0].y, g0[ot][1].x, g0[ot][1].y};
-                        const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
-                        const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
-                        const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
-                        V4 o;
-                        o.w[0] = pack2(v0.x, v0.y);
-                        o.w[1] = pack2(v1.x, v1.y);
-                        *reinterpret_cast<V4 *>(&s_vec[(8 * hs + 7) * VS + 16 * ot + 4 * l4]) = o;
-                    }
                 }
+                const float rn = rsqrtf(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
+#pragma unroll
+                for (int ot = 0; ot < 4; ++ot) {
+                    const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
+                    const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
+                    const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
+                    V4 o;
+                    o.w[0] = pack2(v0.x, v0.y);
+                    o.w[1] = pack2(v1.x, v1.y);
+                    *reinterpret_cast<V4 *>(&s_vec[l15 * VS + 16 * ot + 4 * l4]) = o;
+                }
+                wave_lds_sync();
+                auto mean2 = [&](int m, int hh) { return g0[m][hh]; };
+                value_tail<VS>(AFragGlobal{w, l15, l4}, s_c, s_vec, mean2, w, wdl, moves_left, col_live, b, real, eps, l15, l4);
+                fbase += nslot * S;
+                nslot = 0;
             }
-            wave_lds_sync();
-            pool_columns<VS>(s_score, s_pn, s_vec, hs, lane);
         }
-
-        refresh_lane();
-        heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, b0, b1, B, rows_total, scatter, eps,
-                            lane, l15, l4);
+        if (!more) break;
     }
 }
 
@@ -188,12 +276,16 @@ extern "C" int az_nn_attn_heads(const void *x, const void *prenorm_w, const void
 {
     if (batch <= 0 || x == nullptr || w == nullptr || probs == nullptr || wdl == nullptr || moves_left == nullptr) return 1;
     static DeviceSetup setup;
-    const int cus = setup.cus({reinterpret_cast<const void *>(k_attn_heads)}, L_TOTAL);
+    int cus = setup.cus({reinterpret_cast<const void *>(k_attn_heads<false>), reinterpret_cast<const void *>(k_attn_heads<true>)}, L_TOTAL);
     if (cus == 0) return 2;
+    // az_nn_debug: bit 8 the earlier form, bits 16-27 a cap on the grid (tests: many samples per wavefront)
+    const int dbg = az_nn_debug_flags(), cap = (dbg >> 16) & 0xfff;
+    const auto kern = (dbg & AZ_NN_DEBUG_LEGACY_TAIL) ? k_attn_heads<true> : k_attn_heads<false>;
+    if (cap > 0 && cap < cus) cus = cap;
     // one workgroup per CU, each wavefront on every S-th sample (S = wavefronts in the grid)
     const int64_t want = (batch + WPB - 1) / WPB;
     const unsigned grid = static_cast<unsigned>(want < cus ? want : cus);
-    hipLaunchKernelGGL(k_attn_heads, dim3(grid), dim3(64 * WPB), L_TOTAL, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WPB), L_TOTAL, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(prenorm_w),
                        static_cast<const uint16_t *>(qkvg_w), static_cast<const uint16_t *>(q_norm_w),
                        static_cast<const uint16_t *>(k_norm_w), static_cast<const uint16_t *>(o_w), *w, mask, probs, wdl,

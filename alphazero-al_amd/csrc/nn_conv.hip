@@ -32,6 +32,7 @@
 // it: no x is read at all, each wavefront builds the raw tile of its sample from the leaf's position.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "az_nn.h"
 #include "nn_common.h"
@@ -124,7 +125,9 @@ __global__ void __launch_bounds__(256, 2) k_stem_conv_block(StemIn st, const uin
 #include "nn_conv_body.h"
 }
 
-int g_dbg = 0;   // timing experiments only (az_nn_debug): 1 skips the MFMA loop, 2 skips the store
+// az_nn_debug: timing experiments (1 skips the MFMA loop, 2 skips the store, ...: bits 0-7 go to the kernels of this file)
+// and the launch-time choices of nn_attn.hip / nn_attn_heads.hip (az_nn_debug_flags)
+int g_dbg = [] { const char *e = getenv("AZ_VALUE_TAIL_DEFERRED"); return e != nullptr && strcmp(e, "0") == 0 ? AZ_NN_DEBUG_LEGACY_TAIL : 0; }();
 
 template <int CIN, bool NORM, bool RESID, bool EMBED = false>
 int launch(const void *x, const void *w, const void *bias, const void *gamma, const void *beta, void *y, int64_t B,
@@ -150,7 +153,7 @@ int launch(const void *x, const void *w, const void *bias, const void *gamma, co
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, static_cast<const uint16_t *>(x),
                        static_cast<const uint16_t *>(w), static_cast<const uint16_t *>(bias),
                        static_cast<const uint16_t *>(gamma), static_cast<const uint16_t *>(beta),
-                       static_cast<uint16_t *>(y), B, eps, g_dbg | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev, em);
+                       static_cast<uint16_t *>(y), B, eps, (g_dbg & 255) | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev, em);
     return 0;
 }
 
@@ -178,7 +181,7 @@ int launch_stem(const StemIn &st, const void *w, const void *bias, const void *g
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, st, static_cast<const uint16_t *>(w),
                        static_cast<const uint16_t *>(bias), static_cast<const uint16_t *>(gamma),
                        static_cast<const uint16_t *>(beta), static_cast<uint16_t *>(y), B, eps,
-                       g_dbg | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev);
+                       (g_dbg & 255) | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev);
     return 0;
 }
 
@@ -187,6 +190,7 @@ int launch_stem(const StemIn &st, const void *w, const void *bias, const void *g
 extern "C" {
 
 int az_nn_debug(int flags) { g_dbg = flags; return 0; }
+int az_nn_debug_flags(void) { return g_dbg; }
 
 int az_nn_conv_profile(unsigned long long *out, int n)
 {

@@ -108,7 +108,18 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
  * stores, bit 4 records per-wavefront cycle totals of its phases (az_nn_conv_profile: 8 values
  * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store, and for
  * az_nn_stem_conv_block_positions the stem phase - for the first n / 8 wavefronts of the last launch). */
+/* Bit 8 (AZ_NN_DEBUG_LEGACY_TAIL) selects, at launch time, the earlier forms of az_nn_attn_heads (the value head once per
+ * sample pair) and of the attention's gate tile (four sigmoids per lane) in az_nn_attn_block / az_nn_attn_heads: second
+ * instantiations of the same kernels, same output bytes - for A/B runs and as the tests' oracle.  The bit starts set when
+ * AZ_VALUE_TAIL_DEFERRED=0 is in the environment (read once, when the library is loaded); the variable is named after the
+ * largest of the changes it undoes, and it also undoes the gate tile (az_nn_attn_block too) and the split tail of az_nn_heads.
+ * az_nn_debug() REPLACES all flags: a later az_nn_debug(0), as the probes under tools/ make, clears the bit the environment set.
+ * Bits 16-27 (AZ_NN_DEBUG_GRID_CAP(n)): at most n workgroups in az_nn_attn_heads' grid (0 = one per CU), so that tests
+ * reach many samples per wavefront with few samples. */
+#define AZ_NN_DEBUG_LEGACY_TAIL 256
+#define AZ_NN_DEBUG_GRID_CAP(n) (((n) & 0xfff) << 16)
 int az_nn_debug(int flags);
+int az_nn_debug_flags(void);
 int az_nn_conv_profile(unsigned long long *out, int n);
 /* nn.RMSNorm over the last dimension of 64 */
 int az_nn_rmsnorm64(const void *x, const void *w, void *y, int64_t rows, float eps, void *stream);

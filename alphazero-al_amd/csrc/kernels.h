@@ -227,6 +227,30 @@ struct SpExport {
 
 void launch_sp_export(int game, SpExport a, hipStream_t s);
 
+// ---- evaluation matches between two engines (match_kernels.hip) -------------------------------------
+// One ply's tail of a match (k_match_ply; az_match_* in az_mcts.h): the mover engine's root counts -> the move, the
+// stepped position, what both engines' re-rooting and resets read, results, the move record, totals.
+struct MatchPly {
+    const int32_t *counts;   // [n][A] root visit counts of the engine that searched
+    const int32_t *tape;     // [n] or nullptr: this ply's actions, read instead of picked
+    uint64_t *bb0, *bb1;     // [n] positions, stepped in place
+    int32_t  *turn, *aux;
+    int32_t  *length;        // [n] plies played
+    uint8_t  *dead;          // [n] the game is over: action -1 from then on
+    int32_t  *actions;       // [n] out: what both prunes read
+    uint8_t  *done;          // [n] out: 1 iff the game ended on this ply (both resets read it)
+    int32_t  *winner;        // [n] +1 / -1 / 0, written when the game ends
+    int32_t  *moves;         // [max_plies][n] or nullptr: row `ply` is written
+    unsigned long long *totals;   // won by +1, won by -1, drawn, finished
+    float    temperature;
+    uint64_t seed, ply;      // generator key: engine_p1's seed and the match's ply counter
+    int64_t  n;
+};
+void launch_match_ply(int game, MatchPly a, hipStream_t s);
+// the pick alone on caller-supplied counts (az_match_sample): counts [n][A] -> actions [n], same generator stream
+void launch_match_sample(int game, const int32_t *counts, float temperature, uint64_t seed, uint64_t ply, int32_t *actions,
+                         int64_t n, hipStream_t s);
+
 // ---- training batches from the replay ring (replay_kernels.hip) -------------------------------------
 // Ring rows -> one augmented batch (k_replay_batch; az_replay_batch in az_mcts.h).  Sample b of the batch is the
 // ring row idx[order ? order[first + b] : first + b]; it becomes the output rows s * B + b, s = 0 .. S - 1, one

@@ -1,0 +1,114 @@
+// match_kernels.hip - the ply tail of the evaluation-match driver (az_match_* in az_mcts.h), instantiated per game
+// like the tree kernels.
+//
+//   k_match_ply   the whole tail of a ply in ONE launch: the mover engine's root visit counts -> the move
+//                 (pipeline.py:337-351, the pick of sp_pick.h that k_sp_pick uses), the action both engines' re-rooting
+//                 reads, the stepped position (games.h), `done` for both engines' resets, winner, length, the dead
+//                 flag, the move record and the totals.  The self-play tail is three launches because a finished
+//                 slot is refilled: the tree reset needs `done` BEFORE the refill rewrites the slot, and the end state
+//                 has to survive for the recorded game's last row.  A match never refills and keeps no rows, so
+//                 nothing orders the step against anything else of the ply.
+//                 One lane group per game as in kernels.hip (Connect4: 8 lanes, 8 games per wavefront; Othello: a
+//                 wavefront): lane e owns action e of the count row, Othello's pass rides with lane 0.  Every lane of
+//                 a group steps its game's position in registers (the pick leaves the move in all of them), lane 0 of
+//                 the group stores.  No LDS, no barrier.
+//   k_match_sample  the pick alone, for tests (az_match_sample).
+//
+// Totals: one ballot per figure and wavefront, one atomic per figure per wavefront that has something to add.
+#include "kernels.h"
+
+#include "dev_rng.h"
+#include "games.h"
+#include "sp_pick.h"
+
+namespace az {
+namespace {
+
+constexpr int WAVE = 64;
+
+template <class G>
+__global__ void __launch_bounds__(WAVE) k_match_ply(MatchPly a)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    const int lane = threadIdx.x, sub = lane % L;
+    const int64_t game = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
+    const bool live = game < a.n;                      // the last wavefront may hold fewer games than groups
+    const int64_t g = live ? game : 0;                 // idle groups read game 0 and store nothing
+    const bool dead = a.dead[g] != 0;
+
+    PickLane pl;
+    int action = pick_move<G, MATCH_STREAM>(a.counts + g * A, live, lane, a.temperature, a.tape, a.seed, a.ply, g, pl);
+    if (dead || action < 0 || action >= A) action = -1;    // a tape's -1: the game does not move
+
+    GameState s;
+    s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g];
+    int res = -1;
+    if (action >= 0) {
+        G::step(s, action);
+        res = G::result(s);
+    }
+    const bool fin = live && res >= 0;
+    const int win = res == 1 ? 1 : (res == 2 ? -1 : 0);
+    if (live && sub == 0) {
+        a.actions[g] = action;
+        a.done[g] = fin ? 1 : 0;
+        if (a.moves != nullptr) a.moves[a.ply * static_cast<uint64_t>(a.n) + g] = action;
+        if (action >= 0) {
+            a.bb0[g] = s.bb0; a.bb1[g] = s.bb1; a.turn[g] = s.turn; a.aux[g] = s.aux;
+            a.length[g] += 1;
+        }
+        if (fin) { a.winner[g] = win; a.dead[g] = 1; }
+    }
+    // one vote per game: lane 0 of its group
+    const bool vote = fin && sub == 0;
+    const unsigned long long w1 = __ballot(vote && win == 1), w2 = __ballot(vote && win == -1), w0 = __ballot(vote && win == 0);
+    if (lane == 0) {
+        if (w1) atomicAdd(&a.totals[0], static_cast<unsigned long long>(__popcll(w1)));
+        if (w2) atomicAdd(&a.totals[1], static_cast<unsigned long long>(__popcll(w2)));
+        if (w0) atomicAdd(&a.totals[2], static_cast<unsigned long long>(__popcll(w0)));
+        if (w1 | w2 | w0) atomicAdd(&a.totals[3], static_cast<unsigned long long>(__popcll(w1 | w2 | w0)));
+    }
+}
+
+template <class G>
+__global__ void __launch_bounds__(WAVE) k_match_sample(const int32_t *counts, float temperature, uint64_t seed, uint64_t ply,
+                                                       int32_t *actions, int64_t n)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    const int lane = threadIdx.x;
+    const int64_t game = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
+    const bool live = game < n;
+    const int64_t g = live ? game : 0;
+    PickLane pl;
+    const int action = pick_move<G, MATCH_STREAM>(counts + g * A, live, lane, temperature, nullptr, seed, ply, g, pl);
+    if (live && lane % L == 0) actions[g] = action;
+}
+
+}  // namespace
+
+#define AZ_MATCH_DISPATCH(game, ...)                                               \
+    do {                                                                           \
+        if ((game) == Connect4Dev::GAME_ID) { using G = Connect4Dev; __VA_ARGS__; } \
+        else { using G = OthelloDev; __VA_ARGS__; }                                 \
+    } while (0)
+
+void launch_match_ply(int game, MatchPly a, hipStream_t s)
+{
+    if (a.n <= 0) return;
+    AZ_MATCH_DISPATCH(game, {
+        const unsigned grid = static_cast<unsigned>((a.n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
+        hipLaunchKernelGGL(k_match_ply<G>, dim3(grid), dim3(WAVE), 0, s, a);
+    });
+}
+
+void launch_match_sample(int game, const int32_t *counts, float temperature, uint64_t seed, uint64_t ply, int32_t *actions,
+                         int64_t n, hipStream_t s)
+{
+    if (n <= 0) return;
+    AZ_MATCH_DISPATCH(game, {
+        const unsigned grid = static_cast<unsigned>((n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
+        hipLaunchKernelGGL(k_match_sample<G>, dim3(grid), dim3(WAVE), 0, s, counts, temperature, seed, ply, actions, n);
+    });
+}
+
+}  // namespace az

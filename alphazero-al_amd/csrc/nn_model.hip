@@ -21,6 +21,7 @@ struct az_nn_model {
     int kind = AZ_NN_KIND_CONNECT4_CNN;
     bool attn_heads_fused = true;        // az_nn_attn_heads in place of az_nn_attn_block + az_nn_heads
     bool stem_fused = true;              // az_nn_stem_conv_block_positions in place of the folded stem + the first residual block
+    uint64_t hash_salt = 0;              // AZ_NN_KIND_HASH_*: az_nn_model_create_hash_salted
     az_nn_model_weights w{};
     az_nn_othello_weights ow{};
 };
@@ -63,7 +64,7 @@ __device__ __forceinline__ uint64_t position_hash(uint64_t bb0, uint64_t bb1, bo
 // one 64-lane wavefront per sample: lane = cell (Connect4: 42 of them), a ballot rebuilds the bitboards
 template <bool OTHELLO>
 __global__ void __launch_bounds__(256) k_hash_eval(const float *features, const uint8_t *mask, float *probs, float *wdl,
-                                                   float *ml, int64_t batch, const int32_t *rows, const int64_t *n_rows)
+                                                   float *ml, int64_t batch, const int32_t *rows, const int64_t *n_rows, uint64_t salt)
 {
     constexpr int CELLS = OTHELLO ? 64 : 42, A = OTHELLO ? 65 : 7;
     const int lane = threadIdx.x & 63;
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(256) k_hash_eval(const float *features, const 
         }
         (void)bit;
     }
-    const uint64_t h = position_hash(bb0, bb1, p1);
+    const uint64_t h = position_hash(bb0 ^ salt, bb1, p1);
     const uint8_t *mk = mask != nullptr ? mask + row * A : nullptr;
     if (!OTHELLO) {
         if (lane < 7) {
@@ -125,7 +126,7 @@ __global__ void __launch_bounds__(256) k_hash_eval(const float *features, const 
 // the same function of the position a leaf shows under its symmetry id, from the bitboards: one thread per sample
 template <bool OTHELLO>
 __global__ void __launch_bounds__(256) k_hash_eval_positions(az_nn_positions pos, const uint8_t *mask, float *probs, float *wdl,
-                                                             float *ml, int64_t batch, const int32_t *rows, const int64_t *n_rows)
+                                                             float *ml, int64_t batch, const int32_t *rows, const int64_t *n_rows, uint64_t salt)
 {
     constexpr int A = OTHELLO ? 65 : 7;
     const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -138,7 +139,7 @@ __global__ void __launch_bounds__(256) k_hash_eval_positions(az_nn_positions pos
     const int sym = pos.sym[row];
     if (OTHELLO) { bb0 = az::othello_sym(bb0, sym); bb1 = az::othello_sym(bb1, sym); }
     else if (sym) { bb0 = az::mirror_columns(bb0); bb1 = az::mirror_columns(bb1); }
-    const uint64_t h = position_hash(bb0, bb1, pos.turn[row] > 0);
+    const uint64_t h = position_hash(bb0 ^ salt, bb1, pos.turn[row] > 0);
     const uint8_t *mk = mask != nullptr ? mask + row * A : nullptr;
     if (!OTHELLO) {
         for (int a = 0; a < 7; ++a) {
@@ -192,15 +193,18 @@ int az_nn_model_create(const az_nn_model_weights *w, az_nn_model **out)
     return 0;
 }
 
-int az_nn_model_create_hash(int game, az_nn_model **out)
+int az_nn_model_create_hash_salted(int game, uint64_t salt, az_nn_model **out)
 {
     if (out == nullptr || (game != 0 && game != 1)) return 1;
     auto *m = new (std::nothrow) az_nn_model();
     if (m == nullptr) return 1;
     m->kind = game == 0 ? AZ_NN_KIND_HASH_CONNECT4 : AZ_NN_KIND_HASH_OTHELLO;
+    m->hash_salt = salt;
     *out = m;
     return 0;
 }
+
+int az_nn_model_create_hash(int game, az_nn_model **out) { return az_nn_model_create_hash_salted(game, 0, out); }
 
 int az_nn_model_create_othello(const az_nn_othello_weights *w, az_nn_model **out)
 {
@@ -294,20 +298,20 @@ static int forward_impl(const az_nn_model *m, const float *features, const az_nn
         const dim3 grid(static_cast<unsigned>((batch + 255) / 256)), block(256);
         if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
             hipLaunchKernelGGL(k_hash_eval_positions<true>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
-                               wdl, moves_left, batch, rows, n_rows);
+                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
         else
             hipLaunchKernelGGL(k_hash_eval_positions<false>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
-                               wdl, moves_left, batch, rows, n_rows);
+                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
         return 0;
     }
     if (m->kind != AZ_NN_KIND_CONNECT4_CNN) {
         const dim3 grid(static_cast<unsigned>((batch + 3) / 4)), block(256);
         if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
             hipLaunchKernelGGL(k_hash_eval<true>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
-                               moves_left, batch, rows, n_rows);
+                               moves_left, batch, rows, n_rows, m->hash_salt);
         else
             hipLaunchKernelGGL(k_hash_eval<false>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
-                               moves_left, batch, rows, n_rows);
+                               moves_left, batch, rows, n_rows, m->hash_salt);
         return 0;
     }
     if (scratch == nullptr || scratch_bytes < az_nn_model_scratch_bytes(m, batch)) return 1;

@@ -5,7 +5,7 @@
 //                 schedule of game.py:55-63) and, when recording, this ply's row of the game's
 //                 trajectory (game.py:97-108).  One lane group per game as in kernels.hip (Connect4: 8
 //                 lanes, 8 games per wavefront; Othello: a wavefront): lane e owns action e, Othello's
-//                 65th action (pass) rides with lane 0.
+//                 65th action (pass) rides with lane 0.  The pick itself is sp_pick.h, shared with k_match_ply.
 //   k_sp_advance  after the re-rooting and the game step: ply counters, finished games' rows into the
 //                 finished store, refill, next ply's noise epsilon (game.py:87-91), running totals.
 //                 One lane per game for the bookkeeping; a wavefront then copies the rows of ITS
@@ -23,107 +23,31 @@
 
 #include "dev_rng.h"
 #include "games.h"
+#include "sp_pick.h"
 
 namespace az {
 namespace {
 
 constexpr int WAVE = 64;
 
-template <int L>
-__device__ __forceinline__ unsigned long long group_ballot(bool pred, int lane)
-{
-    const unsigned long long bal = __ballot(pred);
-    constexpr unsigned long long mask = L >= 64 ? ~0ull : ((1ull << (L & 63)) - 1ull);
-    return (bal >> (lane - lane % L)) & mask;
-}
-
-template <int L, class T>
-__device__ __forceinline__ T group_max(T v)
-{
-#pragma unroll
-    for (int o = L / 2; o > 0; o >>= 1) {
-        const T w = __shfl_xor(v, o, L);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-template <int L>
-__device__ __forceinline__ long long group_sum(long long v)
-{
-#pragma unroll
-    for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, L);
-    return v;
-}
-
-// inclusive prefix sum over the lane group, in lane order
-template <int L>
-__device__ __forceinline__ float group_scan(float v, int sub)
-{
-#pragma unroll
-    for (int o = 1; o < L; o <<= 1) {
-        const float w = __shfl_up(v, o, L);
-        if (sub >= o) v += w;
-    }
-    return v;
-}
-
 template <class G, bool RECORD>
 __global__ void __launch_bounds__(WAVE) k_sp_pick(SpPick a)
 {
     constexpr int L = G::LANES, A = G::ACTIONS;
-    constexpr bool TWO = A > L;                       // a second action per lane (Othello: lane 0, the pass)
     const int lane = threadIdx.x, sub = lane % L;
     const int64_t game = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
     const bool live = game < a.n;
     const int64_t g = live ? game : 0;
-    const int32_t *cnt = a.counts + g * A;
-    const bool has0 = live && sub < A, has1 = TWO && live && sub + L < A;
-    const int n0 = has0 ? max(cnt[sub], 0) : 0;
-    const int n1 = has1 ? max(cnt[sub + L], 0) : 0;
     const int ply = a.ply[g];
     const bool dead = a.dead != nullptr && a.dead[g] != 0;
-    const long long total = group_sum<L>(static_cast<long long>(n0) + n1);
 
     // game.py:55-63
     const float temp = (a.temp_decay_moves <= 0 || ply < a.temp_decay_moves) ? a.temperature : a.temp_endgame;
-    int action;
-    if (a.tape != nullptr) {
-        action = a.tape[g];
-    } else if (total == 0) {
-        action = 0;                                    // player.py:355-358
-    } else if (!(temp > 1e-6f)) {
-        // the FIRST maximal count (np.argmax): largest (count, -action)
-        long long key = has0 ? ((static_cast<long long>(n0) << 8) | (255 - sub)) : -1;
-        if (has1) { const long long k1 = (static_cast<long long>(n1) << 8) | (255 - (sub + L)); key = k1 > key ? k1 : key; }
-        key = group_max<L>(key);
-        action = 255 - static_cast<int>(key & 255);
-    } else {
-        // player.py:365-368: weights exp((log N - max log N) / T) over the actions with N > 0, ascending;
-        // one uniform, inverse CDF
-        const float ninf = -__builtin_inff();
-        const float l0 = n0 > 0 ? logf(static_cast<float>(n0)) : ninf;
-        const float l1 = n1 > 0 ? logf(static_cast<float>(n1)) : ninf;
-        const float mx = group_max<L>(l0 > l1 ? l0 : l1);
-        const float w0 = n0 > 0 ? expf((l0 - mx) / temp) : 0.0f;
-        const float w1 = n1 > 0 ? expf((l1 - mx) / temp) : 0.0f;
-        const float c0 = group_scan<L>(w0, sub);
-        const float tot0 = __shfl(c0, L - 1, L);
-        float c1 = 0.0f, tot = tot0;
-        if (TWO) {
-            c1 = tot0 + group_scan<L>(w1, sub);
-            tot = __shfl(c1, L - 1, L);
-        }
-        DevRng rng(a.seed, a.call, static_cast<uint64_t>(g), SP_STREAM);
-        const float target = rng.uniform() * tot;
-        const unsigned long long v0 = group_ballot<L>(n0 > 0, lane), v1 = group_ballot<L>(n1 > 0, lane);
-        const unsigned long long h0 = group_ballot<L>(n0 > 0 && c0 > target, lane);
-        const unsigned long long h1 = group_ballot<L>(n1 > 0 && c1 > target, lane);
-        if (h0) action = __ffsll(static_cast<long long>(h0)) - 1;
-        else if (h1) action = L + __ffsll(static_cast<long long>(h1)) - 1;
-        else if (v1) action = L + 63 - __clzll(static_cast<long long>(v1));     // rounding left the target at the total
-        else action = 63 - __clzll(static_cast<long long>(v0));
-    }
+    PickLane pl;
+    int action = pick_move<G, SP_STREAM>(a.counts + g * A, live, lane, temp, a.tape, a.seed, a.call, g, pl);
+    const int n0 = pl.n0, n1 = pl.n1;
+    const bool has0 = pl.has0, has1 = pl.has1;
+    const long long total = pl.total;
     if (dead) action = -1;
     if (live && sub == 0) a.actions[g] = action;
 

@@ -40,6 +40,7 @@ def lib():
         L.az_mcts_dev_check.argtypes = [vp, vp]
         L.az_mcts_dev_replay.argtypes = [vp, vp, i64, i64, vp]
         L.az_nn_model_create_hash.argtypes = [i32, C.POINTER(vp)]
+        L.az_nn_model_create_hash_salted.argtypes = [i32, C.c_uint64, C.POINTER(vp)]
         L.az_nn_model_destroy.argtypes = [vp]
         L.az_mcts_dev_set_roots.argtypes = [vp, vp, vp, vp, vp]
         L.az_mcts_dev_import_roots.argtypes = [vp, vp, vp, vp]
@@ -189,11 +190,12 @@ class FusedSearch:
             return None
         game = getattr(self.net, "native_hash_game", None)
         if game is not None:
-            # the integer-hash evaluator has a native twin for either game (az_nn_model_create_hash)
+            # the integer-hash evaluator has a native twin for either game (az_nn_model_create_hash[_salted])
             if self._hash_model is None:
                 h = C.c_void_p()
-                if lib().az_nn_model_create_hash(int(game), C.byref(h)) != 0:
-                    raise RuntimeError("az_nn_model_create_hash failed")
+                salt = int(getattr(self.net, "native_hash_salt", 0)) & ((1 << 64) - 1)
+                if lib().az_nn_model_create_hash_salted(int(game), salt, C.byref(h)) != 0:
+                    raise RuntimeError("az_nn_model_create_hash_salted failed")
                 self._hash_model = h
             return self._hash_model
         if self.fast is None or not hasattr(self.fast, "native_model"):

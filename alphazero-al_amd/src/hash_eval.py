@@ -15,6 +15,10 @@ class NumpyHashEvaluator:
     contract (Connect4/Network.py:267-288): the evaluator of bench.py's tree-only CPU baseline."""
     n_actions = 7
 
+    def __init__(self, salt=0):
+        # XOR-ed into the first bitboard word before the hash (az_nn_model_create_hash_salted): 0 is the plain function
+        self.native_hash_salt = int(salt) & ((1 << 64) - 1)
+
     def predict(self, state, action_mask=None):
         state = np.asarray(state)
         turns = state[:, 2, 0, 0].astype(np.int64)
@@ -23,6 +27,7 @@ class NumpyHashEvaluator:
         bit = (np.uint64(1) << (cols * 7 + (5 - rows)).astype(np.uint64))
         bb0 = (bit * (grid == 1)).sum((1, 2), dtype=np.uint64)
         bb1 = (bit * (grid == -1)).sum((1, 2), dtype=np.uint64)
+        bb0 = bb0 ^ np.uint64(self.native_hash_salt)
         with np.errstate(over="ignore"):
             x = bb0 * np.uint64(0x9E3779B97F4A7C15)
             x ^= (bb1 + np.uint64(0x7F4A7C159E3779B9)) * np.uint64(0xBF58476D1CE4E5B9)
@@ -56,9 +61,10 @@ class HashEvaluator(torch.nn.Module):
     n_actions = 7
     native_hash_game = 0        # AZ_GAME_CONNECT4: az_nn_model_create_hash computes the same function
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", salt=0):
         super().__init__()
         self.register_buffer("anchor", torch.zeros(1, device=device))
+        self.native_hash_salt = int(salt) & ((1 << 64) - 1)      # az_nn_model_create_hash_salted
 
     @torch.no_grad()
     def predict_device(self, feats, mask):
@@ -70,7 +76,7 @@ class HashEvaluator(torch.nn.Module):
         bit = torch.ones((), dtype=torch.int64, device=dev) << (cols * 7 + (5 - rows))
         bb0 = (bit * (grid == 1)).sum((1, 2))
         bb1 = (bit * (grid == -1)).sum((1, 2))
-        x = bb0 * _c(0x9E3779B97F4A7C15)
+        x = (bb0 ^ _c(self.native_hash_salt)) * _c(0x9E3779B97F4A7C15)
         x = x ^ ((bb1 + _c(0x7F4A7C159E3779B9)) * _c(0xBF58476D1CE4E5B9))
         x = x + torch.where(turn == 1, torch.full_like(x, _c(0x94D049BB133111EB)),
                             torch.full_like(x, _c(0x2545F4914F6CDD1D)))
@@ -103,9 +109,10 @@ class OthelloHashEvaluator(torch.nn.Module):
     n_actions = 65
     native_hash_game = 1        # AZ_GAME_OTHELLO
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", salt=0):
         super().__init__()
         self.register_buffer("anchor", torch.zeros(1, device=device))
+        self.native_hash_salt = int(salt) & ((1 << 64) - 1)      # az_nn_model_create_hash_salted
 
     @torch.no_grad()
     def predict_device(self, feats, mask):
@@ -116,7 +123,7 @@ class OthelloHashEvaluator(torch.nn.Module):
         bit = torch.ones((), dtype=torch.int64, device=dev) << torch.arange(64, device=dev)
         bb0 = (bit * (grid == 1)).sum(1)
         bb1 = (bit * (grid == -1)).sum(1)
-        x = bb0 * _c(0x9E3779B97F4A7C15)
+        x = (bb0 ^ _c(self.native_hash_salt)) * _c(0x9E3779B97F4A7C15)
         x = x ^ ((bb1 + _c(0x7F4A7C159E3779B9)) * _c(0xBF58476D1CE4E5B9))
         x = x + torch.where(turn == 1, torch.full_like(x, _c(0x94D049BB133111EB)),
                             torch.full_like(x, _c(0x2545F4914F6CDD1D)))

@@ -1,0 +1,221 @@
+"""Evaluation matches between two networks on the device: the gate that decides whether a freshly trained
+network replaces the best one.
+
+The reference's gate is `TrainPipeline.select_best_player` (src/pipeline.py:241-262) on top of
+`_batched_eval_games` (pipeline.py:264-335): two BatchedMCTS objects over the same n games, the side to move
+searches in its own, both are re-rooted with every move, moves are drawn from the visit counts at a low
+temperature (pipeline.py:337-351) - per-ply Python, numpy sampling per game, Env objects on the host.
+
+`EvaluationMatch` is that loop on the native match driver (az_match_* in include/az_mcts.h): positions, ply
+counters, results and the move record live in HBM next to the two engines' trees, and the tail of a ply - the
+move, the game step, results, totals - is one kernel (k_match_ply, csrc/match_kernels.hip).  With two native
+evaluator models (HIP inference twins, hash evaluators) a step is ONE call into the library (az_match_step);
+any other evaluator is searched through `FusedSearch` between az_match_begin_ply and az_match_finish_ply.
+
+Departures from the reference, both deliberate:
+  * the reference's two search objects draw Dirichlet noise and symmetry ids from ONE thread-local mt19937
+    (MCTS.h:13-17); here each engine has its own device generator stream (seeds `seed` and `seed + 1`), and the
+    moves come from a third (keyed by the seed of player +1's engine, the ply and the game);
+  * a finished game is not searched again - its slot is dead, both engines' trees of it stay reset; the reference
+    goes on searching finished games and discards the move.
+
+`select_best(net, best_net, n_games, threshold)` is pipeline.py:241-262 without the bookkeeping: two halves with
+colours swapped, `gate_win_rate` for the arithmetic.  The Elo rating loop against a rollout player, logging and
+the best-network bookkeeping stay with the caller.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from src import fused as F
+from src.selfplay import _reserve_arenas, _setup_search
+
+
+class MatchConfig(C.Structure):
+    """az_match_config (include/az_mcts.h)."""
+    _fields_ = [("temperature", C.c_float), ("record_moves", C.c_int32)]
+
+
+def match_lib():
+    """The engine library with the az_match_* prototypes set."""
+    L = F.lib()
+    if not getattr(L, "_az_match_ready", False):
+        vp, i32, i64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
+        L.az_match_create.argtypes = [vp, vp, C.POINTER(MatchConfig), C.POINTER(vp)]
+        L.az_match_destroy.argtypes = [vp]
+        L.az_match_destroy.restype = None
+        L.az_match_set_positions.argtypes = [vp, vp, vp, vp]
+        L.az_match_step.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+        L.az_match_begin_ply.argtypes = [vp, vp, C.POINTER(i32)]
+        L.az_match_finish_ply.argtypes = [vp, vp]
+        L.az_match_set_action_tape.argtypes = [vp, vp, i64]
+        L.az_match_remaining.argtypes = [vp, C.POINTER(i64)]
+        L.az_match_results.argtypes = [vp, vp, vp, C.POINTER(i64 * 4)]
+        L.az_match_moves.argtypes = [vp, vp]
+        L.az_match_max_plies.argtypes = [vp]
+        L.az_match_sample.argtypes = [i32, vp, C.c_float, u64, u64, vp, i64, vp]
+        L._az_match_ready = True
+    return L
+
+
+def gate_win_rate(results_first, results_second, n_games):
+    """pipeline.py:253-256: `results_first` are the winners of the half the candidate played as +1,
+    `results_second` of the half it played as -1; a draw counts half.  The denominator is `n_games` as the caller
+    asked for them, also when it is odd and only 2 * (n_games // 2) games were played - the reference's figure."""
+    first, second = np.asarray(results_first), np.asarray(results_second)
+    wins = np.sum(first == 1) + np.sum(second == -1)
+    draws = np.sum(first == 0) + np.sum(second == 0)
+    return float((wins + 0.5 * draws) / n_games)
+
+
+def gate_decision(results_first, results_second, n_games, threshold):
+    """pipeline.py:256-262 without `update_best_net`: (win_rate >= threshold, win_rate)."""
+    rate = gate_win_rate(results_first, results_second, n_games)
+    return bool(rate >= threshold), rate
+
+
+class _Side:
+    """One player's engine and evaluator binding (what selfplay._setup_search builds)."""
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+class EvaluationMatch:
+    """`n_games` games between `net_p1` (player +1, moves first from the initial position) and `net_p2` (-1).
+    Defaults are `_batched_eval_games`'s own: c_base 500, noise epsilon 0.05, temperature 0.2, the wrapper's
+    fpu_reduction.  `c_init` may be a pair (player +1, player -1): search parameters live in each engine's own
+    config.  positions: (bb_p1, bb_p2, turns) as integer arrays of n_games entries, one side to move throughout -
+    an opening suite instead of the initial position.  `play()` runs to the end and returns the winners
+    (int32, +1 / -1 / 0) like the reference; `step(n)`, `remaining()`, `results()`, `moves()` are the pieces."""
+
+    def __init__(self, net_p1, net_p2, n_games, n_playout=200, vl_batch=1, c_init=1.25, c_base=500, alpha=0.3,
+                 eval_noise_eps=0.05, eval_temp=0.2, use_symmetry=True, mlh_slope=0.0, mlh_cap=0.2,
+                 score_utility_factor=0.0, score_scale=8.0, value_decay=1.0, fpu_reduction=0.4, seed=0, game="Connect4",
+                 table_log2=0, positions=None, record_moves=False, reserve_slots=None):
+        self._mt = None
+        self.B, self.n_playout, self.vl_batch = int(n_games), int(n_playout), int(vl_batch)
+        self.game = game
+        self.sides = []
+        for i, (net, ci) in enumerate(zip((net_p1, net_p2), _pair(c_init))):
+            s = _Side()
+            _setup_search(s, net, n_games, n_playout, vl_batch, ci, c_base, alpha, eval_noise_eps, fpu_reduction, use_symmetry,
+                          mlh_slope, mlh_cap, value_decay, eval_temp, 0, eval_temp, int(seed) + i, table_log2, game,
+                          score_utility_factor, score_scale)
+            _reserve_arenas(s, reserve_slots)
+            self.sides.append(s)
+        self.device = self.sides[0].device
+        self.MAX_PLIES = self.sides[0].MAX_PLIES
+        self.A = self.sides[0].search.action_size
+        self.L = match_lib()
+        self.config = MatchConfig(float(eval_temp), int(bool(record_moves)))
+        self.record_moves = bool(record_moves)
+        mt = C.c_void_p()
+        with torch.cuda.device(self.device):
+            F.check(self.L.az_match_create(self.sides[0].h, self.sides[1].h, C.byref(self.config), C.byref(mt)))
+        self._mt = mt
+        self._tape = None
+        self.poll_every = 4
+        if positions is not None:
+            self.set_positions(*positions)
+
+    def __del__(self):
+        try:
+            if self.__dict__.get("_mt") is not None:          # before the engines it borrows
+                mt, self._mt = self._mt, None
+                self.L.az_match_destroy(mt)
+        except Exception:
+            pass
+
+    def set_positions(self, bb_p1, bb_p2, turns):
+        a = np.ascontiguousarray(np.asarray(bb_p1).astype(np.uint64))
+        b = np.ascontiguousarray(np.asarray(bb_p2).astype(np.uint64))
+        t = np.ascontiguousarray(turns, dtype=np.int32)
+        assert a.shape == b.shape == t.shape == (self.B,)
+        with torch.cuda.device(self.device):
+            F.check(self.L.az_match_set_positions(self._mt, a.ctypes.data, b.ctypes.data, t.ctypes.data))
+
+    def set_action_tape(self, actions):
+        """actions: (n_plies, n_games) integers, -1 where a game is over; None ends the tape (test hook)."""
+        if actions is None:
+            self._tape = None
+            F.check(self.L.az_match_set_action_tape(self._mt, None, 0))
+            return
+        t = torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(self.device).contiguous()
+        assert t.dim() == 2 and t.shape[1] == self.B
+        torch.cuda.current_stream().synchronize()
+        self._tape = t                                        # read by the kernel: kept alive here
+        F.check(self.L.az_match_set_action_tape(self._mt, t.data_ptr(), t.shape[0]))
+
+    def native_models(self):
+        """(model of +1, model of -1) when both evaluators have a native model object, else None."""
+        models = []
+        for s in self.sides:
+            s.fused._sync_fast_net()
+            models.append(s.fused._native_model())
+        return None if any(m is None for m in models) else tuple(models)
+
+    def step(self, n=1):
+        """n plies in every game that is still running."""
+        models = self.native_models()
+        s = F._stream()
+        with torch.cuda.device(self.device):
+            if models is not None:
+                table = 1 if self.sides[0].fused.table_log2 else 0
+                F.check(self.L.az_match_step(self._mt, models[0], models[1], self.n_playout, max(1, self.vl_batch), table,
+                                             int(n), s))
+                return
+            mover = C.c_int()
+            for _ in range(int(n)):
+                F.check(self.L.az_match_begin_ply(self._mt, s, C.byref(mover)))
+                if mover.value == 0:
+                    return
+                self.sides[0 if mover.value > 0 else 1].fused.search(self.n_playout, self.vl_batch)
+                F.check(self.L.az_match_finish_ply(self._mt, s))
+
+    def remaining(self):
+        """Games still running (synchronises)."""
+        n = C.c_int64()
+        F.check(self.L.az_match_remaining(self._mt, C.byref(n)))
+        return n.value
+
+    def play(self):
+        """Every game to its end: the winners, int32 [n_games] (pipeline.py:335).  The host asks how many games
+        are left every `poll_every` plies, not every ply, and never plays past the game's ply bound."""
+        played = 0
+        while played < self.MAX_PLIES:
+            n = min(int(self.poll_every), self.MAX_PLIES - played)
+            self.step(n)
+            played += n
+            if self.remaining() == 0:
+                break
+        return self.results()["winner"]
+
+    def results(self):
+        """winner (+1 / -1 / 0; 0 while running) and length per game, totals (synchronises)."""
+        w, ln, t = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32), (C.c_int64 * 4)()
+        F.check(self.L.az_match_results(self._mt, w.ctypes.data, ln.ctypes.data, C.byref(t)))
+        return dict(winner=w, length=ln, p1_wins=t[0], p2_wins=t[1], draws=t[2], running=t[3])
+
+    def moves(self):
+        """With record_moves: int32 [max_plies, n_games], -1 where the game had ended (synchronises)."""
+        assert self.record_moves
+        out = np.zeros((self.MAX_PLIES, self.B), np.int32)
+        F.check(self.L.az_match_moves(self._mt, out.ctypes.data))
+        return out
+
+    def engine_counters(self):
+        return tuple(F.counters(s.h) for s in self.sides)
+
+
+def select_best(net, best_net, n_games, threshold, **kw):
+    """pipeline.py:241-262: n_games // 2 games with `net` as +1, as many with `best_net` as +1;
+    returns (win_rate >= threshold, win_rate).  Keyword arguments go to EvaluationMatch (the second half uses
+    seed + 2, its engines' generators differ from the first half's)."""
+    n_half = int(n_games) // 2
+    seed = int(kw.pop("seed", 0))
+    first = EvaluationMatch(net, best_net, n_half, seed=seed, **kw).play() if n_half else np.zeros(0, np.int32)
+    second = EvaluationMatch(best_net, net, n_half, seed=seed + 2, **kw).play() if n_half else np.zeros(0, np.int32)
+    return gate_decision(first, second, n_games, threshold)

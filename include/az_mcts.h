@@ -400,6 +400,87 @@ int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int6
 int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c,
                        uint64_t seed, uint64_t call, int32_t *actions, int64_t n, void *stream);
 
+/* ---- evaluation matches between two networks (alphazero-al_amd/csrc/match_kernels.hip) ---------------------
+ * The reference's gate plays n games between two players in lock step (src/pipeline.py:264-335,
+ * `_batched_eval_games`): two BatchedMCTS objects over the same games (pipeline.py:280-293), the side to move
+ * searches in its own (pipeline.py:306-318), the move comes from its visit counts (pipeline.py:337-351) and BOTH
+ * objects are re-rooted with it (pipeline.py:323-324), so each player keeps its subtree across the opponent's
+ * reply.  Here a match object borrows TWO engines - engine_p1 holds the trees of the player who is +1, engine_p2
+ * those of -1; same game, same n_envs, same device - and owns the positions, per-game ply counters, dead flags,
+ * results and an optional move record in HBM.  A ply outside the search is: the mover engine's root counts,
+ * k_match_ply (the move, the game step, done / winner / length / dead flag, the move record, the totals - ONE
+ * launch), the re-rooting of both engines with the same actions, the reset of both engines' trees of the games that
+ * ended.  Search parameters (c_init, c_base, alpha, noise epsilon, symmetry, ...) stay in each engine's own
+ * az_search_config: the two players may differ.  Destroy the match BEFORE the engines; make every call of a match on
+ * ONE stream and from one thread at a time.
+ *
+ * Every game has the same side to move and turns alternate strictly (Othello's pass is action 64), so one engine
+ * searches per ply.  A finished game is dead from then on: action -1 to both engines (their trees of that game stay
+ * reset), no further row in the move record - like a self-play slot with refill = 0.  The reference goes on searching
+ * finished games and discards the move (pipeline.py:306-318 search every env).
+ *
+ * temperature: T <= 1e-6 plays the first most visited move, else the move is drawn with probability N^(1/T)
+ * (pipeline.py:337-351, the rule of player.py:362-371) - the pick of k_sp_pick, shared.  Draws come from the device
+ * generator on a stream of its own (MATCH_STREAM in dev_rng.h, not the self-play driver's), keyed by (the seed of
+ * engine_p1, the match's ply counter, the game): az_selfplay_sample does NOT reproduce them, az_match_sample does.
+ * The reference's two objects draw noise and symmetry ids from ONE thread-local mt19937 (MCTS.h:13-17); here each
+ * engine has its own device generator stream. */
+typedef struct az_match_config {
+    float   temperature;
+    int32_t record_moves;
+} az_match_config;
+#define AZ_MATCH_CONFIG_BYTES 8
+#ifdef __cplusplus
+static_assert(sizeof(az_match_config) == AZ_MATCH_CONFIG_BYTES, "az_match_config layout");
+#else
+_Static_assert(sizeof(az_match_config) == AZ_MATCH_CONFIG_BYTES, "az_match_config layout");
+#endif
+
+typedef struct az_match az_match;
+
+/* Every game at its initial position with player +1 to move, ply 0, every tree of both engines reset
+ * (synchronises).  AZ_ERR_ARG: the engines differ in game, n_envs or device, or are one and the same. */
+int  az_match_create(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, az_match **out);
+void az_match_destroy(az_match *mt);
+/* Start positions from HOST arrays of n_envs entries (an opening suite; deterministic tests); before the first ply
+ * only (AZ_ERR_ARG after it).  Every game must have the same side to move (AZ_ERR_ARG otherwise).  Both engines'
+ * trees of every game are reset; a position that is already over counts as finished at ply 0 with its winner and
+ * length 0.  Connect4's last mover and Othello's pass count are derived as an import derives them.  Synchronises. */
+int az_match_set_positions(az_match *mt, const uint64_t *bb_p1, const uint64_t *bb_p2, const int32_t *turns);
+/* n_plies whole plies on `stream`: per ply az_mcts_dev_set_roots into the mover's engine, az_mcts_dev_search on it
+ * with the mover's model (model_p1 when +1 moves), its root counts, k_match_ply, az_mcts_dev_prune_roots of BOTH
+ * engines, az_mcts_dev_reset_masked of BOTH, az_mcts_dev_check of both.  Nothing but enqueues unless an engine's
+ * buffers must grow; the host runs at most one ply ahead of the device.  Once every game is over (as
+ * az_match_remaining last saw it, or as the newest completed ply reported) or the game's ply bound is reached, the
+ * remaining plies are not played: the call changes nothing.  AZ_ERR_ARG: a null model. */
+int az_match_step(az_match *mt, const struct az_nn_model *model_p1, const struct az_nn_model *model_p2, int n_playout,
+                  int K, int use_table, int n_plies, void *stream);
+/* The two halves of a ply, for an evaluator that is not an az_nn_model: begin_ply puts the positions into the
+ * mover's engine as roots and reports the mover (+1: search engine_p1, -1: engine_p2; 0: the match is over, nothing
+ * was done and finish_ply will do nothing); the caller searches that engine (az_mcts_dev_prepare_stream and the
+ * select / backprop calls, or alphazero-al_amd/src/fused.py); finish_ply is everything after the search. */
+int az_match_begin_ply(az_match *mt, void *stream, int *mover);
+int az_match_finish_ply(az_match *mt, void *stream);
+/* Test hook - recorded moves instead of the pick, the contract of az_selfplay_set_action_tape: actions int32
+ * [n_plies][n_envs] in DEVICE memory, kept alive by the caller; the p-th ply after this call plays actions[p]
+ * (-1: the game does not move).  Running past the tape is AZ_ERR_STATE.  NULL ends it. */
+int az_match_set_action_tape(az_match *mt, const int32_t *actions, int64_t n_plies);
+/* Games still running (synchronises). */
+int az_match_remaining(az_match *mt, int64_t *n);
+/* HOST arrays, any of them NULL (synchronises): winner[n_envs] +1 / -1 / 0 (0 while the game is running),
+ * length[n_envs] plies played so far, totals = won by +1, won by -1, drawn, still running. */
+int az_match_results(az_match *mt, int32_t *winner, int32_t *length, int64_t totals[4]);
+/* With record_moves: the [max_plies][n_envs] actions played, -1 where the game had ended (or the ply has not been
+ * played); max_plies = az_match_max_plies: 42 for Connect4, 126 for Othello.  HOST array (synchronises). */
+int az_match_moves(az_match *mt, int32_t *actions);
+int az_match_max_plies(const az_match *mt);
+/* k_match_ply's pick on caller-supplied counts, for tests: counts int32 [n][A] in DEVICE memory -> actions int32 [n];
+ * draws are keyed by (seed, ply, row) on the match's generator stream - with seed = what az_mcts_set_seed(s >= 0)
+ * leaves in engine_p1, (uint32) s * 0x9E3779B97F4A7C15 + 1, and ply = the match's ply counter it reproduces a
+ * match's draws. */
+int az_match_sample(int game, const int32_t *counts, float temperature, uint64_t seed, uint64_t ply, int32_t *actions,
+                    int64_t n, void *stream);
+
 /* ---- augmented training batches out of the replay tensors, on the device (k_replay_batch) ----------------
  * The reference's learner draws a sample on the host (src/ReplayBuffer.py:130-145: np.random.randint, `get`, a
  * TensorDataset behind a shuffling DataLoader that collates sample by sample) and passes every batch through the

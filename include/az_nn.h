@@ -194,6 +194,11 @@ int az_nn_model_create(const az_nn_model_weights *w, az_nn_model **out);
  * native loop (az_mcts_dev_search) can be compared bit for bit with the CPU oracle, and so that the
  * tree kernels can be timed with no evaluator to speak of.  Needs no scratch. */
 int az_nn_model_create_hash(int game, az_nn_model **out);
+/* A second deterministic player: `salt` is XOR-ed into the first bitboard word of the position the evaluator
+ * is shown (after the symmetry transform) before the hash.  Salt 0 is az_nn_model_create_hash.  Two salts give
+ * two different evaluators that numpy reproduces bit for bit (src/hash_eval.py `salt`): the players of the
+ * evaluation-match tests (az_match_* in az_mcts.h). */
+int az_nn_model_create_hash_salted(int game, uint64_t salt, az_nn_model **out);
 #define AZ_NN_KIND_CONNECT4_CNN  0
 #define AZ_NN_KIND_HASH_CONNECT4 1
 #define AZ_NN_KIND_HASH_OTHELLO  2

@@ -171,6 +171,7 @@ class FastOthelloNet(torch.nn.Module):
         if L.az_nn_model_create_othello(C.byref(w), C.byref(handle)) != 0:
             raise RuntimeError("az_nn_model_create_othello refused the weights")
         self.__dict__["_model_keep"] = keep
+        self.__dict__["_model_w"] = w                                # what the object was built from (the tests call its entry points with it)
         self.__dict__["_model"] = handle
         return handle
 

@@ -105,6 +105,19 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
     // ---- H = RMSNorm(x) * w, as MFMA fragments (token = tile*16 + lane&15, 8 channels per k-step)
+    // The sample's six row vectors are requested together and without a branch: a padding token reads row 41 and is
+    // zeroed once the vector is in, so the first tile's statistics start when its two vectors have arrived while the
+    // later tiles' are in flight - one memory latency per sample.  GATE4 keeps the earlier order (tile 2 behind an
+    // exec-mask branch, requested after tiles 0 and 1 have arrived): the same bytes, the oracle of this one.
+    V8 xv[TT][2];
+    if constexpr (!GATE4) {
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+            const int tok = tt * 16 + l15, row = tok < CELLS ? tok : CELLS - 1;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) xv[tt][s] = *reinterpret_cast<const V8 *>(xs + row * C + 32 * s + 8 * l4);
+        }
+    }
     bf16x8 hf[TT][2];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
@@ -113,7 +126,12 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             V8 v; v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
-            if (tok < CELLS) v = *reinterpret_cast<const V8 *>(xs + tok * C + 32 * s + 8 * l4);
+            if constexpr (GATE4) {
+                if (tok < CELLS) v = *reinterpret_cast<const V8 *>(xs + tok * C + 32 * s + 8 * l4);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v.w[i] = tok < CELLS ? xv[tt][s].w[i] : 0u;
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 f[s][i] = unpack2(v.w[i]);

@@ -120,15 +120,37 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
         const bool more = b0 < B;
         if (more) {
             const int64_t b1 = b0 + S;
+            // The policy tail's two dependent loads, off its path: the pair's output rows are requested next to the first
+            // sample's rows, and the mask bytes at those rows after the first sample's token pass - a sample ahead of the
+            // tail that reads them.  srow, mbyte: of the sample this lane's policy column belongs to.  srow is consumed
+            // through an opaque copy (the "+v" statements below): otherwise the compiler widens it where it is loaded and
+            // waits for it there.
+            int32_t srow = 0;
+            uint32_t mbyte = 1;
 #pragma unroll 1
             for (int hs = 0; hs < 2; ++hs) {
                 const int64_t bs = hs == 0 ? b0 : b1;
                 if (bs >= B) break;
                 refresh_lane();
+                if constexpr (!LEGACY) {
+                    if (hs == 0) {
+                        const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+                        if (scatter != nullptr && bc < B) srow = scatter[bc];
+                    }
+                }
                 const uint16_t *xs = x + bs * (CELLS * C);
 
                 f32x4 out[4][TT];
                 attn::attn_sample<LEGACY>(xs, s_w32, s_w16, s_pw, s_qk, s_gate, bounded, eps, lane, l15, l4, out);
+                // the residual rows the token pass adds, requested one token tile ahead of the tile that consumes them
+                // (a padding token reads row 41 and is zeroed on arrival); LEGACY loads each where it is used
+                V4 xq[TT][4];
+                auto request_rows = [&](int qt) {
+                    const int tok = qt * 16 + l15, row = tok < CELLS ? tok : CELLS - 1;
+#pragma unroll
+                    for (int ot = 0; ot < 4; ++ot) xq[qt][ot] = *reinterpret_cast<const V4 *>(xs + row * C + ot * 16 + 4 * l4);
+                };
+                if constexpr (!LEGACY) request_rows(0);
                 wave_lds_sync();                     // the gates are read: the token image may overwrite them
 
                 // ======== token pass on y = bf16(x + out): lane = token qt*16 + l15, channels 16 ot + 4 l4 + r ========
@@ -140,10 +162,21 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                     const int tok = qt * 16 + l15;
                     const bool live = tok < CELLS;
                     f32x2 f[4][2], ss2 = {0.0f, 0.0f}, sc2 = {0.0f, 0.0f};
+                    if constexpr (!LEGACY) {
+                        if (qt + 1 < TT) {
+                            request_rows(qt + 1);
+                            asm volatile("" ::: "memory");       // the requests stay ahead of this tile's arithmetic
+                        }
+                    }
 #pragma unroll
                     for (int ot = 0; ot < 4; ++ot) {
                         V4 xr; xr.w[0] = xr.w[1] = 0;
-                        if (live) xr = *reinterpret_cast<const V4 *>(xs + tok * C + ot * 16 + 4 * l4);
+                        if constexpr (LEGACY) {
+                            if (live) xr = *reinterpret_cast<const V4 *>(xs + tok * C + ot * 16 + 4 * l4);
+                        } else {
+                            xr.w[0] = live ? xq[qt][ot].w[0] : 0u;
+                            xr.w[1] = live ? xq[qt][ot].w[1] : 0u;
+                        }
                         const f32x4 ngw = cvec4(K_PNGW, ot);
                         f[ot][0] = unpack2(pack2(out[ot][qt][0] + bf_lo(xr.w[0]), out[ot][qt][1] + bf_hi(xr.w[0])));
                         f[ot][1] = unpack2(pack2(out[ot][qt][2] + bf_lo(xr.w[1]), out[ot][qt][3] + bf_hi(xr.w[1])));
@@ -209,6 +242,17 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                         if (l15 == 0) *reinterpret_cast<V4 *>(&s_slot[(nslot + hs) * C + 16 * ot + 4 * l4]) = o;
                     }
                 }
+                if constexpr (!LEGACY) {
+                    if (hs == 0) {
+                        // the rows are in (they came back with the first sample's): the mask bytes of the pair.  The guard
+                        // comes before the address: an index outside the rows is never dereferenced.
+                        const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+                        int32_t sr = srow;
+                        asm volatile("" : "+v"(sr));
+                        const int64_t b = scatter != nullptr ? sr : bc;
+                        if ((l15 & 7) != 7 && bc < B && b >= 0 && b < rows_total && mask != nullptr) mbyte = mask[b * COLS + (l15 & 7)];
+                    }
+                }
                 wave_lds_sync();
                 pool_columns<VS>(s_score, s_pn, s_vec, hs, lane);
             }
@@ -218,7 +262,11 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                 heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, b0, b1, B, rows_total, scatter, eps,
                                     lane, l15, l4);
             } else {
-                policy_tail<VS>(s_a, s_c, s_vec, w, mask, probs, b0, b1, B, rows_total, scatter, lane, l15, l4);
+                const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+                asm volatile("" : "+v"(srow));
+                const int64_t b = scatter != nullptr ? srow : bc;
+                const bool real = bc < B && b >= 0 && b < rows_total;
+                policy_tail_at<VS>(s_a, s_c, s_vec, w, probs, b, real, real && mask != nullptr && mbyte == 0, lane, l15, l4);
                 nslot += b1 < B ? 2 : 1;
             }
         }

@@ -130,21 +130,19 @@ __device__ __forceinline__ void pool_columns(float *s_score, const void *s_pn, u
 // The policy of both samples of a pair, b0 and b1 (b1 >= B: a half-empty pair): columns 0-6 and 8-14 of the B operand.
 // Compact batch: sample b stands for row scatter[b] of the mask and of the outputs; an index outside the rows (a list
 // longer than what was written) is dropped, never dereferenced.
+// policy_tail_at(): the same for a caller that already holds, per lane, its column's output row b, whether that row is
+// written (real) and whether the column is masked out (a real row whose mask byte is 0) - k_attn_heads requests the
+// row index and the mask byte a sample ahead, so that the tail waits for neither.
 template <int VS>
-__device__ __forceinline__ void policy_tail(const V8 *s_a, const float (*s_c)[C], const uint16_t *s_vec,
-                                            const az_nn_heads_weights &w, const uint8_t *mask, float *probs, int64_t b0,
-                                            int64_t b1, int64_t B, int64_t rows_total, const int32_t *scatter, int lane,
-                                            int l15, int l4)
+__device__ __forceinline__ void policy_tail_at(const V8 *s_a, const float (*s_c)[C], const uint16_t *s_vec,
+                                               const az_nn_heads_weights &w, float *probs, int64_t b, bool real, bool masked,
+                                               int lane, int l15, int l4)
 {
     auto afrag = [&](int f) { return as_bf16x8(s_a[f * 64 + lane]); };
     auto bfrag = [&](int ks) { return as_bf16x8(*reinterpret_cast<const V8 *>(&s_vec[l15 * VS + 32 * ks + 8 * l4])); };
     auto cvec2 = [&](int which, int m, int h) { return *reinterpret_cast<const f32x2 *>(&s_c[which][16 * m + 4 * l4 + 2 * h]); };
     const bool live = (l15 & 7) != 7;          // columns 7 and 15 are no policy columns
-    const int half = l15 >> 3;                 // which sample of the pair the column belongs to
     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int64_t bc = half == 0 ? b0 : b1;       // the sample this lane's column belongs to
-    const int64_t b = (bc < B && scatter != nullptr) ? scatter[bc] : bc;
-    const bool real = bc < B && b >= 0 && b < rows_total;
     f32x4 ap[4];
     {
         const bf16x8 v0 = bfrag(0), v1 = bfrag(1);
@@ -164,13 +162,25 @@ __device__ __forceinline__ void policy_tail(const V8 *s_a, const float (*s_c)[C]
             part2 = __builtin_elementwise_fma(rbf2(silu2(xv)), cvec2(K_POUT_W, m, hh), part2);
         }
     float logit = col_sum(part2.x + part2.y) + w.p_out_b;
-    if (live && real && mask != nullptr && mask[b * COLS + (l15 & 7)] == 0) logit = -1e9f;
+    if (live && masked) logit = -1e9f;
     if (!live) logit = -INFINITY;
     const float mx = max8(logit);
     const float e = live ? fast_exp(logit - mx) : 0.0f;
     const float den = sum8(e);
     if (live && real && l4 == 0) probs[b * COLS + (l15 & 7)] = e * __builtin_amdgcn_rcpf(den);
     wave_lds_sync();
+}
+template <int VS>
+__device__ __forceinline__ void policy_tail(const V8 *s_a, const float (*s_c)[C], const uint16_t *s_vec,
+                                            const az_nn_heads_weights &w, const uint8_t *mask, float *probs, int64_t b0,
+                                            int64_t b1, int64_t B, int64_t rows_total, const int32_t *scatter, int lane,
+                                            int l15, int l4)
+{
+    const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;       // the sample this lane's column belongs to
+    const int64_t b = (bc < B && scatter != nullptr) ? scatter[bc] : bc;
+    const bool real = bc < B && b >= 0 && b < rows_total;
+    const bool masked = (l15 & 7) != 7 && real && mask != nullptr && mask[b * COLS + (l15 & 7)] == 0;
+    policy_tail_at<VS>(s_a, s_c, s_vec, w, probs, b, real, masked, lane, l15, l4);
 }
 
 // The value / moves-left head of the live columns of the B operand (row l15 of s_vec = pool_norm(mean) of the sample

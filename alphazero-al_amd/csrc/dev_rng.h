@@ -1,5 +1,6 @@
 // dev_rng.h - the counter-based generator of the dev_* entry points, shared by the search kernels
-// (kernels.hip: symmetry ids, Dirichlet noise, random playouts) and the self-play driver's move
+// (kernels.hip: symmetry ids, re-rooting noise, random playouts; backup_kernels.hip: Dirichlet noise of root
+// expansions) and the self-play driver's move
 // sampler (selfplay_kernels.hip).  A stream is named by (seed, call, a, b): the engine's seed, a
 // counter that moves per use, an index (tree, leaf, game) and a small constant per purpose - streams
 // in use: b = 3 playouts, 7 symmetry ids, 16.. and 128.. root noise, SP_STREAM the driver's moves,

@@ -1,5 +1,5 @@
 // kernels.h - launch interface between the host engine (engine.hip) and the gfx950 kernels
-// (kernels.hip).  Everything here is plain data: device pointers and sizes.
+// (kernels.hip, select_kernels.hip, backup_kernels.hip and the *_kernels.hip of the drivers).  Everything here is plain data: device pointers and sizes.
 #pragma once
 
 #include <hip/hip_runtime.h>

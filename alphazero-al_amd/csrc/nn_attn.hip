@@ -12,6 +12,8 @@
 // Three workgroups of four wavefronts per CU (three wavefronts per SIMD): 158 registers, the per-sample constants and
 // the gates in LDS (37 KB per workgroup).  k_attn_block<true> is the earlier gate arrangement (attn::attn_sample's
 // GATE4; 46 KB), launched when az_nn_debug bit 8 is set: same bytes, for A/B runs and as the tests' oracle.
+#include <cfloat>
+
 #include "az_nn.h"
 #include "nn_attn_core.h"
 
@@ -77,7 +79,8 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
     const int64_t wgs = (batch + 3) / 4;
     const unsigned cap = 256u * 3u * 2u;       // two rounds of resident workgroups
     const unsigned grid = static_cast<unsigned>(wgs < cap ? wgs : cap);
-    const auto kern = (az_nn_debug_flags() & AZ_NN_DEBUG_LEGACY_TAIL) ? k_attn_block<true> : k_attn_block<false>;
+    // the default form takes its reciprocal square roots bare (rsq_normal): a smaller eps goes to the form that guards them
+    const auto kern = ((az_nn_debug_flags() & AZ_NN_DEBUG_LEGACY_TAIL) || !(eps >= FLT_MIN)) ? k_attn_block<true> : k_attn_block<false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(prenorm_w),
                        static_cast<const uint16_t *>(qkvg_w), static_cast<const uint16_t *>(q_norm_w),

@@ -25,7 +25,9 @@
 // ends up with head g of its token in every accumulator register: it computes ONE sigmoid and stores one float, and
 // the head loop reads gate (token tile, head h, token l15) from the slot lane group h wrote.  GATE4 = true is the
 // earlier arrangement (row 4 g + r = head r: every lane computes all four sigmoids and reads back its own), kept as
-// a second instantiation for A/B runs; the dot products, and so the bits, are the same.
+// a second instantiation for A/B runs; the dot products, and so the bits, are the same.  GATE4 also keeps the
+// instruction sequences the default form shortened - rsqrtf() with its denormal-range guard, one col_sum per value, the
+// query tiles one at a time - where the default takes rsq_normal(), col_sum2 and the three tiles' scores side by side.
 #pragma once
 
 #include "nn_common.h"
@@ -85,6 +87,20 @@ __device__ __forceinline__ bool scores_bounded(const float *s_qk, int l4)
     }
     return 16.0f * col_max(mq) * col_max(mk) < 100.0f;
 }
+// The same with both maxima through one set of swaps (col_max2), for the default form of k_attn_heads.  k_attn_block
+// stays on scores_bounded(): with this one in its default form the compiler schedules the prologue of the OTHER
+// instantiation in the same file differently, and that one is kept as it compiles today.
+__device__ __forceinline__ bool scores_bounded_paired(const float *s_qk, int l4)
+{
+    float mq = 0.0f, mk = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        mq = fmaxf(mq, fabsf(s_qk[4 * l4 + r]));
+        mk = fmaxf(mk, fabsf(s_qk[HD + 4 * l4 + r]));
+    }
+    col_max2(mq, mk);
+    return 16.0f * mq * mk < 100.0f;
+}
 
 // One sample: xs = its 42 x 64 residual-stream rows (bf16), out = out^T in the MFMA C layout (lane holds channels
 // 16 ot + 4 l4 + r of token qt*16 + l15).  s_gate: this wavefront's gate store (GATE_N floats; GATE4: GATE_N f32x4),
@@ -103,6 +119,12 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
         return r.s;
     };
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    // 1 / sqrt of an RMS statistic, sum / n + eps.  The default form is launched with eps >= FLT_MIN only (the host
+    // entry points see to it), which is rsq_normal()'s precondition; GATE4 keeps rsqrtf() and takes any eps.
+    auto rsq = [](float v) {
+        if constexpr (GATE4) return rsqrtf(v);
+        else return rsq_normal(v);
+    };
 
     // ---- H = RMSNorm(x) * w, as MFMA fragments (token = tile*16 + lane&15, 8 channels per k-step)
     // The sample's six row vectors are requested together and without a branch: a padding token reads row 41 and is
@@ -139,7 +161,7 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             }
         }
         const float ss = col_sum(ss2.x + ss2.y);
-        const float r = rsqrtf(ss * (1.0f / C) + eps);
+        const float r = rsq(ss * (1.0f / C) + eps);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             V8 o;
@@ -189,8 +211,14 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             f32x2 q2[2] = {{q[0], q[1]}, {q[2], q[3]}}, k2[2] = {{k[0], k[1]}, {k[2], k[3]}};
             const f32x2 qq = __builtin_elementwise_fma(q2[1], q2[1], q2[0] * q2[0]);
             const f32x2 kk = __builtin_elementwise_fma(k2[1], k2[1], k2[0] * k2[0]);
-            const float qs = col_sum(qq.x + qq.y), ks = col_sum(kk.x + kk.y);
-            const float qr = rsqrtf(qs * (1.0f / HD) + eps), kr = rsqrtf(ks * (1.0f / HD) + eps);
+            float qs, ks;
+            if constexpr (GATE4) {
+                qs = col_sum(qq.x + qq.y), ks = col_sum(kk.x + kk.y);
+            } else {
+                qs = qq.x + qq.y, ks = kk.x + kk.y;
+                col_sum2(qs, ks);
+            }
+            const float qr = rsq(qs * (1.0f / HD) + eps), kr = rsq(ks * (1.0f / HD) + eps);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const f32x2 qw = *reinterpret_cast<const f32x2 *>(&s_qk[4 * l4 + 2 * r]);
@@ -201,64 +229,141 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             kb[tt] = to_s16x4(f32x4{k2[0].x, k2[0].y, k2[1].x, k2[1].y});
             vb[tt] = to_s16x4(v);
         }
+        if constexpr (GATE4) {
+            // the earlier form, one query tile at a time, as it stood: the oracle of the one below
 #pragma unroll
-        for (int qt = 0; qt < TT; ++qt) {
-            // S^T tile rows = keys, column = query lane&15
-            f32x4 st[TT];
-            float den;
-            if (bounded) {
-                // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
-                // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
-                f32x2 den2 = {0.0f, 0.0f};
+            for (int qt = 0; qt < TT; ++qt) {
+                // S^T tile rows = keys, column = query lane&15
+                f32x4 st[TT];
+                float den;
+                if (bounded) {
+                    // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
+                    // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
+                    f32x2 den2 = {0.0f, 0.0f};
 #pragma unroll
-                for (int kt = 0; kt < TT; ++kt) {
-                    st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
+                    for (int kt = 0; kt < TT; ++kt) {
+                        st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
 #pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
-                        const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
-                        st[kt][r] = e.x;
-                        st[kt][r + 1] = e.y;
-                        den2 += e;
+                        for (int r = 0; r < 4; r += 2) {
+                            const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
+                            st[kt][r] = e.x;
+                            st[kt][r + 1] = e.y;
+                            den2 += e;
+                        }
                     }
+                    den = col_sum(den2.x + den2.y) - static_cast<float>(TT * 16 - CELLS);
+                } else {
+                    float m = -INFINITY;
+#pragma unroll
+                    for (int kt = 0; kt < TT; ++kt) {
+                        st[kt] = MFMA16(kb[kt], qb[qt], zero);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
+                            m = fmaxf(m, st[kt][r]);
+                        }
+                    }
+                    m = col_max(m);
+                    f32x2 den2 = {0.0f, 0.0f};
+                    const f32x2 nm = {-m, -m};
+#pragma unroll
+                    for (int kt = 0; kt < TT; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; r += 2) {
+                            const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
+                            const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
+                            st[kt][r] = e.x;
+                            st[kt][r + 1] = e.y;
+                            den2 += e;
+                        }
+                    den = col_sum(den2.x + den2.y);
                 }
-                den = col_sum(den2.x + den2.y) - static_cast<float>(TT * 16 - CELLS);
-            } else {
-                float m = -INFINITY;
+                // normalise after the product: O^T = (V^T . E^T) / den, one scale per output element
+                const float gq = GATE4 ? reinterpret_cast<const float *>(&s_gate[qt * 64 + lane])[h] : s_gate1[qt * 64 + h * 16 + l15];
+                const float scale = __builtin_amdgcn_rcpf(den) * gq;
+                f32x4 o = zero;                                  // O^T rows = d, column = query
 #pragma unroll
-                for (int kt = 0; kt < TT; ++kt) {
-                    st[kt] = MFMA16(kb[kt], qb[qt], zero);
+                for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], to_s16x4(st[kt]), o);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
-                        m = fmaxf(m, st[kt][r]);
-                    }
-                }
-                m = col_max(m);
-                f32x2 den2 = {0.0f, 0.0f};
-                const f32x2 nm = {-m, -m};
+                for (int r = 0; r < 4; ++r) o[r] *= scale;
+                const s16x4 ob = to_s16x4(o);
 #pragma unroll
-                for (int kt = 0; kt < TT; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
-                        const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
-                        const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
-                        st[kt][r] = e.x;
-                        st[kt][r + 1] = e.y;
-                        den2 += e;
-                    }
-                den = col_sum(den2.x + den2.y);
+                for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
             }
-            // normalise after the product: O^T = (V^T . E^T) / den, one scale per output element
-            const float gq = GATE4 ? reinterpret_cast<const float *>(&s_gate[qt * 64 + lane])[h] : s_gate1[qt * 64 + h * 16 + l15];
-            const float scale = __builtin_amdgcn_rcpf(den) * gq;
-            f32x4 o = zero;                                  // O^T rows = d, column = query
+        } else {
+            // E^T = exp2(S^T - max) of query tile qt against every key, as the bf16 B operands of the next product (S^T tile
+            // rows = keys, column = query lane&15); returns this lane's share of the column's softmax denominator
+            auto scores = [&](int qt, s16x4 (&pb)[TT]) {
+                f32x4 st[TT];
+                f32x2 den2 = {0.0f, 0.0f};
+                if (bounded) {
+                    // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
+                    // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
 #pragma unroll
-            for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], to_s16x4(st[kt]), o);
+                    for (int kt = 0; kt < TT; ++kt) {
+                        st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] *= scale;
-            const s16x4 ob = to_s16x4(o);
+                        for (int r = 0; r < 4; r += 2) {
+                            const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
+                            st[kt][r] = e.x;
+                            st[kt][r + 1] = e.y;
+                            den2 += e;
+                        }
+                    }
+                } else {
+                    float m = -INFINITY;
 #pragma unroll
-            for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
+                    for (int kt = 0; kt < TT; ++kt) {
+                        st[kt] = MFMA16(kb[kt], qb[qt], zero);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
+                            m = fmaxf(m, st[kt][r]);
+                        }
+                    }
+                    m = col_max(m);
+                    const f32x2 nm = {-m, -m};
+#pragma unroll
+                    for (int kt = 0; kt < TT; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; r += 2) {
+                            const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
+                            const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
+                            st[kt][r] = e.x;
+                            st[kt][r + 1] = e.y;
+                            den2 += e;
+                        }
+                }
+#pragma unroll
+                for (int kt = 0; kt < TT; ++kt) pb[kt] = to_s16x4(st[kt]);
+                return den2.x + den2.y;
+            };
+            // O^T = (V^T . E^T) / den, gated, and its contribution to the output projection.  den: the column's sum of
+            // scores()' shares; the bounded form counted the six padding keys into it.
+            auto attend = [&](int qt, const s16x4 (&pb)[TT], float den) {
+                if (bounded) den -= static_cast<float>(TT * 16 - CELLS);
+                // normalise after the product: one scale per output element
+                const float scale = __builtin_amdgcn_rcpf(den) * s_gate1[qt * 64 + h * 16 + l15];
+                f32x4 o = zero;                                  // O^T rows = d, column = query
+#pragma unroll
+                for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], pb[kt], o);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] *= scale;
+                const s16x4 ob = to_s16x4(o);
+#pragma unroll
+                for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
+            };
+            // the three query tiles' denominators are independent: tiles 0 and 1 share one set of swaps, and the
+            // tiles' exp2 / add chains stand next to each other for the scheduler to interleave
+            static_assert(TT == 3, "denominators paired as (0, 1), 2");
+            s16x4 pb[TT][TT];
+            float den[TT];
+#pragma unroll
+            for (int qt = 0; qt < TT; ++qt) den[qt] = scores(qt, pb[qt]);
+            col_sum2(den[0], den[1]);
+            den[2] = col_sum(den[2]);
+#pragma unroll
+            for (int qt = 0; qt < TT; ++qt) attend(qt, pb[qt], den[qt]);
         }
     }
 }

@@ -19,8 +19,9 @@
 // fragments are read from the weights (L2) in that one pass; their 18 KB of LDS hold the mean slots instead.
 //
 // LEGACY = true is the earlier form (value head once per pair, in columns 7 and 15 next to the policy columns; gates
-// as attn::attn_sample's GATE4), launched when az_nn_debug bit 8 is set: same bytes, for A/B runs and as the tests'
-// oracle.
+// as attn::attn_sample's GATE4; rsqrtf() and one column reduction per value where the default form takes a bare
+// v_rsq_f32 and reduces in pairs), launched when az_nn_debug bit 8 is set or eps < FLT_MIN: same bytes, for A/B runs and
+// as the tests' oracle.
 //
 // Rounding points are those of k_attn_block followed by k_heads: results differ from the two launches only
 // through f32 summation order (token mean, RMS statistics) - the two token passes are the only code not shared.
@@ -28,6 +29,8 @@
 // Shape: one 12-wavefront workgroup per CU (three per SIMD, the attention kernel's occupancy): one copy of
 // the attention weights (35 KB) and of the policy's (10 KB), and 9.4 KB per wavefront (normalised tokens, which double
 // as the attention's gate store, the B operand, scores and the 16 mean slots): 158 KB of LDS.
+#include <cfloat>
+
 #include "az_nn.h"
 #include "nn_attn_core.h"
 #include "nn_heads_core.h"
@@ -108,8 +111,13 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
     }
     for (int i = lane; i < 16 * VS; i += 64) s_vec[i] = 0;
     __syncthreads();
+    // 1 / sqrt of an RMS statistic: the default form is launched with eps >= FLT_MIN only (rsq_normal()'s precondition)
+    auto rsq = [](float v) {
+        if constexpr (LEGACY) return rsqrtf(v);
+        else return rsq_normal(v);
+    };
     auto cvec4 = [&](int which, int ot) { return *reinterpret_cast<const f32x4 *>(&s_c[which][16 * ot + 4 * l4]); };
-    const bool bounded = attn::scores_bounded(s_qk, l4);
+    const bool bounded = LEGACY ? attn::scores_bounded(s_qk, l4) : attn::scores_bounded_paired(s_qk, l4);
 
     // a wavefront's samples: b0, b0 + S, b0 + 2S, ... (S = wavefronts in the grid), taken two at a time.  nslot of them
     // wait for their value tail, in slots 0 .. nslot - 1: samples fbase, fbase + S, ...
@@ -187,8 +195,14 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                             if (live) msum[ot][j] += f[ot][j];
                         }
                     }
-                    const float ss = col_sum(ss2.x + ss2.y), sc = col_sum(sc2.x + sc2.y);
-                    const float r = rsqrtf(ss * (1.0f / C) + eps);
+                    float ss, sc;
+                    if constexpr (LEGACY) {
+                        ss = col_sum(ss2.x + ss2.y), sc = col_sum(sc2.x + sc2.y);
+                    } else {
+                        ss = ss2.x + ss2.y, sc = sc2.x + sc2.y;
+                        col_sum2(ss, sc);
+                    }
+                    const float r = rsq(ss * (1.0f / C) + eps);
                     if (live) {
 #pragma unroll
                         for (int ot = 0; ot < 4; ++ot) {
@@ -236,7 +250,7 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                         V4 o;
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            const f32x2 m = f32x2{sum16(msum[ot][j].x), sum16(msum[ot][j].y)} * f32x2{1.0f / CELLS, 1.0f / CELLS};
+                            const f32x2 m = f32x2{sum16_dpp(msum[ot][j].x), sum16_dpp(msum[ot][j].y)} * f32x2{1.0f / CELLS, 1.0f / CELLS};
                             o.w[j] = pack2(m.x, m.y);
                         }
                         if (l15 == 0) *reinterpret_cast<V4 *>(&s_slot[(nslot + hs) * C + 16 * ot + 4 * l4]) = o;
@@ -293,7 +307,7 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                         q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
                     }
                 }
-                const float rn = rsqrtf(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
+                const float rn = rsq_normal(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
 #pragma unroll
                 for (int ot = 0; ot < 4; ++ot) {
                     const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
@@ -306,7 +320,7 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                 }
                 wave_lds_sync();
                 auto mean2 = [&](int m, int hh) { return g0[m][hh]; };
-                value_tail<VS>(AFragGlobal{w, l15, l4}, s_c, s_vec, mean2, w, wdl, moves_left, col_live, b, real, eps, l15, l4);
+                value_tail<VS, true>(AFragGlobal{w, l15, l4}, s_c, s_vec, mean2, w, wdl, moves_left, col_live, b, real, eps, l15, l4);
                 fbase += nslot * S;
                 nslot = 0;
             }
@@ -328,7 +342,8 @@ extern "C" int az_nn_attn_heads(const void *x, const void *prenorm_w, const void
     if (cus == 0) return 2;
     // az_nn_debug: bit 8 the earlier form, bits 16-27 a cap on the grid (tests: many samples per wavefront)
     const int dbg = az_nn_debug_flags(), cap = (dbg >> 16) & 0xfff;
-    const auto kern = (dbg & AZ_NN_DEBUG_LEGACY_TAIL) ? k_attn_heads<true> : k_attn_heads<false>;
+    // the default form takes its reciprocal square roots bare (rsq_normal): a smaller eps goes to the form that guards them
+    const auto kern = ((dbg & AZ_NN_DEBUG_LEGACY_TAIL) || !(eps >= FLT_MIN)) ? k_attn_heads<true> : k_attn_heads<false>;
     if (cap > 0 && cap < cus) cus = cap;
     // one workgroup per CU, each wavefront on every S-th sample (S = wavefronts in the grid)
     const int64_t want = (batch + WPB - 1) / WPB;

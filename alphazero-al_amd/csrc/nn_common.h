@@ -59,6 +59,11 @@ __device__ __forceinline__ f32x2 silu2(f32x2 x)
     return x * f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
 }
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504f * x); }
+// One v_rsq_f32.  PRECONDITION: x >= FLT_MIN (or NaN).  rsqrtf() wraps the instruction in a guard for the denormal range
+// (scale by 2^24 below FLT_MIN, select, rescale: five more instructions); at and above FLT_MIN the guard picks the
+// unscaled operand, so this returns rsqrtf()'s bits.  For the RMS statistics sum / n + eps that means eps >= FLT_MIN:
+// the host entry points launch the rsqrtf() forms of their kernels for a smaller eps.
+__device__ __forceinline__ float rsq_normal(float x) { return __builtin_amdgcn_rsqf(x); }
 
 // ---- reductions inside a wavefront.  Along a 16-lane row: DPP, the lane movement is an operand modifier of the add
 // (no LDS crossbar, no address arithmetic).
@@ -75,6 +80,21 @@ __device__ __forceinline__ float sum8(float v)      // over the 8 lanes that sha
     return v;
 }
 __device__ __forceinline__ float sum16(float v) { v = sum8(v); return v + dpp_mov<0x140>(v); }   // + row_mirror: the 16-lane row
+// sum16() with every step kept a scalar add, so that the lane movement folds into it (v_add_f32_dpp).  A caller that
+// builds a float pair from two sum16() results has its adds vectorised into v_pk_add_f32, which takes no DPP operand
+// and so needs a v_mov_b32_dpp per step next to it; the empty statement hides each sum from the vectoriser and emits
+// nothing.  The same additions in the same order as sum16().
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    v += dpp_mov<CTRL>(v);
+    asm("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ float sum16_dpp(float v)
+{
+    return dpp_add<0x140>(dpp_add<0x141>(dpp_add<0x4E>(dpp_add<0xB1>(v))));
+}
 __device__ __forceinline__ float max8(float v)
 {
     v = fmaxf(v, dpp_mov<0xB1>(v));
@@ -108,6 +128,25 @@ __device__ __forceinline__ float col_max(float v)
     r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return fmaxf(__uint_as_float(r.x), __uint_as_float(r.y));
 }
+// Two independent values through ONE set of swaps: a = col_sum(a), b = col_sum(b), bit for bit (the same additions in
+// the same grouping, (v0 + v1) + (v2 + v3) over the rows).  With rows written [r0, r1, r2, r3]:
+//   permlane16_swap(a, b), add  -> [a0+a1, b0+b1, a2+a3, b2+b3]
+//   permlane32_swap(t, t), add  -> [A, B, A, B]
+//   permlane16_swap(u, u)       -> A in every row of one register, B in every row of the other
+// 3 swaps, 2 adds and 2 copies where two col_sum() calls take 4, 4 and 4.
+template <class Op>
+__device__ __forceinline__ void col_reduce2(float &a, float &b, Op op)
+{
+    u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    const float t = op(__uint_as_float(r.x), __uint_as_float(r.y));
+    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
+    const float u = op(__uint_as_float(r.x), __uint_as_float(r.y));
+    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(u), false, false);
+    a = __uint_as_float(r.x);
+    b = __uint_as_float(r.y);
+}
+__device__ __forceinline__ void col_sum2(float &a, float &b) { col_reduce2(a, b, [](float x, float y) { return x + y; }); }
+__device__ __forceinline__ void col_max2(float &a, float &b) { col_reduce2(a, b, [](float x, float y) { return fmaxf(x, y); }); }
 // LDS traffic between lanes of ONE wavefront: the LDS executes a wavefront's instructions in order, so only the
 // compiler has to be stopped from moving accesses across this point.
 __device__ __forceinline__ void wave_lds_sync()

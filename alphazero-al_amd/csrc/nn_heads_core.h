@@ -186,8 +186,9 @@ __device__ __forceinline__ void policy_tail(const V8 *s_a, const float (*s_c)[C]
 // The value / moves-left head of the live columns of the B operand (row l15 of s_vec = pool_norm(mean) of the sample
 // of column l15).  Per lane: col_live - its column holds a sample; b, real - that sample's output row and whether it is
 // written; mean2(m, hh) - the sample's token mean, channels 16 m + 4 l4 + 2 hh, + 1.  afrag: AFragLds or AFragGlobal.
-// After a wave_lds_sync(); ends with one.
-template <int VS, class AFrag, class Mean>
+// After a wave_lds_sync(); ends with one.  BARE_RSQ: the two reciprocal square roots as rsq_normal(), for a caller
+// launched with eps >= FLT_MIN only.
+template <int VS, bool BARE_RSQ = false, class AFrag, class Mean>
 __device__ __forceinline__ void value_tail(const AFrag &afrag, const float (*s_c)[C], uint16_t *s_vec, const Mean &mean2,
                                            const az_nn_heads_weights &w, float *wdl, float *moves_left, bool col_live,
                                            int64_t b, bool real, float eps, int l15, int l4)
@@ -204,6 +205,10 @@ __device__ __forceinline__ void value_tail(const AFrag &afrag, const float (*s_c
                 p[1] = pack2(v[m][1].x, v[m][1].y);
             }
         }
+    };
+    auto rsq = [](float v) {
+        if constexpr (BARE_RSQ) return rsq_normal(v);
+        else return rsqrtf(v);
     };
     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
     // stage 1: g = mean + silu(pool_fc(pool_norm(mean)) + b); n2 = norm(g)
@@ -222,7 +227,7 @@ __device__ __forceinline__ void value_tail(const AFrag &afrag, const float (*s_c
                 ss2 = __builtin_elementwise_fma(g[m][hh], g[m][hh], ss2);
             }
         }
-        const float rn = rsqrtf(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
+        const float rn = rsq(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -246,7 +251,7 @@ __device__ __forceinline__ void value_tail(const AFrag &afrag, const float (*s_c
                 ss2 = __builtin_elementwise_fma(g[m][hh], g[m][hh], ss2);
             }
         }
-        const float rn = rsqrtf(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
+        const float rn = rsq(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll

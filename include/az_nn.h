@@ -100,7 +100,11 @@ int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void
 /* The whole gated attention block as a single MFMA kernel (nn_attn.hip):
  *   y = x + o_proj(sigmoid(gate) * softmax(qnorm(Q) knorm(K)^T / 4) V),  [Q|K|V|gate] = qkvg(RMSNorm(x))
  * (Network.py:51-93).  x, y (batch, 42, 64); qkvg_w (196, 64) row-major [out][in] with rows
- * 0-63 Q, 64-127 K, 128-191 V, 192-195 gate; o_w (64, 64) [out][in]; 4 heads of 16. */
+ * 0-63 Q, 64-127 K, 128-191 V, 192-195 gate; o_w (64, 64) [out][in]; 4 heads of 16.
+ * eps is the RMSNorms' epsilon (1e-5 in the reference).  The default forms of this kernel and of az_nn_attn_heads take
+ * 1 / sqrt(mean square + eps) as one bare v_rsq_f32, which is exact only for arguments >= FLT_MIN; a call with
+ * eps < FLT_MIN (0 included; NaN too) is therefore launched as the form bit 8 of az_nn_debug selects, whose rsqrtf()
+ * carries the denormal-range guard.  Same output bytes either way. */
 int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w,
                      const void *k_norm_w, const void *o_w, void *y, int64_t batch, float eps, const int64_t *batch_dev,
                      void *stream);
@@ -121,6 +125,10 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
 int az_nn_debug(int flags);
 int az_nn_debug_flags(void);
 int az_nn_conv_profile(unsigned long long *out, int n);
+/* Self-test of the paired column reductions (nn_common.h col_sum2 / col_max2) on one wavefront: a, b = 64 floats each
+ * (lane l's two values), out = 8 x 64 floats: col_sum2's a and b, col_sum(a), col_sum(b), then the same four with max.
+ * Nothing on the evaluator's path calls it. */
+int az_nn_debug_col_reduce2(const float *a, const float *b, float *out, void *stream);
 /* nn.RMSNorm over the last dimension of 64 */
 int az_nn_rmsnorm64(const void *x, const void *w, void *y, int64_t rows, float eps, void *stream);
 /* qkvg (batch*42, row_len) with row_len 196 or 200 (3*64 q|k|v, 4 gate logits, optional zero
@@ -156,7 +164,8 @@ int az_nn_heads(const void *tokens, const az_nn_heads_weights *w, const uint8_t 
 /* az_nn_attn_block followed by az_nn_heads as ONE kernel (nn_attn_heads.hip): the residual stream x (batch, 42, 64)
  * and the weights of both, as those two take them, in; probs, wdl, moves_left out, with mask / scatter / batch_dev as
  * az_nn_heads reads them.  The block's output stays on chip (no token tensor is written); the rounding points are
- * those of the two kernels, so results differ from them only through f32 summation order. */
+ * those of the two kernels, so results differ from them only through f32 summation order.  eps: as for
+ * az_nn_attn_block (below FLT_MIN the guarded form is launched). */
 int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w, const void *k_norm_w,
                      const void *o_w, const az_nn_heads_weights *w, const uint8_t *mask, float *probs, float *wdl,
                      float *moves_left, int64_t batch, float eps, const int32_t *scatter, const int64_t *batch_dev,

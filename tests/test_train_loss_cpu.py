@@ -1,0 +1,252 @@
+"""The training losses, the parts that need no GPU: the float64 restatement (tests/train_loss_ref.py) and the plain
+torch route of `training_loss` against what the reference's own loss code returned (fixture G18,
+tests/golden/make_golden_loss.py); `macro_f1` against sklearn's recorded values; argument checks; the ctypes mirror
+of az_train_loss_config against the header; `train_step` against a hand-written loop.
+
+Tolerances (G18 is float32, as the reference computes it): losses within 1e-6 relative, every gradient tensor
+within 1e-6 x its largest magnitude - five times what float32 summation order alone was measured to move them
+(1.2e-7 and 2.0e-7 over the eight cases).  The float32 torch route is held to the same bound against G18.
+
+The reference itself is never imported here: the golden file stands for it."""
+import ctypes as C
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+import train_loss_ref as R
+from test_oracle_golden import load
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "alphazero-al_amd")
+CASES = [(key, name) for key in ("c4", "ot") for name in sorted(R.CONFIGS)]
+TD_ROWS = {("a", "c4"): 0, ("a", "ot"): 0, ("b", "c4"): 70, ("b", "ot"): 160, ("c", "c4"): 90, ("c", "ot"): 168,
+           ("d", "c4"): 0, ("d", "ot"): 64}
+
+
+@pytest.fixture(scope="module")
+def TL():
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    ge.build()
+    if PKG not in sys.path:
+        sys.path.insert(0, PKG)
+    from src import train_loss
+    return train_loss
+
+
+def golden_batch(key):
+    g = load("g16_training_batch")
+    return tuple(g[f"{key}_{t}"] for t in R.TENSORS)
+
+
+def golden_heads(key):
+    g = load("g18_training_loss")
+    return g[f"{key}_log_p"], g[f"{key}_value"], g[f"{key}_steps"]
+
+
+def rel_dev(got, want):
+    """Largest absolute difference over the largest magnitude of `want` (0 / 0 counts as 0)."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    top = np.abs(want).max()
+    gap = np.abs(got - want).max()
+    return 0.0 if gap == 0 else gap / top
+
+
+def check_against_g18(key, name, losses, entropy, grads, tol=1e-6):
+    g = load("g18_training_loss")
+    k = f"{key}_{name}_"
+    for i, what in enumerate(("policy", "value", "aux")):
+        assert abs(losses[i] - g[k + "losses"][i]) <= tol * abs(g[k + "losses"][i]), (what, losses[i], g[k + "losses"][i])
+    assert abs(entropy - g[k + "entropy"][0]) <= tol * abs(g[k + "entropy"][0])
+    for what, got in zip(("d_log_p", "d_value", "d_steps"), grads):
+        assert got.shape == g[k + what].shape
+        assert rel_dev(got, g[k + what]) <= tol, (what, rel_dev(got, g[k + what]))
+
+
+def test_fixture_heads_are_the_seeded_ones_and_have_no_argmax_ties():
+    for key in ("c4", "ot"):
+        batch, heads = golden_batch(key), golden_heads(key)
+        again = R.seeded_heads(key, batch, 18)
+        assert all(np.array_equal(a, b) and a.dtype == np.float32 for a, b in zip(heads, again))
+        top = np.sort(heads[1], 1)
+        assert (top[:, 2] > top[:, 1]).all()
+        assert (heads[0][~batch[6]] < -1e8).all() and np.isfinite(heads[0]).all()
+
+
+@pytest.mark.parametrize("key,name", CASES)
+def test_float64_restatement_equals_the_reference(key, name):
+    g = load("g18_training_loss")
+    r = R.reference(*golden_heads(key), golden_batch(key), R.OFFSET[key], R.CONFIGS[name])
+    check_against_g18(key, name, (r["policy"], r["value"], r["aux"]), r["entropy"], (r["d_log_p"], r["d_value"], r["d_steps"]))
+    assert r["td_rows"] == int(g[f"{key}_{name}_td_rows"][0]) == TD_ROWS[(name, key)]
+    assert np.array_equal(r["value_class"], g[f"{key}_value_class"])
+    assert np.array_equal(r["turn_sign"], g[f"{key}_turn_sign"])
+    assert np.array_equal(r["policy_mask"], g[f"{key}_policy_mask"])
+    assert r["confusion"].sum() == len(r["value_class"]) and r["policy_rows"] == int(g[f"{key}_policy_mask"].sum())
+    assert abs(R.macro_f1(r["confusion"]) - g[f"{key}_{name}_f1"][0]) < 1e-12
+
+
+@pytest.mark.parametrize("key,name", CASES)
+def test_torch_route_equals_the_reference_through_backward(TL, key, name):
+    import torch
+    g = load("g18_training_loss")
+    heads = [torch.from_numpy(x.copy()).requires_grad_(True) for x in golden_heads(key)]
+    heads[2] = heads[2].detach().reshape(-1, 1).requires_grad_(True)            # steps as [N, 1]
+    batch = tuple(torch.from_numpy(x) for x in golden_batch(key))
+    out = TL.training_loss(*heads, batch, R.OFFSET[key], TL.LossConfig(**R.CONFIGS[name]))
+    assert out.policy.dim() == out.value.dim() == out.aux.dim() == 0
+    out.total.backward()
+    grads = [h.grad.numpy() for h in heads]
+    assert grads[2].shape == (len(batch[0]), 1)
+    grads[2] = grads[2].reshape(-1)
+    check_against_g18(key, name, (out.policy.item(), out.value.item(), out.aux.item()), out.entropy.item(), grads)
+    r = R.reference(*golden_heads(key), golden_batch(key), R.OFFSET[key], R.CONFIGS[name])
+    assert np.array_equal(out.confusion.numpy(), r["confusion"]) and out.confusion.dtype == torch.int32
+    assert int(out.policy_rows) == r["policy_rows"] and int(out.td_rows) == TD_ROWS[(name, key)]
+    assert not (out.entropy.requires_grad or out.confusion.requires_grad)
+    assert abs(TL.macro_f1(out.confusion) - g[f"{key}_{name}_f1"][0]) < 1e-12
+
+
+def test_config_d_on_connect4_leaves_the_value_loss_unscaled(TL):
+    """No TD row: the reference's `None` branch, td_alpha = 1 must not wipe the value loss out."""
+    import torch
+    heads = [torch.from_numpy(x.copy()) for x in golden_heads("c4")]
+    batch = tuple(torch.from_numpy(x) for x in golden_batch("c4"))
+    with_td = TL.training_loss(*heads, batch, 42, TL.LossConfig(**R.CONFIGS["d"]))
+    without = TL.training_loss(*heads, batch, 42, TL.LossConfig(**dict(R.CONFIGS["d"], td_alpha=0.0)))
+    assert int(with_td.td_rows) == 0 and with_td.value.item() == without.value.item() > 1.0
+
+
+def test_macro_f1_equals_sklearn(TL):
+    g = load("g18_training_loss")
+    assert len(g["f1_cases"]) >= 5 and any(c[2].sum() == 0 and c[:, 2].sum() == 0 for c in g["f1_cases"])
+    for conf, want in zip(g["f1_cases"], g["f1_scores"]):
+        assert abs(TL.macro_f1(conf) - want) < 1e-12, conf
+        assert abs(R.macro_f1(conf) - want) < 1e-12, conf
+    import torch
+    assert abs(TL.macro_f1(torch.from_numpy(g["f1_cases"][0]).to(torch.int32).reshape(-1)) - g["f1_scores"][0]) < 1e-12
+
+
+@pytest.mark.parametrize("bad", [dict(value_decay=0.0), dict(value_decay=1.01), dict(distill_alpha=-0.1), dict(distill_alpha=1.5),
+                                 dict(td_alpha=-0.1), dict(td_alpha=1.1), dict(distill_temp=0.0), dict(psw_beta=-1.0),
+                                 dict(entropy_lambda=-0.01), dict(td_steps=-1), dict(td_steps=2.5)])
+def test_loss_config_validates(TL, bad):
+    with pytest.raises(ValueError):
+        TL.LossConfig(**bad)
+
+
+def test_loss_config_defaults_are_the_train_step_defaults(TL):
+    c = TL.LossConfig()
+    assert (c.value_decay, c.distill_alpha, c.distill_temp, c.psw_beta, c.entropy_lambda, c.td_alpha, c.td_steps) == \
+        (1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 5)
+
+
+def test_arguments_are_checked_and_the_kernel_route_refuses_cpu_tensors(TL):
+    import torch
+    heads = [torch.from_numpy(x.copy()) for x in golden_heads("c4")]
+    batch = tuple(torch.from_numpy(x) for x in golden_batch("c4"))
+    with pytest.raises(ValueError, match="kernel"):
+        TL.training_loss(*heads, batch, 42, route="kernel")
+    with pytest.raises(ValueError):
+        TL.training_loss(*heads, batch, 42, route="triton")
+    with pytest.raises(ValueError):
+        TL.training_loss(*heads, batch, 0)
+    with pytest.raises(ValueError):
+        TL.training_loss(*heads, batch[:7], 42)
+    with pytest.raises(ValueError):
+        TL.training_loss(heads[0], heads[1][:5], heads[2], batch, 42)
+    with pytest.raises(ValueError):
+        TL.training_loss(heads[0][:, :6], heads[1], heads[2], batch, 42)
+
+
+def test_config_struct_mirror_has_the_size_and_fields_the_header_asserts(TL):
+    hdr = open(os.path.join(ROOT, "include", "az_train.h")).read()
+    assert '#include "az_mcts.h"' in hdr
+    m = re.search(r"#define\s+AZ_TRAIN_LOSS_CONFIG_BYTES\s+(\d+)", hdr)
+    assert m and "sizeof(az_train_loss_config) == AZ_TRAIN_LOSS_CONFIG_BYTES" in hdr
+    assert C.sizeof(TL.TrainLossConfigC) == int(m.group(1))
+    body = re.search(r"typedef struct az_train_loss_config \{(.*?)\} az_train_loss_config;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(double|int32_t)\s+(\w+);", body)
+    assert [f[1] for f in fields] == [f[0] for f in TL.TrainLossConfigC._fields_]
+    kinds = {"double": C.c_double, "int32_t": C.c_int32}
+    assert [kinds[f[0]] for f in fields] == [f[1] for f in TL.TrainLossConfigC._fields_]
+    for struct, mirror in (("az_train_heads", TL.TrainHeadsC), ("az_train_loss_out", TL.TrainLossOutC), ("az_train_grads", TL.TrainGradsC)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        assert re.findall(r"\*(\w+);", body) == [f[0] for f in mirror._fields_]
+        assert C.sizeof(mirror) == int(re.search(r"#define\s+%s_BYTES\s+(\d+)" % struct.upper(), hdr).group(1))
+    for name in ("az_train_dev_loss", "az_train_dev_loss_grad"):
+        assert re.search(r"\bint\s+%s\(" % name, hdr), name
+    assert re.search(r"\bint64_t\s+az_train_loss_workspace_bytes\(", hdr)
+    L = TL.train_lib()
+    assert L.az_train_loss_workspace_bytes(0, 128) > 0 and L.az_train_loss_workspace_bytes(1, 192) > 0
+    assert L.az_train_loss_workspace_bytes(2, 128) == -1 and L.az_train_loss_workspace_bytes(0, 0) == -1
+    assert L.az_train_loss_workspace_bytes(0, 2 ** 30 + 1) == -1 and L.az_train_loss_workspace_bytes(1, 2 ** 30) > 0
+
+
+def tiny_net(torch, seed=3):
+    """Three heads over a flattened Connect4 state, SGD as `opt`, a scheduler that halves the rate."""
+    class Tiny(torch.nn.Module):
+        aux_target_offset = 42
+
+        def __init__(self):
+            super().__init__()
+            gen = torch.Generator().manual_seed(seed)
+            self.body = torch.nn.Linear(126, 16)
+            self.policy, self.val, self.aux = torch.nn.Linear(16, 7), torch.nn.Linear(16, 3), torch.nn.Linear(16, 1)
+            with torch.no_grad():
+                for p in self.parameters():
+                    p.copy_(torch.randn(p.shape, generator=gen) * 0.3)
+            self.opt = torch.optim.SGD(self.parameters(), lr=0.05)
+            self.scheduler = torch.optim.lr_scheduler.StepLR(self.opt, 1, 0.5)
+
+        def forward(self, x, action_mask=None):
+            h = torch.tanh(self.body(x.reshape(x.shape[0], -1).to(self.body.weight.dtype)))
+            logits = self.policy(h)
+            if action_mask is not None:
+                logits = logits.masked_fill(~action_mask, -1e9)
+            return torch.log_softmax(logits, 1), torch.log_softmax(self.val(h), 1), torch.sigmoid(self.aux(h)).squeeze(-1)
+    return Tiny()
+
+
+def test_train_step_equals_a_hand_written_loop(TL):
+    import torch
+    batch = tuple(torch.from_numpy(x) for x in golden_batch("c4"))
+    loader = [tuple(t[:64] for t in batch), tuple(t[64:] for t in batch)]
+    knobs = dict(R.CONFIGS["b"])
+    net = tiny_net(torch)
+    calls = []
+
+    def augment(b):
+        calls.append(1)
+        return b
+    got = TL.train_step(net, loader, augment, n_epochs=2, **knobs)
+
+    twin = tiny_net(torch)
+    cfg = TL.LossConfig(**knobs)
+    sums, n = np.zeros(3), 0
+    for _ in range(2):
+        twin.train()
+        for b in loader:
+            twin.opt.zero_grad(set_to_none=True)
+            out = TL.training_loss(*twin(b[0], action_mask=b[6]), b, 42, cfg, route="torch")
+            (out.policy + out.value + out.aux).backward()
+            norm = torch.nn.utils.clip_grad_norm_(twin.parameters(), 5)
+            twin.opt.step()
+            sums += [out.policy.item(), out.value.item(), out.aux.item()]
+            n += 1
+    twin.eval()
+    twin.scheduler.step()
+    with torch.no_grad():
+        conf = TL.training_loss(*twin(b[0], action_mask=b[6]), b, 42, cfg, route="torch").confusion
+    want = (*(sums / n), out.entropy.item(), float(norm), TL.macro_f1(conf))
+    assert len(got) == 6 and all(isinstance(x, float) for x in got)
+    assert np.allclose(got, want, rtol=1e-6, atol=0), (got, want)
+    assert len(calls) == 4 and not net.training
+    assert net.opt.param_groups[0]["lr"] == twin.opt.param_groups[0]["lr"] == 0.025
+    for p, q in zip(net.parameters(), twin.parameters()):
+        assert torch.equal(p, q)

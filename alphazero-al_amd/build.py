@@ -56,7 +56,7 @@ def build_engine(force=False):
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(LIB, "libaz_mcts.so")
-    names = ("kernels", "select_kernels", "backup_kernels", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_conv2", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "nn_othello", "nn_othello_heads", "nn_selftest")
+    names = ("kernels", "select_kernels", "backup_kernels", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "nn_othello", "nn_othello_heads", "nn_selftest")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = _headers()
     jobs = []
@@ -68,7 +68,10 @@ def build_engine(force=False):
                          *PER_FILE_FLAGS.get(n, ()),
                          "-I", INC, "-I", CSRC, "-c", src, "-o", obj])
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
+        # at most MAX_JOBS compilers at once when the environment sets it, else at most 16: a shared host shows far more
+        # CPUs than one command may use
+        limit = int(os.environ["MAX_JOBS"]) if os.environ.get("MAX_JOBS", "").isdigit() else 16
+        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), limit, os.cpu_count() or 4))) as pool:
             list(pool.map(_run, jobs))
     objs = [os.path.join(objdir, n + ".o") for n in names]
     if force or jobs or _stale(out, objs):

@@ -3,8 +3,7 @@
 //
 // Everything here is __device__ __forceinline__ in an anonymous namespace (or a host-side inline): a translation unit
 // that includes it gets its own copy, no device code crosses translation units.  A helper belongs here only if every
-// user means the same instructions by it; variants (nn_kernels.hip's pack_bf16, a silu on __expf, nn_othello.hip's
-// round_bf) stay in their files under their own names.
+// user means the same instructions by it; variants (nn_kernels.hip's pack_bf16, nn_othello.hip's round_bf) stay in their files under their own names.
 #pragma once
 
 #include <hip/hip_bf16.h>

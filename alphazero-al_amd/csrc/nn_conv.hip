@@ -129,6 +129,33 @@ __global__ void __launch_bounds__(256, 2) k_stem_conv_block(StemIn st, const uin
 // and the launch-time choices of nn_attn.hip / nn_attn_heads.hip (az_nn_debug_flags)
 int g_dbg = [] { const char *e = getenv("AZ_VALUE_TAIL_DEFERRED"); return e != nullptr && strcmp(e, "0") == 0 ? AZ_NN_DEBUG_LEGACY_TAIL : 0; }();
 
+// What a launch of either kernel does once its pointer and its dynamic LDS bytes are known: the once-per-device set-up
+// (with AZ_NN_VERBOSE: the occupancy line; c_in 0 words it for k_stem_conv_block), then the grid - one workgroup per
+// tile of TS samples, at most AZ_NN_CONV_GRID - and the kernel's dbg word.  `setup` is the caller's: one static
+// DeviceSetup per kernel instantiation (nn_common.h).  The environment is read once per process.  Returns 0, or 2 when
+// the device refused the set-up.
+int prepare(DeviceSetup &setup, const void *kern, size_t smem, int c_in, int64_t B, unsigned &grid, int &dbg)
+{
+    if (setup.cus({kern}, static_cast<int>(smem), [&] {
+            if (getenv("AZ_NN_VERBOSE") != nullptr) {
+                int per_cu = 0;
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, smem);
+                if (c_in != 0)
+                    fprintf(stderr, "[az_nn] conv block C_in=%d: %zu B LDS, %d workgroups per CU\n", c_in, smem, per_cu);
+                else
+                    fprintf(stderr, "[az_nn] stem + conv block: %zu B LDS, %d workgroups per CU\n", smem, per_cu);
+            }
+        }) == 0)
+        return 2;
+    // issue priority of the matrix phase over the other workgroup's load / store phases (s_setprio 0..3; AZ_NN_CONV_PRIO)
+    static const int prio = [] { const char *e = getenv("AZ_NN_CONV_PRIO"); const int v = e ? atoi(e) : 1; return v < 0 || v > 3 ? 1 : v; }();
+    const int64_t ntiles = (B + TS - 1) / TS;
+    static const int64_t max_grid = getenv("AZ_NN_CONV_GRID") ? atoll(getenv("AZ_NN_CONV_GRID")) : 512;   // two workgroups per CU
+    grid = static_cast<unsigned>(ntiles < max_grid ? ntiles : max_grid);
+    dbg = (g_dbg & 255) | (((g_dbg >> 5) & 3) ? 0 : (prio << 5));
+    return 0;
+}
+
 template <int CIN, bool NORM, bool RESID, bool EMBED = false>
 int launch(const void *x, const void *w, const void *bias, const void *gamma, const void *beta, void *y, int64_t B,
            float eps, const int64_t *batch_dev, hipStream_t s, EmbedIn em = EmbedIn{})
@@ -137,23 +164,13 @@ int launch(const void *x, const void *w, const void *bias, const void *gamma, co
                             (RESID ? 0 : static_cast<size_t>(TS) * CELLS * COUT * 2) + 2 * CIN * sizeof(float) + 512;
     auto kern = k_conv_block<CIN, NORM, RESID, EMBED>;
     static DeviceSetup setup;
-    if (setup.cus({reinterpret_cast<const void *>(kern)}, static_cast<int>(smem), [&] {
-            if (getenv("AZ_NN_VERBOSE") != nullptr) {
-                int per_cu = 0;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, smem);
-                fprintf(stderr, "[az_nn] conv block C_in=%d: %zu B LDS, %d workgroups per CU\n", CIN, smem, per_cu);
-            }
-        }) == 0)
-        return 2;
-    // issue priority of the matrix phase over the other workgroup's load / store phases (s_setprio 0..3; AZ_NN_CONV_PRIO)
-    static const int prio = [] { const char *e = getenv("AZ_NN_CONV_PRIO"); const int v = e ? atoi(e) : 1; return v < 0 || v > 3 ? 1 : v; }();
-    const int64_t ntiles = (B + TS - 1) / TS;
-    static const int64_t max_grid = getenv("AZ_NN_CONV_GRID") ? atoll(getenv("AZ_NN_CONV_GRID")) : 512;   // two workgroups per CU
-    const unsigned grid = static_cast<unsigned>(ntiles < max_grid ? ntiles : max_grid);
+    unsigned grid;
+    int dbg;
+    if (prepare(setup, reinterpret_cast<const void *>(kern), smem, CIN, B, grid, dbg) != 0) return 2;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, static_cast<const uint16_t *>(x),
                        static_cast<const uint16_t *>(w), static_cast<const uint16_t *>(bias),
                        static_cast<const uint16_t *>(gamma), static_cast<const uint16_t *>(beta),
-                       static_cast<uint16_t *>(y), B, eps, (g_dbg & 255) | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev, em);
+                       static_cast<uint16_t *>(y), B, eps, dbg, batch_dev, em);
     return 0;
 }
 
@@ -164,24 +181,13 @@ int launch_stem(const StemIn &st, const void *w, const void *bias, const void *g
     constexpr size_t smem = static_cast<size_t>(TS) * PCELLS * CELLB + static_cast<size_t>(TS) * CELLS * 64 * 2 +
                             2 * 64 * sizeof(float) + 512 + PMAPB + FRAGB;
     static_assert(2 * smem <= 160 * 1024, "two workgroups per CU");
-    auto kern = k_stem_conv_block;
     static DeviceSetup setup;
-    if (setup.cus({reinterpret_cast<const void *>(kern)}, static_cast<int>(smem), [&] {
-            if (getenv("AZ_NN_VERBOSE") != nullptr) {
-                int per_cu = 0;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, smem);
-                fprintf(stderr, "[az_nn] stem + conv block: %zu B LDS, %d workgroups per CU\n", smem, per_cu);
-            }
-        }) == 0)
-        return 2;
-    static const int prio = [] { const char *e = getenv("AZ_NN_CONV_PRIO"); const int v = e ? atoi(e) : 1; return v < 0 || v > 3 ? 1 : v; }();
-    const int64_t ntiles = (B + TS - 1) / TS;
-    static const int64_t max_grid = getenv("AZ_NN_CONV_GRID") ? atoll(getenv("AZ_NN_CONV_GRID")) : 512;   // two workgroups per CU
-    const unsigned grid = static_cast<unsigned>(ntiles < max_grid ? ntiles : max_grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, st, static_cast<const uint16_t *>(w),
+    unsigned grid;
+    int dbg;
+    if (prepare(setup, reinterpret_cast<const void *>(k_stem_conv_block), smem, 0, B, grid, dbg) != 0) return 2;
+    hipLaunchKernelGGL(k_stem_conv_block, dim3(grid), dim3(256), smem, s, st, static_cast<const uint16_t *>(w),
                        static_cast<const uint16_t *>(bias), static_cast<const uint16_t *>(gamma),
-                       static_cast<const uint16_t *>(beta), static_cast<uint16_t *>(y), B, eps,
-                       (g_dbg & 255) | (((g_dbg >> 5) & 3) ? 0 : (prio << 5)), batch_dev);
+                       static_cast<const uint16_t *>(beta), static_cast<uint16_t *>(y), B, eps, dbg, batch_dev);
     return 0;
 }
 

@@ -79,7 +79,6 @@ __global__ void __launch_bounds__(256) k_hash_eval(const float *features, const 
     const float own = in ? f[lane] : 0.0f, opp = in ? f[CELLS + lane] : 0.0f;
     const bool p1 = f[2 * CELLS] > 0.0f;
     // display cell -> bit of the reference's bitboards (Connect4.h:15-29: col*7 + 5-row; Othello.h:18-23: row*8+col)
-    const int bit = OTHELLO ? lane : ((lane % 7) * 7 + (5 - lane / 7));
     const bool is_p1 = in && ((p1 && own != 0.0f) || (!p1 && opp != 0.0f));
     const bool is_p2 = in && ((p1 && opp != 0.0f) || (!p1 && own != 0.0f));
     uint64_t bb0 = 0, bb1 = 0;
@@ -93,7 +92,6 @@ __global__ void __launch_bounds__(256) k_hash_eval(const float *features, const 
             bb0 |= ((m1 >> c) & 1ull) << bt;
             bb1 |= ((m2 >> c) & 1ull) << bt;
         }
-        (void)bit;
     }
     const uint64_t h = position_hash(bb0 ^ salt, bb1, p1);
     const uint8_t *mk = mask != nullptr ? mask + row * A : nullptr;
@@ -165,7 +163,159 @@ __global__ void __launch_bounds__(256) k_hash_eval_positions(az_nn_positions pos
     const float v = static_cast<float>((h >> 43) & 63);
     ml[row] = OTHELLO ? (v / 32.0f - 1.0f) : (v / 2.0f);
 }
+
+// ---- one forward call per kind of model.  forward() below has checked m, the three outputs, batch > 0 and that rows
+// and n_rows come together; exactly one of features / positions is given.
+
+// Othello/Network.py:213-227 on the kernels of nn_othello.hip / nn_othello_heads.hip; needs positions + masks
+int forward_othello(const az_nn_model *m, const az_nn_positions *positions, const uint8_t *mask, float *probs, float *wdl,
+                    float *moves_left, int64_t batch, const int32_t *rows, const int64_t *n_rows, void *scratch,
+                    uint64_t scratch_bytes, void *stream)
+{
+    if (positions == nullptr || mask == nullptr) return 1;
+    if (scratch == nullptr || scratch_bytes < az_nn_model_scratch_bytes(m, batch)) return 1;
+    const az_nn_othello_weights &o = m->ow;
+    char *base = static_cast<char *>(scratch);
+    char *tok = base; base += batch * kOtTok;
+    char *map[3];
+    for (auto &p : map) { p = base; base += batch * kOtMap10; }
+    char *pa = base; base += batch * kOtMap8;
+    char *pb = base; base += batch * kOtMap8;
+    char *neck = base;
+    auto conv = [&](int i, const void *x, const void *res, void *y) {
+        const az_nn_othello_conv_layer &l = o.conv[i];
+        return az_nn_othello_conv(x, l.w_packed, l.pre_scale, l.pre_shift, l.post_scale, l.post_shift, l.residual ? res : nullptr,
+                                  y, batch, l.c_in, l.h_in, l.pad, 1, n_rows, stream);
+    };
+    int rc = az_nn_othello_embed(positions, mask, o.embed_table, tok, batch, rows, n_rows, stream);
+    int cur = 0;                                      // map[cur] holds the running hidden state
+    if (rc == 0) rc = conv(0, tok, nullptr, map[cur]);
+    for (int i = 1; rc == 0 && i + 1 < o.n_body; i += 2) {
+        const int y1 = (cur + 1) % 3, y2 = (cur + 2) % 3;
+        rc = conv(i, map[cur], nullptr, map[y1]);
+        if (rc == 0) rc = conv(i + 1, map[y1], map[cur], map[y2]);
+        cur = y2;
+    }
+    const int hid = (cur + 1) % 3;
+    if (rc == 0) rc = conv(o.n_body - 1, map[cur], nullptr, map[hid]);
+    if (rc == 0) rc = conv(o.n_body, map[hid], nullptr, pa);
+    if (rc == 0) rc = conv(o.n_body + 1, pa, nullptr, pb);
+    if (rc == 0) rc = az_nn_othello_conv_narrow(map[hid], o.dual_w16, o.dual_scale16, o.dual_shift16, neck, batch, n_rows, stream);
+    if (rc == 0) rc = az_nn_othello_heads(pb, neck, &o.heads, probs, wdl, moves_left, batch, rows, n_rows, stream);
+    return rc;
 }
+
+// AZ_NN_KIND_HASH_*: from the leaf positions, else from the feature planes; no scratch
+int forward_hash(const az_nn_model *m, const float *features, const az_nn_positions *positions, const uint8_t *mask,
+                 float *probs, float *wdl, float *moves_left, int64_t batch, const int32_t *rows, const int64_t *n_rows,
+                 void *stream)
+{
+    if (positions != nullptr) {
+        const dim3 grid(static_cast<unsigned>((batch + 255) / 256)), block(256);
+        if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
+            hipLaunchKernelGGL(k_hash_eval_positions<true>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
+                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
+        else
+            hipLaunchKernelGGL(k_hash_eval_positions<false>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
+                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
+        return 0;
+    }
+    const dim3 grid(static_cast<unsigned>((batch + 3) / 4)), block(256);
+    if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
+        hipLaunchKernelGGL(k_hash_eval<true>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
+                           moves_left, batch, rows, n_rows, m->hash_salt);
+    else
+        hipLaunchKernelGGL(k_hash_eval<false>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
+                           moves_left, batch, rows, n_rows, m->hash_salt);
+    return 0;
+}
+
+// the Connect4 network: stem and first residual block, the other blocks, attention and heads
+int forward_connect4(const az_nn_model *m, const float *features, const az_nn_positions *positions, const uint8_t *mask,
+                     float *probs, float *wdl, float *moves_left, int64_t batch, const int32_t *rows, const int64_t *n_rows,
+                     void *scratch, uint64_t scratch_bytes, void *stream)
+{
+    if (scratch == nullptr || scratch_bytes < az_nn_model_scratch_bytes(m, batch)) return 1;
+    const az_nn_model_weights &w = m->w;
+    char *a = static_cast<char *>(scratch);
+    char *b = a + batch * kTokenBytes;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // this call carries event pairs?  (never while the stream is capturing: no timestamps there)
+    bool timed = false;
+    int slot[kKinds] = {-1, -1, -1, -1};
+    if (g_prof.on) {
+        std::lock_guard<std::mutex> lk(g_prof.mu);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const bool capturing = hipStreamIsCapturing(hs, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+        if (g_prof.on && !capturing && (g_prof.seen++ % g_prof.stride) == 0) {
+            timed = true;
+            for (int kd = 0; kd < kKinds; ++kd)
+                if (g_prof.used[kd] < g_prof.start[kd].size()) slot[kd] = static_cast<int>(g_prof.used[kd]++);
+        }
+    }
+    auto begin = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.start[kd][slot[kd]], hs); };
+    auto end = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.stop[kd][slot[kd]], hs); };
+    int rc;
+    int first = 0;                                        // the first residual block still to run
+    // the folded stem from positions and the first residual block as one launch (a call that carries event pairs
+    // runs the two, so that the STEM and CONV rings keep timing the kernels they are named after)
+    if (m->stem_fused && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr && w.n_blocks >= 1) {
+        rc = az_nn_stem_conv_block_positions(positions, w.stem_frag, w.stem_pmap, w.block_w[0], w.block_b[0], w.block_gamma[0],
+                                             w.block_beta[0], a, batch, w.eps, rows, n_rows, stream);
+        first = 1;
+    } else {
+        begin(AZ_NN_PROFILE_STEM);
+        if (w.stem_frag != nullptr && w.stem_pmap != nullptr)
+            rc = positions != nullptr
+                ? az_nn_stem_folded_positions(positions, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream)
+                : az_nn_stem_folded(features, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream);
+        else
+            rc = positions != nullptr
+                ? az_nn_stem_embed_positions(positions, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream)
+                : az_nn_stem_embed(features, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream);
+        end(AZ_NN_PROFILE_STEM);
+    }
+    for (int i = first; rc == 0 && i < w.n_blocks; ++i) {
+        if (i == 0) begin(AZ_NN_PROFILE_CONV);
+        rc = az_nn_conv_block(a, 64, w.block_w[i], w.block_b[i], w.block_gamma[i], w.block_beta[i], 1, b, batch,
+                              w.eps, n_rows, stream);
+        if (i == 0) end(AZ_NN_PROFILE_CONV);
+        char *t = a; a = b; b = t;
+    }
+    // a call that carries event pairs runs the attention block and the heads as two launches, so that the ATTN and
+    // HEADS rings keep timing the kernels they are named after (the fused kernel has no split to time)
+    if (rc == 0 && m->attn_heads_fused && !timed)
+        return az_nn_attn_heads(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, &w.heads, mask, probs, wdl, moves_left, batch,
+                                w.eps, rows, n_rows, stream);
+    if (rc == 0) {
+        begin(AZ_NN_PROFILE_ATTN);
+        rc = az_nn_attn_block(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, b, batch, w.eps, n_rows, stream);
+        end(AZ_NN_PROFILE_ATTN);
+        char *t = a; a = b; b = t;
+    }
+    if (rc == 0) {
+        begin(AZ_NN_PROFILE_HEADS);
+        rc = az_nn_heads(a, &w.heads, mask, probs, wdl, moves_left, batch, w.eps, rows, n_rows, stream);
+        end(AZ_NN_PROFILE_HEADS);
+    }
+    return rc;
+}
+
+int forward(const az_nn_model *m, const float *features, const az_nn_positions *positions, const uint8_t *mask, float *probs,
+            float *wdl, float *moves_left, int64_t batch, const int32_t *rows, const int64_t *n_rows, void *scratch,
+            uint64_t scratch_bytes, void *stream)
+{
+    if (m == nullptr || probs == nullptr || wdl == nullptr || moves_left == nullptr) return 1;
+    if (batch <= 0) return batch == 0 ? 0 : 1;
+    if ((rows == nullptr) != (n_rows == nullptr)) return 1;
+    if (m->kind == AZ_NN_KIND_OTHELLO_CNN)
+        return forward_othello(m, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
+    if (m->kind != AZ_NN_KIND_CONNECT4_CNN)
+        return forward_hash(m, features, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, stream);
+    return forward_connect4(m, features, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -233,16 +383,12 @@ uint64_t az_nn_model_scratch_bytes(const az_nn_model *m, int64_t batch)
     return batch > 0 ? static_cast<uint64_t>(2 * batch * kTokenBytes) : 0;
 }
 
-static int forward_impl(const az_nn_model *m, const float *features, const az_nn_positions *positions, const uint8_t *mask,
-                        float *probs, float *wdl, float *moves_left, int64_t batch, const int32_t *rows,
-                        const int64_t *n_rows, void *scratch, uint64_t scratch_bytes, void *stream);
-
 int az_nn_model_forward(const az_nn_model *m, const float *features, const uint8_t *mask, float *probs,
                         float *wdl, float *moves_left, int64_t batch, const int32_t *rows,
                         const int64_t *n_rows, void *scratch, uint64_t scratch_bytes, void *stream)
 {
     if (features == nullptr) return 1;
-    return forward_impl(m, features, nullptr, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
+    return forward(m, features, nullptr, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
 }
 
 int az_nn_model_forward_positions(const az_nn_model *m, const az_nn_positions *positions, const uint8_t *mask, float *probs,
@@ -250,134 +396,7 @@ int az_nn_model_forward_positions(const az_nn_model *m, const az_nn_positions *p
                                   const int64_t *n_rows, void *scratch, uint64_t scratch_bytes, void *stream)
 {
     if (positions == nullptr || !positions->bb_p1 || !positions->bb_p2 || !positions->turn || !positions->sym) return 1;
-    return forward_impl(m, nullptr, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
-}
-
-static int forward_impl(const az_nn_model *m, const float *features, const az_nn_positions *positions, const uint8_t *mask,
-                        float *probs, float *wdl, float *moves_left, int64_t batch, const int32_t *rows,
-                        const int64_t *n_rows, void *scratch, uint64_t scratch_bytes, void *stream)
-{
-    if (m == nullptr || probs == nullptr || wdl == nullptr || moves_left == nullptr) return 1;
-    if (batch <= 0) return batch == 0 ? 0 : 1;
-    if ((rows == nullptr) != (n_rows == nullptr)) return 1;
-    if (m->kind == AZ_NN_KIND_OTHELLO_CNN) {
-        // Othello/Network.py:213-227 on the kernels of nn_othello.hip / nn_othello_heads.hip; needs positions + masks
-        if (positions == nullptr || mask == nullptr) return 1;
-        if (scratch == nullptr || scratch_bytes < az_nn_model_scratch_bytes(m, batch)) return 1;
-        const az_nn_othello_weights &o = m->ow;
-        char *base = static_cast<char *>(scratch);
-        char *tok = base; base += batch * kOtTok;
-        char *map[3];
-        for (auto &p : map) { p = base; base += batch * kOtMap10; }
-        char *pa = base; base += batch * kOtMap8;
-        char *pb = base; base += batch * kOtMap8;
-        char *neck = base;
-        auto conv = [&](int i, const void *x, const void *res, void *y) {
-            const az_nn_othello_conv_layer &l = o.conv[i];
-            return az_nn_othello_conv(x, l.w_packed, l.pre_scale, l.pre_shift, l.post_scale, l.post_shift, l.residual ? res : nullptr,
-                                      y, batch, l.c_in, l.h_in, l.pad, 1, n_rows, stream);
-        };
-        int rc = az_nn_othello_embed(positions, mask, o.embed_table, tok, batch, rows, n_rows, stream);
-        int cur = 0;                                      // map[cur] holds the running hidden state
-        if (rc == 0) rc = conv(0, tok, nullptr, map[cur]);
-        for (int i = 1; rc == 0 && i + 1 < o.n_body; i += 2) {
-            const int y1 = (cur + 1) % 3, y2 = (cur + 2) % 3;
-            rc = conv(i, map[cur], nullptr, map[y1]);
-            if (rc == 0) rc = conv(i + 1, map[y1], map[cur], map[y2]);
-            cur = y2;
-        }
-        const int hid = (cur + 1) % 3;
-        if (rc == 0) rc = conv(o.n_body - 1, map[cur], nullptr, map[hid]);
-        if (rc == 0) rc = conv(o.n_body, map[hid], nullptr, pa);
-        if (rc == 0) rc = conv(o.n_body + 1, pa, nullptr, pb);
-        if (rc == 0) rc = az_nn_othello_conv_narrow(map[hid], o.dual_w16, o.dual_scale16, o.dual_shift16, neck, batch, n_rows, stream);
-        if (rc == 0) rc = az_nn_othello_heads(pb, neck, &o.heads, probs, wdl, moves_left, batch, rows, n_rows, stream);
-        return rc;
-    }
-    if (m->kind != AZ_NN_KIND_CONNECT4_CNN && positions != nullptr) {
-        const dim3 grid(static_cast<unsigned>((batch + 255) / 256)), block(256);
-        if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
-            hipLaunchKernelGGL(k_hash_eval_positions<true>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
-                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
-        else
-            hipLaunchKernelGGL(k_hash_eval_positions<false>, grid, block, 0, static_cast<hipStream_t>(stream), *positions, mask, probs,
-                               wdl, moves_left, batch, rows, n_rows, m->hash_salt);
-        return 0;
-    }
-    if (m->kind != AZ_NN_KIND_CONNECT4_CNN) {
-        const dim3 grid(static_cast<unsigned>((batch + 3) / 4)), block(256);
-        if (m->kind == AZ_NN_KIND_HASH_OTHELLO)
-            hipLaunchKernelGGL(k_hash_eval<true>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
-                               moves_left, batch, rows, n_rows, m->hash_salt);
-        else
-            hipLaunchKernelGGL(k_hash_eval<false>, grid, block, 0, static_cast<hipStream_t>(stream), features, mask, probs, wdl,
-                               moves_left, batch, rows, n_rows, m->hash_salt);
-        return 0;
-    }
-    if (scratch == nullptr || scratch_bytes < az_nn_model_scratch_bytes(m, batch)) return 1;
-    const az_nn_model_weights &w = m->w;
-    char *a = static_cast<char *>(scratch);
-    char *b = a + batch * kTokenBytes;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    // this call carries event pairs?  (never while the stream is capturing: no timestamps there)
-    bool timed = false;
-    int slot[kKinds] = {-1, -1, -1, -1};
-    if (g_prof.on) {
-        std::lock_guard<std::mutex> lk(g_prof.mu);
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(hs, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-        if (g_prof.on && !capturing && (g_prof.seen++ % g_prof.stride) == 0) {
-            timed = true;
-            for (int kd = 0; kd < kKinds; ++kd)
-                if (g_prof.used[kd] < g_prof.start[kd].size()) slot[kd] = static_cast<int>(g_prof.used[kd]++);
-        }
-    }
-    auto begin = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.start[kd][slot[kd]], hs); };
-    auto end = [&](int kd) { if (timed && slot[kd] >= 0) (void)hipEventRecord(g_prof.stop[kd][slot[kd]], hs); };
-    int rc;
-    int first = 0;                                        // the first residual block still to run
-    // the folded stem from positions and the first residual block as one launch (a call that carries event pairs
-    // runs the two, so that the STEM and CONV rings keep timing the kernels they are named after)
-    if (m->stem_fused && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr && w.n_blocks >= 1) {
-        rc = az_nn_stem_conv_block_positions(positions, w.stem_frag, w.stem_pmap, w.block_w[0], w.block_b[0], w.block_gamma[0],
-                                             w.block_beta[0], a, batch, w.eps, rows, n_rows, stream);
-        first = 1;
-    } else {
-        begin(AZ_NN_PROFILE_STEM);
-        if (w.stem_frag != nullptr && w.stem_pmap != nullptr)
-            rc = positions != nullptr
-                ? az_nn_stem_folded_positions(positions, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream)
-                : az_nn_stem_folded(features, w.stem_frag, w.stem_pmap, a, batch, rows, n_rows, stream);
-        else
-            rc = positions != nullptr
-                ? az_nn_stem_embed_positions(positions, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream)
-                : az_nn_stem_embed(features, w.emb_own, w.emb_opp, w.pos, w.stem_w, w.stem_b, a, batch, rows, n_rows, stream);
-        end(AZ_NN_PROFILE_STEM);
-    }
-    for (int i = first; rc == 0 && i < w.n_blocks; ++i) {
-        if (i == 0) begin(AZ_NN_PROFILE_CONV);
-        rc = az_nn_conv_block(a, 64, w.block_w[i], w.block_b[i], w.block_gamma[i], w.block_beta[i], 1, b, batch,
-                              w.eps, n_rows, stream);
-        if (i == 0) end(AZ_NN_PROFILE_CONV);
-        char *t = a; a = b; b = t;
-    }
-    // a call that carries event pairs runs the attention block and the heads as two launches, so that the ATTN and
-    // HEADS rings keep timing the kernels they are named after (the fused kernel has no split to time)
-    if (rc == 0 && m->attn_heads_fused && !timed)
-        return az_nn_attn_heads(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, &w.heads, mask, probs, wdl, moves_left, batch,
-                                w.eps, rows, n_rows, stream);
-    if (rc == 0) {
-        begin(AZ_NN_PROFILE_ATTN);
-        rc = az_nn_attn_block(a, w.pre_w, w.qkvg_w, w.qn_w, w.kn_w, w.o_w, b, batch, w.eps, n_rows, stream);
-        end(AZ_NN_PROFILE_ATTN);
-        char *t = a; a = b; b = t;
-    }
-    if (rc == 0) {
-        begin(AZ_NN_PROFILE_HEADS);
-        rc = az_nn_heads(a, &w.heads, mask, probs, wdl, moves_left, batch, w.eps, rows, n_rows, stream);
-        end(AZ_NN_PROFILE_HEADS);
-    }
-    return rc;
+    return forward(m, nullptr, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
 }
 
 int az_nn_model_profile(int enable)

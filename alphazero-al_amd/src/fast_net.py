@@ -37,14 +37,8 @@ def glue():
             L = C.CDLL(path)
             vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
             L.az_nn_embed.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
-            L.az_nn_groupnorm1.argtypes = [vp, vp, vp, vp, i64, i32, f32, vp]
-            L.az_nn_silu_add.argtypes = [vp, vp, i32, vp, vp, i64, vp]
-            L.az_nn_rmsnorm64.argtypes = [vp, vp, vp, i64, f32, vp]
-            L.az_nn_qkv_prep.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, f32, vp]
-            L.az_nn_attn_post.argtypes = [vp, vp, vp, i64, vp]
             L.az_nn_heads_prep.argtypes = [vp, vp, vp, f32, vp, vp, i64, f32, vp]
             L.az_nn_conv_block.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i64, f32, vp, vp]
-            L.az_nn_conv_block2.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp, vp]
             L.az_nn_attn_block.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp]
             L.az_nn_heads.argtypes = [vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp, vp, vp]
             L.az_nn_attn_heads.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp,
@@ -62,27 +56,6 @@ def glue():
         except OSError:
             _GLUE = False
     return _GLUE or None
-
-
-def fold_block(w, bias, gamma, beta):
-    """What az_nn_conv_block2 (include/az_nn.h) takes instead of (weight, bias, gamma, beta) of a residual block
-    y = x + silu(conv(GroupNorm1(x) * gamma + beta) + bias): the weight with gamma folded in and rounded to bf16 once
-    (OHWI), t1 (9, 64) = per border class the sum of those ROUNDED weights over the taps inside the board,
-    t2_scaled (9, 64) = log2(e) * (bias + the same sum of weight * beta).  Border class = 3 * rowclass + colclass,
-    0 = first row / column (the tap at -1 falls off the board), 1 = inner, 2 = last."""
-    w32 = w.float().contiguous()                                    # (O, I, 3, 3), the bf16 values the first kernel multiplies
-    wf = (w32 * gamma.float().view(1, -1, 1, 1)).to(torch.bfloat16)
-    wff = wf.float()
-    wb = w32 * beta.float().view(1, -1, 1, 1)
-    t1 = torch.zeros((9, w.shape[0]), dtype=torch.float32, device=w.device)
-    t2 = torch.zeros_like(t1)
-    taps = {0: (1, 2), 1: (0, 1, 2), 2: (0, 1)}
-    for rc in range(3):
-        for cc in range(3):
-            kh, kw = list(taps[rc]), list(taps[cc])
-            t1[3 * rc + cc] = wff[:, :, kh][:, :, :, kw].sum((1, 2, 3))
-            t2[3 * rc + cc] = bias.float() + wb[:, :, kh][:, :, :, kw].sum((1, 2, 3))
-    return (wf.contiguous(memory_format=torch.channels_last), t1.contiguous(), (t2 * 1.4426950408889634).contiguous())
 
 
 def fold_stem(weight, bias, emb_own, emb_opp, pos_map):
@@ -211,12 +184,12 @@ class FastConnect4Net(torch.nn.Module):
         # builds for the parity tests, other widths).  One switch: tests flip `hip` to compare the two.
         self.hip = (self.device.type == "cuda" and dtype == torch.bfloat16 and self.embed_dim == 32
                     and self.h_dim == 64 and heads == 4 and glue() is not None)
-        self.mfma_conv = self.mfma_attn = self.fused_stem = self.fused_heads = self.hip
+        self.mfma_conv = self.hip            # the same switch under the name bench.py reads
         # predict_device: attention block and heads as one kernel (az_nn_attn_heads), as the native model object runs
         # them; AZ_ATTN_HEADS_FUSED=0 (read here, and by az_nn_model_create): the two launches
         self.attn_heads_fused = self.hip and os.environ.get("AZ_ATTN_HEADS_FUSED", "1") != "0"
         self._heads_w = None
-        if self.fused_heads:
+        if self.hip:
             hw = HeadsWeights()
             for n in HeadsWeights._PTRS:
                 setattr(hw, n, getattr(self, n).data_ptr())
@@ -229,7 +202,7 @@ class FastConnect4Net(torch.nn.Module):
     def native_model(self):
         """az_nn_model* over this twin's weight buffers (include/az_nn.h): the whole forward pass as
         one C call, what az_mcts_dev_search runs inside its loop.  None when the all-HIP path is off."""
-        if not self.supports_compact or not self.fused_stem or len(self.res) > MAX_BLOCKS:
+        if not self.hip or len(self.res) > MAX_BLOCKS:
             return None
         if self.__dict__.get("_model") is None:
             w = ModelWeights()
@@ -310,9 +283,6 @@ class FastConnect4Net(torch.nn.Module):
             return probs, wdl, ml
         if not (self.hip and x.is_cuda):
             lp, v, st = self(x, action_mask)
-            return lp.exp(), v.exp(), st * float(self.aux_target_offset)
-        if not self.fused_heads:
-            lp, v, st = self._forward_hip(x, action_mask)
             return lp.exp(), v.exp(), st * float(self.aux_target_offset)
         t, bsz, L, s = self._body_hip(x, attention=not self.attn_heads_fused)
         probs = torch.empty((bsz, COLS), dtype=torch.float32, device=self.device)

@@ -1,19 +1,24 @@
 /*
- * az_nn.h - C ABI of the fused "glue" kernels of the leaf evaluator (part of libaz_mcts.so).
+ * az_nn.h - C ABI of the leaf evaluator's kernels (part of libaz_mcts.so).
  *
  * These do not replace a reference FFI entry point: the reference's evaluator is a PyTorch
- * module (src/environments/Connect4/Network.py) and stays one here.  They replace, inside our
- * inference twin of that module (alphazero-al_amd/src/fast_net.py), the chains of small
- * PyTorch kernels between its GEMM-shaped operations.  All tensors are DEVICE pointers to
+ * module (src/environments/Connect4/Network.py).  Here its forward pass is three HIP launches -
+ * stem + first residual block, the other residual blocks, attention + heads - issued either from
+ * native code (az_nn_model_forward*, what az_mcts_dev_search runs) or per call from our inference
+ * twin of that module (alphazero-al_amd/src/fast_net.py).  All tensors are DEVICE pointers to
  * contiguous bf16 data in token layout (batch, 42, channels) unless stated; `stream` is a
  * hipStream_t; every function only enqueues work and returns 0, or 1 on a bad argument.
  *
- * Compact batches: the four kernels of the forward pass (embed, conv_block, attn_block, heads)
- * take `batch_dev`, a device pointer to an int64 (or NULL): when given, only the first
- * min(batch, *batch_dev) samples are processed - `batch` sizes the launch, the device decides
- * the work (the leaves that missed the transposition table, az_mcts.h).  `gather[b]` (embed)
- * is the row of the feature tensor that compact sample b shows, `scatter[b]` (heads) the row
- * of the mask and of the three output arrays it belongs to; NULL = identity.
+ * Compact batches: the kernels of the forward pass (the stem forms, conv_block, stem_conv_block,
+ * attn_block, heads, attn_heads) take `batch_dev`, a device pointer to an int64 (or NULL): when
+ * given, only the first min(batch, *batch_dev) samples are processed - `batch` sizes the launch,
+ * the device decides the work (the leaves that missed the transposition table, az_mcts.h).
+ * `gather[b]` (the stem) is the row of the feature tensor / of the positions that compact sample b
+ * shows, `scatter[b]` (heads) the row of the mask and of the three output arrays it belongs to;
+ * NULL = identity.
+ *
+ * In this order: the forward pass; the model object and its profiling; debug and self-test entry
+ * points; kernels kept as test oracles; the Othello network.
  */
 #ifndef AZ_NN_H
 #define AZ_NN_H
@@ -24,40 +29,7 @@
 extern "C" {
 #endif
 
-/* tokens[b, cell, :] = pos[cell, :] + own(b, cell) * emb_own + opp(b, cell) * emb_opp
- * (Network.py:226-239).  features: float32 (batch, 3, 6, 7) relative planes; embed_dim 32. */
-int az_nn_embed(const float *features, const void *emb_own, const void *emb_opp, const void *pos,
-                void *tokens, int64_t batch, int embed_dim, const int32_t *gather, const int64_t *batch_dev,
-                void *stream);
-/* GroupNorm(num_groups=1) over each sample's 42*channels values + per-channel affine
- * (Network.py:38,44); channels 64. */
-int az_nn_groupnorm1(const void *x, const void *gamma, const void *beta, void *y, int64_t batch,
-                     int channels, float eps, void *stream);
-/* y = residual + silu(x + bias[channel]) - convolution bias, SiLU and skip connection in one
- * pass (Network.py:44-48).  bias (channels values, channel = fastest dimension of x) and
- * residual may be NULL; n_elements and channels multiples of 8. */
-int az_nn_silu_add(const void *x, const void *bias, int channels, const void *residual, void *y,
-                   int64_t n_elements, void *stream);
-/* One whole convolution block as a single MFMA kernel (nn_conv.hip):
- *   y = [x +] silu(conv3x3([GroupNorm1(x) * gamma + beta]) + bias)        (Network.py:27-48,166-170)
- * x (batch, 42, c_in), y (batch, 42, 64); weight_ohwi = the (64, c_in, 3, 3) weight stored
- * output-major with the input channel fastest, i.e. (64, 3, 3, c_in) contiguous
- * (torch channels_last memory of the OIHW tensor).  gamma/beta NULL = no normalisation.
- * Supported: c_in 64 with normalisation (residual 0/1), c_in 32 without either (the stem). */
-int az_nn_conv_block(const void *x, int c_in, const void *weight_ohwi, const void *bias, const void *gamma,
-                     const void *beta, int residual, void *y, int64_t batch, float eps, const int64_t *batch_dev,
-                     void *stream);
-/* The residual block (c_in 64, normalised, residual) in its second form (nn_conv2.hip): one wavefront per SIMD on
- * 32x32x16 MFMAs, GroupNorm folded into weights and epilogue.  The caller prepares, once per set of weights
- * (alphazero-al_amd/src/fast_net.py `fold_block`):
- *   weight_folded_ohwi  bf16 (64, 3, 3, 64): weight * gamma[c_in], rounded to bf16 once
- *   t1  float32 (9, 64): for border class k = 3 * rowclass + colclass (0 first / 1 inner / 2 last row or column)
- *       the sum of the FOLDED (rounded) weights over the taps that fall inside the board and over c_in
- *   t2_scaled  float32 (9, 64): log2(e) * (bias + the same sum of weight * beta)
- * so that  conv(W, pad(GN(x)))[o, cell] + bias = rstd * (conv(Wf, pad(x)) - mean * t1[class(cell)][o]) + t2[class][o].
- * Same result as az_nn_conv_block up to where the one bf16 rounding sits (weights instead of normalised activations). */
-int az_nn_conv_block2(const void *x, const void *weight_folded_ohwi, const float *t1, const float *t2_scaled, void *y,
-                      int64_t batch, float eps, const int64_t *batch_dev, void *stream);
+/* ---- the forward pass */
 
 /* The stem with the embedding fused in: az_nn_embed + az_nn_conv_block(c_in 32) as one kernel
  * that builds its tokens from the feature planes (no (batch, 42, 32) tensor in HBM). */
@@ -89,6 +61,15 @@ int az_nn_stem_folded(const float *features, const void *w_frag, const float *pm
                       const int32_t *gather, const int64_t *batch_dev, void *stream);
 int az_nn_stem_folded_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap, void *y,
                                 int64_t batch, const int32_t *gather, const int64_t *batch_dev, void *stream);
+/* One whole convolution block as a single MFMA kernel (nn_conv.hip):
+ *   y = [x +] silu(conv3x3([GroupNorm1(x) * gamma + beta]) + bias)        (Network.py:27-48,166-170)
+ * x (batch, 42, c_in), y (batch, 42, 64); weight_ohwi = the (64, c_in, 3, 3) weight stored
+ * output-major with the input channel fastest, i.e. (64, 3, 3, c_in) contiguous
+ * (torch channels_last memory of the OIHW tensor).  gamma/beta NULL = no normalisation.
+ * Supported: c_in 64 with normalisation (residual 0/1), c_in 32 without either (the stem). */
+int az_nn_conv_block(const void *x, int c_in, const void *weight_ohwi, const void *bias, const void *gamma,
+                     const void *beta, int residual, void *y, int64_t batch, float eps, const int64_t *batch_dev,
+                     void *stream);
 /* az_nn_stem_folded_positions followed by the first residual block - az_nn_conv_block(c_in 64, gamma, beta, residual 1) -
  * as ONE kernel (nn_conv.hip): each wavefront computes the stem's output of its sample from the leaf's position into
  * the tile in LDS the block would have staged from HBM, so the (batch, 42, 64) stem output is neither written nor read
@@ -108,42 +89,6 @@ int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void
 int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w,
                      const void *k_norm_w, const void *o_w, void *y, int64_t batch, float eps, const int64_t *batch_dev,
                      void *stream);
-/* timing experiments on az_nn_conv_block: bit 0 skips its MFMA phase, bit 1 its epilogue and
- * stores, bit 4 records per-wavefront cycle totals of its phases (az_nn_conv_profile: 8 values
- * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store, and for
- * az_nn_stem_conv_block_positions the stem phase - for the first n / 8 wavefronts of the last launch). */
-/* Bit 8 (AZ_NN_DEBUG_LEGACY_TAIL) selects, at launch time, the earlier forms of az_nn_attn_heads (the value head once per
- * sample pair) and of the attention's gate tile (four sigmoids per lane) in az_nn_attn_block / az_nn_attn_heads: second
- * instantiations of the same kernels, same output bytes - for A/B runs and as the tests' oracle.  The bit starts set when
- * AZ_VALUE_TAIL_DEFERRED=0 is in the environment (read once, when the library is loaded); the variable is named after the
- * largest of the changes it undoes, and it also undoes the gate tile (az_nn_attn_block too) and the split tail of az_nn_heads.
- * az_nn_debug() REPLACES all flags: a later az_nn_debug(0), as the probes under tools/ make, clears the bit the environment set.
- * Bits 16-27 (AZ_NN_DEBUG_GRID_CAP(n)): at most n workgroups in az_nn_attn_heads' grid (0 = one per CU), so that tests
- * reach many samples per wavefront with few samples. */
-#define AZ_NN_DEBUG_LEGACY_TAIL 256
-#define AZ_NN_DEBUG_GRID_CAP(n) (((n) & 0xfff) << 16)
-int az_nn_debug(int flags);
-int az_nn_debug_flags(void);
-int az_nn_conv_profile(unsigned long long *out, int n);
-/* Self-test of the paired column reductions (nn_common.h col_sum2 / col_max2) on one wavefront: a, b = 64 floats each
- * (lane l's two values), out = 8 x 64 floats: col_sum2's a and b, col_sum(a), col_sum(b), then the same four with max.
- * Nothing on the evaluator's path calls it. */
-int az_nn_debug_col_reduce2(const float *a, const float *b, float *out, void *stream);
-/* nn.RMSNorm over the last dimension of 64 */
-int az_nn_rmsnorm64(const void *x, const void *w, void *y, int64_t rows, float eps, void *stream);
-/* qkvg (batch*42, row_len) with row_len 196 or 200 (3*64 q|k|v, 4 gate logits, optional zero
- * pad) -> q, k, v (batch, 4, 42, 16) with per-head RMSNorm on q and k, and sigmoid(gate)
- * (batch*42, 4) (Network.py:66-71,80). */
-int az_nn_qkv_prep(const void *qkvg, int row_len, const void *q_norm_w, const void *k_norm_w, void *q,
-                   void *k, void *v, void *gate_sigmoid, int64_t batch, float eps, void *stream);
-/* out[tok, h*16+d] = attn[b, h, t, d] * gate_sigmoid[tok, h] (Network.py:80-82) */
-int az_nn_attn_post(const void *attn, const void *gate_sigmoid, void *out, int64_t batch, void *stream);
-/* policy-head pooling and value-head mean of one pass over the final tokens (batch, 42, 64):
- * col (batch, 7, 64) = softmax-over-rows weighted sum of the RMS-normalised tokens of each
- * column, mean (batch, 64) = plain token mean (Network.py:107-113,135). */
-int az_nn_heads_prep(const void *tokens, const void *p_norm_w, const void *p_gate_w, float p_gate_b,
-                     void *col, void *mean, int64_t batch, float eps, void *stream);
-
 /* Both output heads as one kernel (nn_heads.hip): final tokens (batch, 42, 64) ->
  *   probs (batch, 7) f32       softmax of the column policy head, illegal columns (mask byte 0,
  *                              mask (batch, 7) uint8 or NULL) filled with -1e9 before the softmax
@@ -171,17 +116,21 @@ int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, c
                      float *moves_left, int64_t batch, float eps, const int32_t *scatter, const int64_t *batch_dev,
                      void *stream);
 
-/* The whole evaluator as one call (nn_model.hip): az_nn_stem_embed, n_blocks x az_nn_conv_block
- * (64 -> 64, normalised, residual), az_nn_attn_heads (az_nn_attn_block + az_nn_heads as one kernel;
- * AZ_ATTN_HEADS_FUSED=0 in the environment when the object is created: the two launches) on `stream`, issued
- * from native code - what alphazero-al_amd/src/fast_net.py does per call from Python.  The object keeps the
- * POINTERS given here (the caller keeps the arrays alive and unchanged) and is immutable, so it
+/* ---- the model object and its profiling */
+
+/* The whole evaluator as one call (nn_model.hip), issued from native code on `stream` - what
+ * alphazero-al_amd/src/fast_net.py does per call from Python.  The launches:
+ *   the stem and the first residual block  az_nn_stem_conv_block_positions - ONE launch - when the model has the folded
+ *       stem (stem_frag / stem_pmap) and n_blocks >= 1 and the call is given POSITIONS (AZ_STEM_FUSED=0 in the
+ *       environment when the object is created: two launches; same bits either way).  Else a stem form of its own:
+ *       az_nn_stem_folded[_positions] with the folded stem, az_nn_stem_embed[_positions] without;
+ *   the blocks  az_nn_conv_block (64 -> 64, normalised, residual) for each of the n_blocks not yet run;
+ *   attention and heads  az_nn_attn_heads (AZ_ATTN_HEADS_FUSED=0 in the environment when the object is created:
+ *       az_nn_attn_block, then az_nn_heads).
+ * The object keeps the POINTERS given here (the caller keeps the arrays alive and unchanged) and is immutable, so it
  * may be used from several host threads / streams at once; each call brings its own `scratch`
  * (device memory, az_nn_model_scratch_bytes(batch) bytes: two activation tensors).
  * rows / n_rows: the compact form described at the top (both NULL = every row 0..batch-1). */
-/* A model with the folded stem (stem_frag / stem_pmap) and n_blocks >= 1 that is given POSITIONS runs the stem and the
- * first residual block as one launch, az_nn_stem_conv_block_positions (AZ_STEM_FUSED=0 in the environment when the
- * object is created: the two launches; same bits either way). */
 #define AZ_NN_MAX_BLOCKS 8
 typedef struct az_nn_model_weights {
     const void *emb_own, *emb_opp, *pos;                    /* as az_nn_stem_embed */
@@ -239,6 +188,48 @@ int az_nn_model_profile_read(double *out_ms, int64_t *out_launches);
 #define AZ_NN_PROFILE_ATTN  2
 #define AZ_NN_PROFILE_HEADS 3
 int az_nn_model_profile_read_kernels(double out_ms[4], int64_t out_launches[4]);
+
+/* ---- debug and self-test entry points */
+
+/* timing experiments on az_nn_conv_block: bit 0 skips its MFMA phase, bit 1 its epilogue and
+ * stores, bit 4 records per-wavefront cycle totals of its phases (az_nn_conv_profile: 8 values
+ * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store, and for
+ * az_nn_stem_conv_block_positions the stem phase - for the first n / 8 wavefronts of the last launch). */
+/* Bit 8 (AZ_NN_DEBUG_LEGACY_TAIL) selects, at launch time, the earlier forms of az_nn_attn_heads (the value head once per
+ * sample pair) and of the attention's gate tile (four sigmoids per lane) in az_nn_attn_block / az_nn_attn_heads: second
+ * instantiations of the same kernels, same output bytes - for A/B runs and as the tests' oracle.  The bit starts set when
+ * AZ_VALUE_TAIL_DEFERRED=0 is in the environment (read once, when the library is loaded); the variable is named after the
+ * largest of the changes it undoes, and it also undoes the gate tile (az_nn_attn_block too) and the split tail of az_nn_heads.
+ * az_nn_debug() REPLACES all flags: a later az_nn_debug(0), as the probes under tools/ make, clears the bit the environment set.
+ * Bits 16-27 (AZ_NN_DEBUG_GRID_CAP(n)): at most n workgroups in az_nn_attn_heads' grid (0 = one per CU), so that tests
+ * reach many samples per wavefront with few samples. */
+#define AZ_NN_DEBUG_LEGACY_TAIL 256
+#define AZ_NN_DEBUG_GRID_CAP(n) (((n) & 0xfff) << 16)
+int az_nn_debug(int flags);
+int az_nn_debug_flags(void);
+int az_nn_conv_profile(unsigned long long *out, int n);
+/* Self-test of the paired column reductions (nn_common.h col_sum2 / col_max2) on one wavefront: a, b = 64 floats each
+ * (lane l's two values), out = 8 x 64 floats: col_sum2's a and b, col_sum(a), col_sum(b), then the same four with max.
+ * Nothing on the evaluator's path calls it. */
+int az_nn_debug_col_reduce2(const float *a, const float *b, float *out, void *stream);
+
+/* ---- kept as test oracles: neither the model object nor fast_net's predict_device launches these.  (az_nn_heads_prep
+ * also runs in fast_net's forward(), the log-probability path: its torch heads start from the pooled tokens.) */
+
+/* tokens[b, cell, :] = pos[cell, :] + own(b, cell) * emb_own + opp(b, cell) * emb_opp
+ * (Network.py:226-239).  features: float32 (batch, 3, 6, 7) relative planes; embed_dim 32. */
+int az_nn_embed(const float *features, const void *emb_own, const void *emb_opp, const void *pos,
+                void *tokens, int64_t batch, int embed_dim, const int32_t *gather, const int64_t *batch_dev,
+                void *stream);
+/* policy-head pooling and value-head mean of one pass over the final tokens (batch, 42, 64):
+ * col (batch, 7, 64) = softmax-over-rows weighted sum of the RMS-normalised tokens of each
+ * column, mean (batch, 64) = plain token mean (Network.py:107-113,135). */
+int az_nn_heads_prep(const void *tokens, const void *p_norm_w, const void *p_gate_w, float p_gate_b,
+                     void *col, void *mean, int64_t batch, float eps, void *stream);
+/* az_nn_conv_block above with c_in 32 (no normalisation, no residual): the stem convolution on az_nn_embed's tokens -
+ * the two-launch form that the stem kernels with the embedding fused in are held to, bit for bit. */
+
+/* ---- Othello */
 
 /* One 3x3 convolution layer of the reference's Othello network (Othello/Network.py:22-66,129-139:
  * 256 output channels on 10x10 / 8x8 maps) as an implicit-GEMM MFMA kernel (nn_othello.hip):

@@ -1,5 +1,5 @@
-"""The algebra behind the folded kernels, in torch fp32 on the CPU (no GPU, no HIP): what fast_net.fold_stem hands
-nn_stem.hip and what fast_net.fold_block hands nn_conv2.hip reproduce the layers they replace."""
+"""The algebra behind the folded stem, in torch fp32 on the CPU (no GPU, no HIP): what fast_net.fold_stem hands
+nn_stem.hip reproduces the layer it replaces."""
 import os
 import sys
 
@@ -53,32 +53,3 @@ def test_fold_stem_reproduces_embedding_and_convolution():
             got = got + sh.unsqueeze(1) * table[:, 2 * tap + plane].reshape(1, 64, 1, 1)
     err = (got - want).abs().max().item()
     assert err < 2e-4 * want.abs().max().item(), err
-
-
-def test_fold_block_reproduces_groupnorm_convolution():
-    """conv(W, pad(GroupNorm1(x) * gamma + beta)) + bias == rstd * (conv(W * gamma, pad(x)) - mean * t1[class]) + t2[class]
-    with the nine border classes of fast_net.fold_block (t2 comes scaled by log2 e)."""
-    from src.fast_net import fold_block
-    torch.manual_seed(6)
-    w = (torch.randn(64, 64, 3, 3) * 0.05).to(torch.bfloat16)
-    bias, gamma, beta = torch.randn(64) * 0.2, torch.randn(64) * 0.3 + 1.0, torch.randn(64) * 0.2
-    wf, t1, t2s = fold_block(w, bias, gamma, beta)
-    x = torch.randn(5, 64, 6, 7, dtype=torch.float64)
-    mean = x.mean((1, 2, 3), keepdim=True)
-    rstd = 1.0 / torch.sqrt(x.var((1, 2, 3), unbiased=False, keepdim=True) + 1e-5)
-    # the folded weight is rounded to bf16 once: compare with the convolution of THAT weight un-folded again
-    w_eff = wf.double() / gamma.double().view(1, -1, 1, 1)
-    xn = (x - mean) * rstd * gamma.double().view(1, -1, 1, 1) + beta.double().view(1, -1, 1, 1)
-    want = torch.nn.functional.conv2d(xn, w_eff, None, padding=1)
-    w32 = w.double()
-    want = want + bias.double().view(1, -1, 1, 1) + torch.nn.functional.conv2d(
-        torch.ones(1, 64, 6, 7, dtype=torch.float64) * beta.double().view(1, -1, 1, 1), w32 - w_eff, None, padding=1)
-    raw = torch.nn.functional.conv2d(x, wf.double(), None, padding=1)
-    cls = torch.zeros(6, 7, dtype=torch.long)
-    for r in range(6):
-        for c in range(7):
-            cls[r, c] = 3 * (0 if r == 0 else 2 if r == 5 else 1) + (0 if c == 0 else 2 if c == 6 else 1)
-    t1m = t1.double()[cls].permute(2, 0, 1).unsqueeze(0)          # (1, 64, 6, 7)
-    t2m = (t2s.double() / 1.4426950408889634)[cls].permute(2, 0, 1).unsqueeze(0)
-    got = rstd * (raw - mean * t1m) + t2m
-    assert (got - want).abs().max().item() < 1e-3 * want.abs().max().item()

@@ -48,16 +48,47 @@ constexpr int TS = 4;                          // samples per tile = wavefronts 
 constexpr int COUT = 64;
 constexpr int CELLB = 128;                     // bytes per image cell (C_in 32 uses half of it)
 
-// 16 bytes per lane from global memory straight into LDS at (wave-uniform) lds_off + lane * 16.
-// Written as inline assembly on purpose: when the compiler knows that a global_load_lds is in
-// flight it puts s_waitcnt vmcnt(0) in front of every later LDS read that might alias it, i.e.
-// at the top of the MFMA phase, and the HBM latency this staging is meant to hide is paid in
-// full.  The kernel orders the accesses itself (vmcnt(0) + barrier before the buffer is read).
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_off)
+// A sample's raw vectors from global memory straight into LDS, 16 bytes per lane and instruction, as ONE statement:
+// vector i of lane l comes from base + voff(l) + 1024 i and lands at lds_off + 1024 i + 16 l (the LDS side of the
+// instruction is wave-uniform base + lane order); N = 6 vectors (64 channels) or 3 (32), the last one in the lanes of
+// last_mask only.  Inline assembly on purpose: when the compiler knows that a global_load_lds is in flight it puts
+// s_waitcnt vmcnt(0) in front of every later LDS read that might alias it, i.e. at the top of the MFMA phase, and the
+// HBM latency this staging is meant to hide is paid in full.  The kernel orders the accesses itself (vmcnt(0) + barrier
+// before the buffer is read).
+// base is wave-uniform (an SGPR pair) and 1024 i sits in the instruction's offset field, which is added to the global
+// address AND to the LDS address (the compiler's own __builtin_amdgcn_global_load_lds(g, l, 16, 1024, 0) sets M0 to l
+// and the field to 1024), so M0 is written once per group of four (the field is 13-bit signed: up to 3072).  M0 is
+// compiler-reserved: saved and restored inside the statement, once.  The s_nop cover an SGPR base written by a VALU
+// (5 states) and the M0 write (1).
+template <int N>
+__device__ __forceinline__ void stage_sample(const void *base, uint32_t voff, uint32_t lds_off, uint64_t last_mask)
 {
-    uint32_t keep;      // M0 is compiler-reserved: saved and restored inside the statement
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_off) : "memory");
+    uint32_t keep;
+    uint64_t ex;
+    if constexpr (N == 6)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 2\n\t"
+                     "global_load_lds_dwordx4 %2, %3\n\t"
+                     "global_load_lds_dwordx4 %2, %3 offset:1024\n\t"
+                     "global_load_lds_dwordx4 %2, %3 offset:2048\n\t"
+                     "global_load_lds_dwordx4 %2, %3 offset:3072\n\t"
+                     "s_mov_b32 m0, %6\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %5, %3\n\t"
+                     "s_and_saveexec_b64 %1, %7\n\t"
+                     "global_load_lds_dwordx4 %5, %3 offset:1024\n\t"
+                     "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep), "=&s"(ex)
+                     : "v"(voff), "s"(base), "s"(lds_off), "v"(voff + 4096), "s"(lds_off + 4096), "s"(last_mask)
+                     : "memory", "scc");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 2\n\t"
+                     "global_load_lds_dwordx4 %2, %3\n\t"
+                     "global_load_lds_dwordx4 %2, %3 offset:1024\n\t"
+                     "s_and_saveexec_b64 %1, %5\n\t"
+                     "global_load_lds_dwordx4 %2, %3 offset:2048\n\t"
+                     "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep), "=&s"(ex)
+                     : "v"(voff), "s"(base), "s"(lds_off), "s"(last_mask)
+                     : "memory", "scc");
 }
 __device__ __forceinline__ uint32_t lds_addr(const void *p)
 {

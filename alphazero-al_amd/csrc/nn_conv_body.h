@@ -21,6 +21,10 @@
     constexpr int OVPS = CELLS * COUT / 8;        // vectors per output sample
     constexpr int OPER = (OVPS + 63) / 64;
     constexpr int OSB = OVPS * 16;                // bytes per output sample
+    // Lane l of a sample's wavefront owns vectors l, l + 64, ...: only the LAST one can lie past the sample, and only in
+    // the lanes from LASTN (OLASTN) on - 16 of 64 at 64 channels (5 * 64 + 16 = 336), 40 of 64 at 32 (2 * 64 + 40 = 168)
+    constexpr int LASTN = VPS - 64 * (PER - 1), OLASTN = OVPS - 64 * (OPER - 1);
+    static_assert(LASTN > 0 && LASTN < 64 && OLASTN > 0 && OLASTN < 64 && (PER == 6 || PER == 3), "stage_sample's two forms");
 
     extern __shared__ __align__(16) uint8_t smem[];
     uint8_t *img = smem;                                          // TS * PCELLS * CELLB, swizzled
@@ -78,30 +82,28 @@
     // output tile, so the residual block updates the raw tile in place, and it leaves every
     // lane with one fixed channel chunk in P1.
     auto swz_in = [](int cell) { return VPC == 8 ? (cell & 7) : 0; };
+    // The same layout seen from a lane (l < 64): vector l + 64 i of a sample is cell l / VPC + (64 / VPC) i - a multiple
+    // of 8 cells on, so the key does not depend on i - and sits tok_off(l) + 1024 i bytes into the sample, in HBM on
+    // either side of the kernel; in LDS (lane order) it is at 16 l + 1024 i.
+    auto tok_off = [](uint32_t l, int vpc) { return vpc == 8 ? ((l >> 3) << 7) | (((l & 7) ^ ((l >> 3) & 7)) << 4) : l << 4; };
     const uint32_t raw_lds = lds_addr(rawb);
     if (EMBED) {                                   // the raw buffers are free: the position table lives there
         for (int i = tid; i < CELLS * CIN / 8; i += 256)
             reinterpret_cast<V8 *>(rawb)[i] = reinterpret_cast<const V8 *>(em.pos)[i];
         __syncthreads();
     }
-    auto stage_tile = [&](int64_t tile, int buf, int lane) {
+    auto stage_tile = [&](int64_t tile, int buf, uint32_t lane) {
         const int64_t b = tile * TS + wave;
         if (EMBED || STEM || b >= B) return;
-        const uint16_t *xs = x + b * (CELLS * CIN);
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int s = lane + 64 * i;
-            if (s < VPS) {
-                const int cell = s / VPC;
-                glds16(xs + (cell * VPC + ((s % VPC) ^ swz_in(cell))) * 8, raw_lds + (buf * TS + wave) * SB + i * 1024);
-            }
-        }
+        // one statement for the sample: its base in SGPRs, one offset per lane, 1024 i in the offset fields; the last
+        // vector in lanes 0 .. LASTN - 1 only (another lane would read past the sample and write the next wave's slot)
+        stage_sample<PER>(x + b * (CELLS * CIN), tok_off(lane, VPC), raw_lds + (buf * TS + wave) * SB, (1ull << LASTN) - 1);
     };
 
     const int64_t ntiles = (B + TS - 1) / TS;
     // EMBED: the two planes of this wave's sample at this lane's cells, one tile ahead
     float pl_own[PER], pl_opp[PER];
-    auto load_planes = [&](int64_t tile, int lane) {
+    auto load_planes = [&](int64_t tile, uint32_t lane) {
         const int64_t b = tile * TS + wave;
         const bool live = b < B;
         int64_t row = !live ? 0 : (em.gather != nullptr ? em.gather[b] : b);
@@ -110,7 +112,7 @@
             const float *fs = em.features + row * (3 * CELLS);
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int s = lane + 64 * i;
+                const uint32_t s = lane + 64 * i;
                 const bool ok = live && s < VPS;
                 pl_own[i] = ok ? fs[s / VPC] : 0.0f;
                 pl_opp[i] = ok ? fs[CELLS + s / VPC] : 0.0f;
@@ -121,7 +123,7 @@
             const uint64_t own = p1 ? em.bb_p1[row] : em.bb_p2[row], opp = p1 ? em.bb_p2[row] : em.bb_p1[row];
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int s = lane + 64 * i;
+                const uint32_t s = lane + 64 * i;
                 const bool ok = live && s < VPS;
                 const int cell = ok ? s / VPC : 0;
                 const int r = cell / COLS, c = cell - r * COLS;
@@ -140,7 +142,7 @@
         if (tile < ntiles && b < B && st.gather != nullptr) r = st.gather[b];
         return r;
     };
-    auto request_pos = [&](int64_t tile, int32_t rowv, int lane) {
+    auto request_pos = [&](int64_t tile, int32_t rowv, uint32_t lane) {
         const int64_t b = tile * TS + wave;
         uint32_t v = 0;
         if (tile < ntiles && b < B) {
@@ -195,8 +197,11 @@
         // Opaque copy of the lane id: everything P1, P3 and the staging derive from it is
         // recomputed per tile (a few VALU ops) instead of being hoisted out of the tile loop,
         // where ~40 loop-invariant addresses would push the resident weights into scratch.
-        int lane_t = lane;
-        asm volatile("" : "+v"(lane_t));
+        // The copy is masked to what a lane id is, 0 .. 63, and unsigned: of a lane's vectors only the last one needs
+        // a bounds test, and its divisions are shifts.
+        int lane_o = lane;
+        asm volatile("" : "+v"(lane_o));
+        const uint32_t lane_t = static_cast<uint32_t>(lane_o) & 63u;
 
         // ---- P0 (STEM): this wave's sample from its position to the raw tile - k_stem's arithmetic (nn_stem.hip) with
         // the tables in LDS and the 16-byte store going to cell tok, chunk (4 m + g) ^ (tok & 7) of the raw tile.  The
@@ -211,7 +216,7 @@
                 const uint64_t own = p1 ? bb1 : bb2, opp = p1 ? bb2 : bb1;
                 const int g = lane_t >> 4, tl = lane_t & 15;
                 // the cell this lane tests when the board masks are built (cell order: 7 * row + column, row 0 on top)
-                const int my_r = lane_t / COLS, my_c = lane_t - my_r * COLS;
+                const int my_r = lane_t / COLS, my_c = static_cast<int>(lane_t) - my_r * COLS;
                 const int bit = (mir ? COLS - 1 - my_c : my_c) * 7 + (5 - my_r);
                 const bool own_here = lane_t < CELLS && ((own >> bit) & 1ull);
                 const bool opp_here = lane_t < CELLS && ((opp >> bit) & 1ull);
@@ -277,6 +282,8 @@
         // normalised vectors go to the padded image
         {
             const int ck = (lane_t % VPC) ^ swz_in(lane_t / VPC);   // the channel chunk of every slot this lane owns
+            const bool last_ok = lane_t < LASTN;                    // the only vector of a lane that can lie past the sample
+            const uint8_t *rawl = rawt + wave * SB + lane_t * 16;   // this lane's vectors: 1 KiB apart
             V8 raw[PER];
             if (EMBED) {
                 // tokens = pos[cell] + own * emb_own + opp * emb_opp (fp32 on the bf16 tables, rounded once:
@@ -284,9 +291,8 @@
                 const V8 eo = *reinterpret_cast<const V8 *>(em.emb_own + ck * 8), ep = *reinterpret_cast<const V8 *>(em.emb_opp + ck * 8);
 #pragma unroll
                 for (int i = 0; i < PER; ++i) {
-                    const int s = lane_t + 64 * i;
-                    if (s < VPS) {
-                        const V8 ps = *reinterpret_cast<const V8 *>(rawb + s * 16);
+                    if (i < PER - 1 || last_ok) {
+                        const V8 ps = *reinterpret_cast<const V8 *>(rawb + lane_t * 16 + i * 1024);
                         const f32x2 own = {pl_own[i], pl_own[i]}, opp = {pl_opp[i], pl_opp[i]};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
@@ -301,8 +307,7 @@
             } else {
 #pragma unroll
                 for (int i = 0; i < PER; ++i) {
-                    const int s = lane_t + 64 * i;
-                    if (s < VPS) raw[i] = *reinterpret_cast<const V8 *>(rawt + wave * SB + s * 16);
+                    if (i < PER - 1 || last_ok) raw[i] = *reinterpret_cast<const V8 *>(rawl + i * 1024);
                     else raw[i].w[0] = raw[i].w[1] = raw[i].w[2] = raw[i].w[3] = 0;
                 }
             }
@@ -332,8 +337,7 @@
             }
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int s = lane_t + 64 * i;
-                if (s < VPS) {
+                if (i < PER - 1 || last_ok) {
                     V8 out = raw[i];
                     if (NORM) {
 #pragma unroll
@@ -491,14 +495,22 @@
 
         // ---- P3: the output tile leaves as whole 128-byte rows (wave = sample, 16 bytes per lane)
         if (b0 + wave < B && !(dbg & 2)) {
-            uint16_t *ys = y + (b0 + wave) * (CELLS * COUT);
+            // the sample's (wave-uniform) base, one offset per lane on either side, 1024 i as a constant
+            // (the base is the sample's MIDDLE: a store's offset field holds -4096 .. 4095, which then reaches all six)
+            constexpr int MID = (OPER / 2) * 1024;
+            uint8_t *ym = reinterpret_cast<uint8_t *>(y + (b0 + wave) * (CELLS * COUT)) + MID;
+            uint32_t outl = static_cast<uint32_t>(outt - smem) + wave * OSB + lane_t * 16;
+            // (opaque, or the compiler folds MID back into the constants and builds a 64-bit address per lane for the
+            // vectors past 4095, and adds the LDS constants in registers instead of offset fields)
+            asm volatile("" : "+s"(ym), "+v"(outl));
+            auto *ymg = (__attribute__((address_space(1))) uint8_t *)ym;      // still global memory, which the statement hid
+            const uint32_t yo = tok_off(lane_t, COUT / 8);
 #pragma unroll
             for (int i = 0; i < OPER; ++i) {
-                const int s = lane_t + 64 * i;
-                if (s < OVPS) {
-                    const int cell = s >> 3;
-                    const V8 v = *reinterpret_cast<const V8 *>(outt + wave * OSB + s * 16);
-                    *reinterpret_cast<V8 *>(ys + cell * COUT + (((s & 7) ^ (cell & 7)) << 3)) = v;
+                if (i < OPER - 1 || lane_t < OLASTN) {
+                    const V8 v = *reinterpret_cast<const V8 *>(&smem[outl + i * 1024]);
+                    // (a built-in vector type: a struct has no assignment into a named address space)
+                    *reinterpret_cast<__attribute__((address_space(1))) f32x4 *>(ymg + yo + (i * 1024 - MID)) = __builtin_bit_cast(f32x4, v);
                 }
             }
         }

@@ -23,39 +23,9 @@ import os
 import torch
 import torch.nn.functional as F
 
+from src.abi import MAX_BLOCKS, HeadsWeights, ModelWeights, Positions, glue      # noqa: F401  (Positions: for callers)
+
 ROWS, COLS, CELLS = 6, 7, 42
-
-_GLUE = None
-
-
-def glue():
-    """libaz_mcts.so's fused glue kernels (include/az_nn.h), or None when unavailable."""
-    global _GLUE
-    if _GLUE is None:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libaz_mcts.so")
-        try:
-            L = C.CDLL(path)
-            vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
-            L.az_nn_embed.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
-            L.az_nn_heads_prep.argtypes = [vp, vp, vp, f32, vp, vp, i64, f32, vp]
-            L.az_nn_conv_block.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i64, f32, vp, vp]
-            L.az_nn_attn_block.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp]
-            L.az_nn_heads.argtypes = [vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp, vp, vp]
-            L.az_nn_attn_heads.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(HeadsWeights), vp, vp, vp, vp, i64, f32, vp,
-                                           vp, vp]
-            L.az_nn_stem_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
-            L.az_nn_stem_folded.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-            L.az_nn_stem_conv_block_positions.argtypes = [C.POINTER(Positions), vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, vp]
-            L.az_nn_model_create.argtypes = [C.POINTER(ModelWeights), C.POINTER(vp)]
-            L.az_nn_model_destroy.argtypes = [vp]
-            L.az_nn_model_destroy.restype = None
-            L.az_nn_model_scratch_bytes.argtypes = [vp, i64]
-            L.az_nn_model_scratch_bytes.restype = C.c_uint64
-            L.az_nn_model_forward.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, C.c_uint64, vp]
-            _GLUE = L
-        except OSError:
-            _GLUE = False
-    return _GLUE or None
 
 
 def fold_stem(weight, bias, emb_own, emb_opp, pos_map):
@@ -86,29 +56,6 @@ def fold_stem(weight, bias, emb_own, emb_opp, pos_map):
     pmap = torch.zeros((48, 68), dtype=torch.float32, device=w.device)
     pmap[:CELLS, :out_c] = pm.reshape(out_c, CELLS).t()
     return frag, pmap.contiguous()
-
-
-class Positions(C.Structure):
-    """az_nn_positions of include/az_nn.h"""
-    _fields_ = [(n, C.c_void_p) for n in ("bb_p1", "bb_p2", "turn", "sym")]
-
-
-class HeadsWeights(C.Structure):
-    """az_nn_heads_weights of include/az_nn.h"""
-    _PTRS = ("p_norm", "p_gate_w", "p_fc_w", "p_fc_b", "p_out_w", "d_pool_norm", "d_pool_w", "d_pool_b", "d_norm",
-             "d_fc_w", "d_fc_b", "d_out_norm", "d_val_w", "d_val_b", "d_aux_w")
-    _fields_ = [(n, C.c_void_p) for n in _PTRS] + [(n, C.c_float) for n in ("p_gate_b", "p_out_b", "d_aux_b", "aux_scale")]
-
-
-MAX_BLOCKS = 8          # AZ_NN_MAX_BLOCKS
-
-
-class ModelWeights(C.Structure):
-    """az_nn_model_weights of include/az_nn.h"""
-    _fields_ = ([(n, C.c_void_p) for n in ("emb_own", "emb_opp", "pos", "stem_w", "stem_b")] + [("n_blocks", C.c_int32)] +
-                [(n, C.c_void_p * MAX_BLOCKS) for n in ("block_w", "block_b", "block_gamma", "block_beta")] +
-                [(n, C.c_void_p) for n in ("pre_w", "qkvg_w", "qn_w", "kn_w", "o_w")] +
-                [("heads", HeadsWeights), ("eps", C.c_float), ("stem_frag", C.c_void_p), ("stem_pmap", C.c_void_p)])
 
 
 class FastConnect4Net(torch.nn.Module):
@@ -226,9 +173,9 @@ class FastConnect4Net(torch.nn.Module):
         # may run while the interpreter is being torn down: no nn.Module machinery, no exceptions
         try:
             h = self.__dict__.get("_model")
-            if h is not None and _GLUE:
+            if h is not None:
                 self.__dict__["_model"] = None
-                _GLUE.az_nn_model_destroy(h)
+                glue().az_nn_model_destroy(h)
         except Exception:
             pass
 

@@ -16,24 +16,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from src.fast_net import glue
-
-
-class _HeadsW(C.Structure):          # az_nn_othello_heads_weights (include/az_nn.h)
-    _PTRS = ("board_w", "pass_norm_w", "pass_fc_w", "v_conv_w", "v_bn_s", "v_bn_b", "v_fc_w", "v_fc_b", "a_fc_wt", "a_fc_b",
-             "a_norm_w", "a_out_w")
-    _fields_ = ([(n, C.c_void_p) for n in _PTRS] + [(n, C.c_float) for n in ("board_b", "pass_fc_b", "a_out_b", "aux_to_score", "eps")] +
-                [("a_fc_w16", C.c_void_p)])
-
-
-class _ConvLayer(C.Structure):       # az_nn_othello_conv_layer
-    _fields_ = [(n, C.c_void_p) for n in ("w_packed", "pre_scale", "pre_shift", "post_scale", "post_shift")] + \
-               [(n, C.c_int32) for n in ("residual", "c_in", "h_in", "pad")]
-
-
-class _OthelloW(C.Structure):        # az_nn_othello_weights
-    _fields_ = [("embed_table", C.c_void_p), ("n_body", C.c_int32), ("n_convs", C.c_int32), ("conv", _ConvLayer * 16),
-                ("dual_w16", C.c_void_p), ("dual_scale16", C.c_void_p), ("dual_shift16", C.c_void_p), ("heads", _HeadsW)]
+from src.abi import _HeadsW, _OthelloW, glue      # noqa: F401  (_HeadsW: for callers)
 
 
 def _bn_affine(bn):
@@ -73,10 +56,7 @@ class FastOthelloNet(torch.nn.Module):
         self.net = net
         self.device = net.stem[0].weight.device
         self.score_scale = float(getattr(net, "score_scale", 8.0))
-        L = glue()
-        vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-        L.az_nn_othello_conv.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
-        self._L = L
+        self._L = glue()
         dev = self.device
         ones = torch.ones(256, device=dev)
         zeros = torch.zeros(256, device=dev)
@@ -119,7 +99,6 @@ class FastOthelloNet(torch.nn.Module):
         self.dual_s = torch.ones(16, device=dev)
         self.dual_b = torch.zeros(16, device=dev)
         self.dual_s[:8], self.dual_b[:8] = s8.to(dev), b8.to(dev)
-        L.az_nn_othello_conv_narrow.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
         self.v_conv_w = dh.value_out[0].weight.detach().float().reshape(8, 72).t().contiguous()    # (72, 8)
         self.v_bn = tuple(t.to(dev).view(1, 8, 1) for t in _bn_affine(dh.value_out[1]))
 
@@ -165,10 +144,8 @@ class FastOthelloNet(torch.nn.Module):
         h.board_b, h.pass_fc_b, h.a_out_b = self.board_b, float(ph.pass_fc.bias.item()), float(dh.aux_out[5].bias.item())
         h.aux_to_score = float(self.aux_target_offset) / self.score_scale
         h.eps = 1e-5
-        L = self._L
-        L.az_nn_model_create_othello.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         handle = C.c_void_p()
-        if L.az_nn_model_create_othello(C.byref(w), C.byref(handle)) != 0:
+        if self._L.az_nn_model_create_othello(C.byref(w), C.byref(handle)) != 0:
             raise RuntimeError("az_nn_model_create_othello refused the weights")
         self.__dict__["_model_keep"] = keep
         self.__dict__["_model_w"] = w                                # what the object was built from (the tests call its entry points with it)

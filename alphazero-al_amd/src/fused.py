@@ -25,55 +25,7 @@ import os
 import numpy as np
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
-
-
-def lib():
-    global _LIB
-    if _LIB is None:
-        L = C.CDLL(os.path.join(os.path.dirname(_HERE), "lib", "libaz_mcts.so"))
-        vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-        L.az_last_error.restype = C.c_char_p
-        L.az_mcts_dev_prepare.argtypes = [vp, i32, i64]
-        L.az_mcts_dev_prepare_stream.argtypes = [vp, i32, i64, vp]
-        L.az_mcts_dev_check.argtypes = [vp, vp]
-        L.az_mcts_dev_replay.argtypes = [vp, vp, i64, i64, vp]
-        L.az_nn_model_create_hash.argtypes = [i32, C.POINTER(vp)]
-        L.az_nn_model_create_hash_salted.argtypes = [i32, C.c_uint64, C.POINTER(vp)]
-        L.az_nn_model_destroy.argtypes = [vp]
-        L.az_mcts_dev_set_roots.argtypes = [vp, vp, vp, vp, vp]
-        L.az_mcts_dev_import_roots.argtypes = [vp, vp, vp, vp]
-        L.az_mcts_dev_select.argtypes = [vp, i32, i32, vp, vp, vp]
-        L.az_mcts_dev_backprop.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-        L.az_mcts_dev_leaves.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-        L.az_mcts_dev_leaf_syms.argtypes = [vp, i32, vp, vp]
-        L.az_mcts_dev_counts.argtypes = [vp, vp, vp]
-        L.az_mcts_dev_root_stats.argtypes = [vp, vp, vp]
-        L.az_mcts_dev_prune_roots.argtypes = [vp, vp, vp]
-        L.az_mcts_dev_reset_masked.argtypes = [vp, vp, vp]
-        L.az_mcts_reserve.argtypes = [vp, i64]
-        L.az_mcts_capacity.argtypes = [vp]; L.az_mcts_capacity.restype = i64
-        L.az_mcts_epoch.argtypes = [vp]; L.az_mcts_epoch.restype = i64
-        L.az_mcts_max_used.argtypes = [vp, C.POINTER(i64)]
-        L.az_mcts_counters.argtypes = [vp, C.POINTER(i64 * 8)]
-        L.az_mcts_counters_reset.argtypes = [vp]
-        L.az_mcts_profile.argtypes = [vp, i32]
-        L.az_mcts_profile_read.argtypes = [vp, C.POINTER(C.c_double * 2), C.POINTER(i64 * 2)]
-        L.az_c4_dev_step.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, vp]
-        L.az_game_dev_step.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]
-        L.az_game_dev_valid_mask.argtypes = [i32, vp, vp, vp, vp, vp, i64, vp]
-        L.az_mcts_dev_live_leaves.argtypes = [vp, i32, vp, vp, vp]
-        L.az_mcts_dev_search.argtypes = [vp, vp, i32, i32, i32, vp]
-        L.az_mcts_dev_search_more.argtypes = [vp, vp, i32, i32, i32, vp]
-        L.az_mcts_dev_tt_create.argtypes = [vp, i32]
-        L.az_mcts_dev_tt_clear.argtypes = [vp, vp]
-        L.az_mcts_dev_tt_lookup.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-        L.az_mcts_dev_tt_insert.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-        L.az_mcts_dev_tt_stats.argtypes = [vp, C.POINTER(i64 * 4)]
-        L.az_mcts_dev_tt_refresh.argtypes = [vp, vp, vp]
-        _LIB = L
-    return _LIB
+from src.abi import _stream, check, counters, lib      # noqa: F401  (counters: read through this module by the drivers)
 
 
 def hip_runtimes_loaded():
@@ -95,11 +47,6 @@ def require_single_hip_runtime():
                            "src.MCTS_cpp so that the engine binds to torch's runtime" % ", ".join(libs))
 
 
-def check(rc):
-    if rc != 0:
-        raise RuntimeError(lib().az_last_error().decode())
-
-
 def is_device_module(pv):
     if not isinstance(pv, torch.nn.Module):
         return False
@@ -109,18 +56,6 @@ def is_device_module(pv):
     if p is None:
         return bool(getattr(pv, "is_device_evaluator", False))
     return p.is_cuda
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def counters(handle):
-    arr = (C.c_int64 * 8)()
-    check(lib().az_mcts_counters(handle, C.byref(arr)))
-    names = ("sims", "levels", "expansions", "terminal", "dup_leaves", "backup_nodes",
-             "select_launches", "backprop_launches")
-    return dict(zip(names, list(arr)))
 
 
 class FusedSearch:
@@ -205,9 +140,9 @@ class FusedSearch:
     def __del__(self):
         try:
             h = self.__dict__.get("_hash_model")
-            if h is not None and _LIB is not None:
+            if h is not None:
                 self.__dict__["_hash_model"] = None
-                _LIB.az_nn_model_destroy(h)
+                lib().az_nn_model_destroy(h)
         except Exception:
             pass
 

@@ -29,34 +29,8 @@ import numpy as np
 import torch
 
 from src import fused as F
+from src.abi import MatchConfig, lib as match_lib      # noqa: F401  (match_lib: the name callers written before src/abi.py use)
 from src.selfplay import _reserve_arenas, _setup_search
-
-
-class MatchConfig(C.Structure):
-    """az_match_config (include/az_mcts.h)."""
-    _fields_ = [("temperature", C.c_float), ("record_moves", C.c_int32)]
-
-
-def match_lib():
-    """The engine library with the az_match_* prototypes set."""
-    L = F.lib()
-    if not getattr(L, "_az_match_ready", False):
-        vp, i32, i64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
-        L.az_match_create.argtypes = [vp, vp, C.POINTER(MatchConfig), C.POINTER(vp)]
-        L.az_match_destroy.argtypes = [vp]
-        L.az_match_destroy.restype = None
-        L.az_match_set_positions.argtypes = [vp, vp, vp, vp]
-        L.az_match_step.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-        L.az_match_begin_ply.argtypes = [vp, vp, C.POINTER(i32)]
-        L.az_match_finish_ply.argtypes = [vp, vp]
-        L.az_match_set_action_tape.argtypes = [vp, vp, i64]
-        L.az_match_remaining.argtypes = [vp, C.POINTER(i64)]
-        L.az_match_results.argtypes = [vp, vp, vp, C.POINTER(i64 * 4)]
-        L.az_match_moves.argtypes = [vp, vp]
-        L.az_match_max_plies.argtypes = [vp]
-        L.az_match_sample.argtypes = [i32, vp, C.c_float, u64, u64, vp, i64, vp]
-        L._az_match_ready = True
-    return L
 
 
 def gate_win_rate(results_first, results_second, n_games):
@@ -109,7 +83,7 @@ class EvaluationMatch:
         self.device = self.sides[0].device
         self.MAX_PLIES = self.sides[0].MAX_PLIES
         self.A = self.sides[0].search.action_size
-        self.L = match_lib()
+        self.L = F.lib()
         self.config = MatchConfig(float(eval_temp), int(bool(record_moves)))
         self.record_moves = bool(record_moves)
         mt = C.c_void_p()

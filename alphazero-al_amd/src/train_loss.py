@@ -20,8 +20,8 @@ from dataclasses import dataclass
 
 import torch
 
-from src import fused as F
-from src.selfplay import ReplayBatchC
+from src.abi import ReplayBatchC, TrainGradsC, TrainHeadsC, TrainLossConfigC, TrainLossOutC, _stream, check, lib
+from src.abi import lib as train_lib      # noqa: F401  (train_lib: the name callers written before src/abi.py use)
 
 GAME_OF_ACTIONS = {7: 0, 65: 1}             # the width of log_p names the game: Connect4, Othello
 
@@ -51,44 +51,6 @@ class LossConfig:
             raise ValueError("psw_beta and entropy_lambda must not be negative")
         if int(self.td_steps) != self.td_steps or self.td_steps < 0:
             raise ValueError("td_steps must be a whole number, not negative")
-
-
-class TrainLossConfigC(C.Structure):
-    """az_train_loss_config (include/az_train.h)."""
-    _fields_ = [("value_decay", C.c_double), ("distill_alpha", C.c_double), ("distill_temp", C.c_double),
-                ("psw_beta", C.c_double), ("entropy_lambda", C.c_double), ("td_alpha", C.c_double),
-                ("td_steps", C.c_int32), ("reserved", C.c_int32), ("aux_target_offset", C.c_double)]
-
-
-class TrainHeadsC(C.Structure):
-    """az_train_heads (include/az_train.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("log_p", "value", "steps")]
-
-
-class TrainLossOutC(C.Structure):
-    """az_train_loss_out (include/az_train.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("losses", "counts", "workspace")]
-
-
-class TrainGradsC(C.Structure):
-    """az_train_grads (include/az_train.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("d_log_p", "d_value", "d_steps")]
-
-
-def train_lib():
-    """The engine library with the az_train_* prototypes set."""
-    L = F.lib()
-    if not getattr(L, "_az_train_ready", False):
-        vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-        L.az_train_loss_workspace_bytes.argtypes = [i32, i64]
-        L.az_train_loss_workspace_bytes.restype = i64
-        L.az_train_dev_loss.argtypes = [i32, C.POINTER(ReplayBatchC), C.POINTER(TrainHeadsC), i64,
-                                        C.POINTER(TrainLossConfigC), C.POINTER(TrainLossOutC), vp]
-        L.az_train_dev_loss_grad.argtypes = [i32, C.POINTER(ReplayBatchC), C.POINTER(TrainHeadsC), i64,
-                                             C.POINTER(TrainLossConfigC), C.POINTER(TrainLossOutC), vp,
-                                             C.POINTER(TrainGradsC), vp]
-        L._az_train_ready = True
-    return L
 
 
 def config_c(config, aux_target_offset):
@@ -211,15 +173,14 @@ class _KernelLoss(torch.autograd.Function):
     def forward(ctx, log_p, value, steps, batch, game, cfg):
         N = log_p.shape[0]
         dev = log_p.device
-        L = train_lib()
+        L = lib()
         losses = torch.empty(4, dtype=torch.float32, device=dev)
         counts = torch.empty(11, dtype=torch.int32, device=dev)
         work = torch.empty(L.az_train_loss_workspace_bytes(game, N), dtype=torch.uint8, device=dev)
         heads = TrainHeadsC(log_p.data_ptr(), value.data_ptr(), steps.data_ptr())
         out = TrainLossOutC(losses.data_ptr(), counts.data_ptr(), work.data_ptr())
         with torch.cuda.device(dev):
-            F.check(L.az_train_dev_loss(game, C.byref(_batch_c(batch)), C.byref(heads), N, C.byref(cfg), C.byref(out),
-                                        F._stream()))
+            check(L.az_train_dev_loss(game, C.byref(_batch_c(batch)), C.byref(heads), N, C.byref(cfg), C.byref(out), _stream()))
         ctx.save_for_backward(log_p, value, steps, losses, counts)
         ctx.batch, ctx.game, ctx.cfg = batch, game, cfg
         ctx.set_materialize_grads(False)
@@ -244,9 +205,8 @@ class _KernelLoss(torch.autograd.Function):
         out = TrainLossOutC(losses.data_ptr(), counts.data_ptr(), None)
         grads = TrainGradsC(d_log_p.data_ptr(), d_value.data_ptr(), d_steps.data_ptr())
         with torch.cuda.device(dev):
-            F.check(train_lib().az_train_dev_loss_grad(ctx.game, C.byref(_batch_c(ctx.batch)), C.byref(heads), log_p.shape[0],
-                                                       C.byref(ctx.cfg), C.byref(out), upstream.data_ptr(), C.byref(grads),
-                                                       F._stream()))
+            check(lib().az_train_dev_loss_grad(ctx.game, C.byref(_batch_c(ctx.batch)), C.byref(heads), log_p.shape[0],
+                                               C.byref(ctx.cfg), C.byref(out), upstream.data_ptr(), C.byref(grads), _stream()))
         return d_log_p, d_value, d_steps, None, None, None
 
 

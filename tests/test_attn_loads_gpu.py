@@ -38,8 +38,6 @@ def env():
     net = az_net.Connect4Net(device="cuda").eval()
     az_net.load_reference_weights(net, {k: wts[k] for k in wts.files})
     L = glue()
-    vp, i64 = C.c_void_p, C.c_int64
-    L.az_nn_model_forward_positions.argtypes = [vp, C.POINTER(Positions), vp, vp, vp, vp, i64, vp, vp, vp, C.c_uint64, vp]
     twins = {}
     for sharp in (False, True):
         fast = FastConnect4Net.from_module(net)

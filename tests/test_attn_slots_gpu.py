@@ -54,7 +54,6 @@ def env():
     from src.fast_net import FastConnect4Net, glue
     net = _random_net(torch, az_net)
     L = glue()
-    L.az_nn_debug_col_reduce2.argtypes = [C.c_void_p] * 4
     twins = {}
     for sharp in (False, True):
         fast = FastConnect4Net.from_module(net)

@@ -21,7 +21,6 @@ for E in 1..7 (Connect4; roots with full columns) and up to 33 edges (Othello), 
 root-expansion and re-rooting paths.  The same checks REJECT a sample drawn with a wrong alpha < 1 boost
 (gamma(alpha+1) left unboosted), a biased symmetry draw and a stream shared by neighbouring trees.
 """
-import ctypes as C
 import os
 import sys
 
@@ -54,7 +53,6 @@ def env():
 def host_dirichlet(L, alpha, E, rows, seed):
     """Rows of the pinned host generator: E gamma(alpha, 1) draws each, normalised as MCTS.h:360-362."""
     out = np.zeros(rows * E, np.float32)
-    L.az_rng_gamma_selftest.argtypes = [C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     assert L.az_rng_gamma_selftest(seed, alpha, rows * E, out.ctypes.data) == 0
     g = out.reshape(rows, E)
     inv = np.float32(1.0) / (g.sum(1, dtype=np.float32) + np.float32(1e-8))

@@ -985,10 +985,8 @@ def test_folded_stem_matches_torch_and_the_embedding_stem(env):
     gsym = torch.where(sym.view(-1, 1, 1) != 0, grid.flip(2), grid)
     feat = torch.stack([(gsym * turn.view(-1, 1, 1) > 0).float(), (gsym * turn.view(-1, 1, 1) < 0).float(), torch.ones_like(gsym)], 1).contiguous()
 
-    class Pos(C.Structure):
-        _fields_ = [(n, vp) for n in ("bb_p1", "bb_p2", "turn", "sym")]
-    pos = Pos(bb1.data_ptr(), bb2.data_ptr(), turn.data_ptr(), sym.data_ptr())
-    L.az_nn_stem_folded_positions.argtypes = [C.POINTER(Pos), vp, vp, vp, C.c_int64, vp, vp, vp]
+    from src.abi import Positions
+    pos = Positions(bb1.data_ptr(), bb2.data_ptr(), turn.data_ptr(), sym.data_ptr())
     ya = torch.empty((bsz, 42, 64), dtype=torch.bfloat16, device="cuda"); yb = torch.empty_like(ya)
     assert L.az_nn_stem_folded(feat.data_ptr(), net.stem_frag.data_ptr(), net.stem_pmap.data_ptr(), ya.data_ptr(), bsz, None, None, s) == 0
     assert L.az_nn_stem_folded_positions(C.byref(pos), net.stem_frag.data_ptr(), net.stem_pmap.data_ptr(), yb.data_ptr(), bsz, None, None, s) == 0
@@ -1014,8 +1012,6 @@ def test_othello_conv_kernel_matches_torch(env):
     from src.fast_othello import pack_conv_weight
     from src.fast_net import glue
     L = glue()
-    vp = C.c_void_p
-    L.az_nn_othello_conv.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     F = torch.nn.functional
     bf = lambda t: t.to(torch.bfloat16).float()                                   # noqa: E731
     g = torch.Generator(device="cuda"); g.manual_seed(5)
@@ -1048,7 +1044,6 @@ def test_othello_conv_kernel_matches_torch(env):
     assert L.az_nn_othello_conv(x.data_ptr(), wp.data_ptr(), None, None, post_s.data_ptr(), post_b.data_ptr(), None, y.data_ptr(),
                                 4, 64, 8, 1, 1, None, None) == 1                 # unsupported geometry is refused
     # the narrow kernel of the dual head's bottleneck: 256 -> 8 channels, no padding
-    L.az_nn_othello_conv_narrow.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp]
     for bsz in (3, 1000):
         x = rn(bsz, 10, 10, 256).to(torch.bfloat16)
         w = rn(8, 256, 3, 3) * (1.5 / 2304 ** 0.5)
@@ -1206,13 +1201,8 @@ def test_othello_native_model_object(env):
     net = _rand_othello_net(env, 5)
     twin = FastOthelloNet(net)
     model = twin.native_model()
+    from src.abi import Positions as Pos
     L = F.lib()
-    vp, i64 = C.c_void_p, C.c_int64
-
-    class Pos(C.Structure):
-        _fields_ = [("bb_p1", vp), ("bb_p2", vp), ("turn", vp), ("sym", vp)]
-    L.az_nn_model_forward_positions.argtypes = [vp, C.POINTER(Pos), vp, vp, vp, vp, i64, vp, vp, vp, C.c_uint64, vp]
-    L.az_nn_model_scratch_bytes.argtypes = [vp, i64]; L.az_nn_model_scratch_bytes.restype = C.c_uint64
     rng = np.random.default_rng(12)
     n = 150
     boards, turns = S.ot_openings(rng, n, 44, 0)
@@ -1305,7 +1295,6 @@ def test_native_search_refuses_misuse_and_reservation_is_sized(env):
     torch = env["torch"]
     F = env["F"]
     L = F.lib()
-    L.az_last_error.restype = F.C.c_char_p
     w = env["W"].BatchedMCTS(600, 1.4, 400, 0.3, 16)
     h = F.C.c_void_p(w.mcts.handle)
     s = F._stream()

@@ -40,7 +40,7 @@ def env():
         sys.path.insert(0, PKG)
     import torch
     from src import MCTS_cpp, az_net, fused, hash_eval, match
-    return dict(torch=torch, W=MCTS_cpp, F=fused, H=hash_eval, M=match, N=az_net, L=match.match_lib())
+    return dict(torch=torch, W=MCTS_cpp, F=fused, H=hash_eval, M=match, N=az_net, L=fused.lib())
 
 
 class _OracleC4(O.BatchedMCTS_Connect4):

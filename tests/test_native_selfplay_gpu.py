@@ -38,7 +38,7 @@ def env():
         sys.path.insert(0, PKG)
     import torch
     from src import MCTS_cpp, fused, hash_eval, selfplay
-    return dict(torch=torch, W=MCTS_cpp, F=fused, H=hash_eval, SP=selfplay, L=selfplay.selfplay_lib())
+    return dict(torch=torch, W=MCTS_cpp, F=fused, H=hash_eval, SP=selfplay, L=fused.lib())
 
 
 # ---------------------------------------------------------------------------------------- 1. fixtures

@@ -41,14 +41,6 @@ def env():
     from src import az_net, fast_othello
     from src.fast_net import Positions, glue
     L = glue()
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.az_nn_othello_conv.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
-    L.az_nn_othello_conv_narrow.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
-    L.az_nn_othello_embed.argtypes = [C.POINTER(Positions), vp, vp, vp, i64, vp, vp, vp]
-    L.az_nn_othello_heads.argtypes = [vp, vp, C.POINTER(fast_othello._HeadsW), vp, vp, vp, i64, vp, vp, vp]
-    # (other test modules declare this one with the same structure class: declared again here, for this one)
-    L.az_nn_model_forward_positions.argtypes = [vp, C.POINTER(Positions), vp, vp, vp, vp, i64, vp, vp, vp, C.c_uint64, vp]
-    L.az_nn_model_scratch_bytes.argtypes = [vp, i64]; L.az_nn_model_scratch_bytes.restype = C.c_uint64
     return dict(torch=torch, N=az_net, FO=fast_othello, Positions=Positions, L=L, cache={})
 
 

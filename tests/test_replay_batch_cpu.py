@@ -1,5 +1,5 @@
 """Augmented training batches out of the replay tensors, the parts that need no GPU (`ReplayTensors.batches`,
-`SampledReplayTensors.sample`, `ReplayBatches`, `augmented` in src/selfplay.py) against what the reference's own
+`SampledReplayTensors.sample`, `ReplayBatches`, `augmented` in src/replay.py) against what the reference's own
 `get` + `augment` and `sample` gave (fixture G16, tests/golden/make_golden_batch.py), bit for bit; and the Python
 mirror of az_replay_batch against the size the header asserts.
 
@@ -22,14 +22,14 @@ GEOMETRY = {"Connect4": (7, 6, 7, 2), "Othello": (65, 8, 8, 4)}          # actio
 
 
 @pytest.fixture(scope="module")
-def SP():
+def RP():
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     ge.build()
     if PKG not in sys.path:
         sys.path.insert(0, PKG)
-    from src import selfplay
-    return selfplay
+    from src import replay
+    return replay
 
 
 def raw_bytes(a):
@@ -37,11 +37,11 @@ def raw_bytes(a):
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
-def golden_buffer(SP, key, device="cpu", cls=None):
+def golden_buffer(RP, key, device="cpu", cls=None):
     """A buffer (ReplayTensors unless `cls`) holding fixture G15's tensors of game `key`."""
     import torch
     g = load("g15_replay_buffer")
-    buf = (cls or SP.ReplayTensors)(GAMES[key], int(g[f"{key}_capacity"][0]), device)
+    buf = (cls or RP.ReplayTensors)(GAMES[key], int(g[f"{key}_capacity"][0]), device)
     for t in TENSORS:
         getattr(buf, t).copy_(torch.from_numpy(g[f"{key}_{t}"]))
     buf._ptr = int(g[f"{key}_ptr"][0])
@@ -80,7 +80,7 @@ def reassembled(batches, S):
     return out
 
 
-def check_shapes(SP, game, batch, n):
+def check_shapes(RP, game, batch, n):
     import torch
     A, R, Cc, S = GEOMETRY[game]
     want = [(torch.float32, (S * n, 3, R, Cc)), (torch.float32, (S * n, A)), (torch.int8, (S * n, 1)), (torch.int16, (S * n, 1)),
@@ -91,14 +91,14 @@ def check_shapes(SP, game, batch, n):
 # ------------------------------------------------------------------------------------------ 1. rows
 
 @pytest.mark.parametrize("key", sorted(GAMES))
-def test_torch_route_equals_the_reference_batch(SP, key):
+def test_torch_route_equals_the_reference_batch(RP, key):
     game = GAMES[key]
-    buf = golden_buffer(SP, key)
+    buf = golden_buffer(RP, key)
     idx, expected = golden_batch(key)
     S = GEOMETRY[game][3]
     whole = list(buf.batches(idx, len(idx), route="torch"))
     assert len(whole) == 1
-    check_shapes(SP, game, whole[0], len(idx))
+    check_shapes(RP, game, whole[0], len(idx))
     assert differences(batch_arrays(whole[0]), expected) == []
     # the default route on the CPU is the torch route
     assert differences(batch_arrays(next(iter(buf.batches(idx, len(idx))))), expected) == []
@@ -116,8 +116,8 @@ def test_torch_route_equals_the_reference_batch(SP, key):
         short = len(idx) % size
         assert short and len(parts) == len(loader) == len(idx) // size + 1
         for p in parts[:-1]:
-            check_shapes(SP, game, p, size)
-        check_shapes(SP, game, parts[-1], short)
+            check_shapes(RP, game, p, size)
+        check_shapes(RP, game, parts[-1], short)
         assert differences(reassembled(parts, S), expected) == []
         dropped = buf.batches(idx, size, route="torch", drop_last=True)
         kept = list(dropped)
@@ -128,9 +128,9 @@ def test_torch_route_equals_the_reference_batch(SP, key):
 
 
 @pytest.mark.parametrize("key", sorted(GAMES))
-def test_order_names_positions_of_the_sample(SP, key):
+def test_order_names_positions_of_the_sample(RP, key):
     game = GAMES[key]
-    buf = golden_buffer(SP, key)
+    buf = golden_buffer(RP, key)
     idx, expected = golden_batch(key)
     S, n = GEOMETRY[game][3], len(idx)
     order = np.random.default_rng(3).permutation(n)
@@ -164,22 +164,22 @@ def test_the_fixture_holds_the_rows_it_promises():
             assert (mask[:, 64] & ~mask.all(1)).any()
 
 
-def test_augmented_is_the_identity(SP):
+def test_augmented_is_the_identity(RP):
     batch = tuple(object() for _ in range(8))
-    assert SP.augmented(batch) is batch
+    assert RP.augmented(batch) is batch
 
 
 # ------------------------------------------------------------------------------------------ 2. sample sizes
 
-def test_sample_sizes_equal_the_reference(SP):
+def test_sample_sizes_equal_the_reference(RP):
     g = load("g16_training_batch")
     cases, sizes = g["sample_cases"], g["sample_sizes"]
     assert len(cases) == len(sizes) >= 40
     assert {0.25, 0.025} == set(cases[:, 2].tolist()) and {0, 1} == set(cases[:, 4].astype(int).tolist())
     for (length, capacity, ratio, batch, full), (n_rows, n_batches) in zip(cases.tolist(), sizes.tolist()):
         length, capacity, batch, full = int(length), int(capacity), int(batch), bool(int(full))
-        assert SP.sample_size(length, batch, full, ratio) == n_rows, (length, ratio, batch, full)
-        buf = SP.SampledReplayTensors("Connect4", capacity, "cpu")
+        assert RP.sample_size(length, batch, full, ratio) == n_rows, (length, ratio, batch, full)
+        buf = RP.SampledReplayTensors("Connect4", capacity, "cpu")
         buf._ptr = length
         loader = buf.sample(batch, full_batches=full, replay_ratio=ratio, seed=5)
         assert (loader.indices.numel(), len(loader)) == (n_rows, n_batches), (length, capacity, ratio, batch, full)
@@ -187,9 +187,9 @@ def test_sample_sizes_equal_the_reference(SP):
         assert 0 <= lo and hi < length
 
 
-def test_sample_is_seeded_and_counts_its_calls(SP):
+def test_sample_is_seeded_and_counts_its_calls(RP):
     import torch
-    a, b = golden_buffer(SP, "c4", cls=SP.SampledReplayTensors), golden_buffer(SP, "c4", cls=SP.SampledReplayTensors)
+    a, b = golden_buffer(RP, "c4", cls=RP.SampledReplayTensors), golden_buffer(RP, "c4", cls=RP.SampledReplayTensors)
     first_a, first_b = a.sample(32, seed=9), b.sample(32, seed=9)
     assert first_a.indices.dtype == torch.int64 and first_a.indices.numel() == len(a) == 389
     assert torch.equal(first_a.indices, first_b.indices)
@@ -202,16 +202,16 @@ def test_sample_is_seeded_and_counts_its_calls(SP):
     with pytest.raises(ValueError):
         a.sample(-3, full_batches=True)
     with pytest.raises(AssertionError):
-        SP.SampledReplayTensors("Connect4", 50, "cpu").sample(8)       # nothing stored yet
+        RP.SampledReplayTensors("Connect4", 50, "cpu").sample(8)       # nothing stored yet
 
 
 # ------------------------------------------------------------------------------------------ 3. epochs
 
 @pytest.mark.parametrize("key", sorted(GAMES))
-def test_epochs_cover_the_sample_once_each_in_different_orders(SP, key):
+def test_epochs_cover_the_sample_once_each_in_different_orders(RP, key):
     import torch
     game = GAMES[key]
-    buf = golden_buffer(SP, key, cls=SP.SampledReplayTensors)
+    buf = golden_buffer(RP, key, cls=RP.SampledReplayTensors)
     buf.aux_target[:, 0] = torch.arange(len(buf), dtype=torch.int16)     # tag every ring row with its index
     loader = buf.sample(50, seed=2)
     n, S = loader.indices.numel(), GEOMETRY[game][3]
@@ -236,12 +236,12 @@ def test_epochs_cover_the_sample_once_each_in_different_orders(SP, key):
 
 # ------------------------------------------------------------------------------------------ 4. the header
 
-def test_batch_struct_mirror_has_the_size_the_header_asserts(SP):
+def test_batch_struct_mirror_has_the_size_the_header_asserts(RP):
     hdr = open(os.path.join(ROOT, "include", "az_mcts.h")).read()
     m = re.search(r"#define\s+AZ_REPLAY_BATCH_BYTES\s+(\d+)", hdr)
     assert m and "sizeof(az_replay_batch) == AZ_REPLAY_BATCH_BYTES" in hdr
-    assert C.sizeof(SP.ReplayBatchC) == int(m.group(1)) == 8 * C.sizeof(C.c_void_p)
+    assert C.sizeof(RP.ReplayBatchC) == int(m.group(1)) == 8 * C.sizeof(C.c_void_p)
     body = re.search(r"typedef struct az_replay_batch \{(.*?)\} az_replay_batch;", hdr, re.S).group(1)
-    assert re.findall(r"\b(\w+);", body) == [f[0] for f in SP.ReplayBatchC._fields_] == list(TENSORS)
+    assert re.findall(r"\b(\w+);", body) == [f[0] for f in RP.ReplayBatchC._fields_] == list(TENSORS)
     for name in ("az_game_num_augment", "az_replay_dev_batch", "az_replay_dev_sample_indices"):
         assert re.search(r"\bint\s+%s\(" % name, hdr), name

@@ -1,6 +1,6 @@
 """Augmented training batches out of the replay ring on the device (k_replay_batch and k_replay_indices:
 az_replay_dev_batch / az_replay_dev_sample_indices in include/az_mcts.h, `ReplayTensors.batches`,
-`SampledReplayTensors.sample` and `ReplayBatches` in src/selfplay.py).
+`SampledReplayTensors.sample` and `ReplayBatches` in src/replay.py).
 
 1. the kernel against what the reference's `get` + `augment` returned (fixture G16), both games, whole and split
    batches, with and without `order`;
@@ -43,8 +43,8 @@ def env():
     if PKG not in sys.path:
         sys.path.insert(0, PKG)
     import torch
-    from src import fused, hash_eval, selfplay
-    return dict(torch=torch, F=fused, H=hash_eval, SP=selfplay, L=selfplay.selfplay_lib())
+    from src import fused, hash_eval, replay, selfplay
+    return dict(torch=torch, F=fused, H=hash_eval, SP=selfplay, RP=replay, L=fused.lib())
 
 
 def hash_net(env, game):
@@ -60,17 +60,17 @@ def one_batch(buf, idx, route):
 
 @pytest.mark.parametrize("key", sorted(GAMES))
 def test_kernel_equals_the_reference_batch(env, key):
-    SP = env["SP"]
+    RP = env["RP"]
     game = GAMES[key]
     S = GEOMETRY[game][3]
-    buf = golden_buffer(SP, key, "cuda")
+    buf = golden_buffer(RP, key, "cuda")
     idx, expected = golden_batch(key)
     n = len(idx)
     loader = buf.batches(idx, n)
     assert loader.route == "kernel"
     whole = list(loader)
     assert len(whole) == 1
-    check_shapes(SP, game, whole[0], n)
+    check_shapes(RP, game, whole[0], n)
     assert all(x.is_cuda and x.is_contiguous() for x in whole[0])
     assert differences(batch_arrays(whole[0]), expected) == []
     order = np.random.default_rng(8).permutation(n)
@@ -94,10 +94,10 @@ def test_kernel_equals_the_reference_batch(env, key):
 # ---------------------------------------------------------------------------------------- 2. at scale
 
 def played_ring(env, game, n_games, plies, every, capacity, cls=None):
-    SP = env["SP"]
+    SP, RP = env["SP"], env["RP"]
     sp = SP.NativeSelfPlay(hash_net(env, game), n_games, n_playout=16, vl_batch=4, seed=33, temp_decay_moves=10, record=True,
                            td_steps=3, refill=True, game=game)
-    buf = (cls or SP.ReplayTensors)(game, capacity, "cuda")
+    buf = (cls or RP.ReplayTensors)(game, capacity, "cuda")
     for _ in range(plies // every):
         sp.step(every)
         sp.export(buf)
@@ -133,7 +133,7 @@ def test_kernel_route_equals_torch_route_at_scale(env, game, n_games, plies, eve
             assert len(fast) == len(slow) == (n + size - 1) // size
             with_policy = []
             for a, b in zip(fast, slow):
-                check_shapes(env["SP"], game, a, a[2].shape[0] // S)
+                check_shapes(env["RP"], game, a, a[2].shape[0] // S)
                 assert differences(batch_arrays(a), batch_arrays(b)) == []
                 pa, ta = consumer_lines(a)
                 pb, tb = consumer_lines(b)
@@ -149,10 +149,10 @@ def test_kernel_route_equals_torch_route_at_scale(env, game, n_games, plies, eve
 
 @pytest.mark.parametrize("key", sorted(GAMES))
 def test_rows_outside_the_ring_are_zero_and_nothing_else_is_touched(env, key):
-    torch, SP, L, F = env["torch"], env["SP"], env["L"], env["F"]
+    torch, SP, RP, L, F = env["torch"], env["SP"], env["RP"], env["L"], env["F"]
     game = GAMES[key]
     A, R, Cc, S = GEOMETRY[game]
-    buf = golden_buffer(SP, key, "cuda")
+    buf = golden_buffer(RP, key, "cuda")
     cap = buf.current_capacity
     good, _ = golden_batch(key)
     idx = good[:24].copy()
@@ -170,7 +170,7 @@ def test_rows_outside_the_ring_are_zero_and_nothing_else_is_touched(env, key):
         assert (slabs[t].data_ptr() + GUARD) % 16 == 0
     out = SP.ReplayBatchC(*(slabs[t].data_ptr() + GUARD for t in TENSORS))
     d_idx = torch.from_numpy(idx).cuda()
-    F.check(L.az_replay_dev_batch(0 if game == "Connect4" else 1, C.byref(SP.replay_tensors_c(buf, game, "cuda")), d_idx.data_ptr(),
+    F.check(L.az_replay_dev_batch(0 if game == "Connect4" else 1, C.byref(RP.replay_tensors_c(buf, game, "cuda")), d_idx.data_ptr(),
                                   None, 0, B, C.byref(out), F._stream()))
     torch.cuda.synchronize()
     inside = np.array([i for i in range(B) if i not in outside])
@@ -201,7 +201,7 @@ class RawBatch(C.Structure):
 
 
 def test_c_abi_alone_via_ctypes(env):
-    torch, SP = env["torch"], env["SP"]
+    torch, RP = env["torch"], env["RP"]
     L = C.CDLL(os.path.join(PKG, "lib", "libaz_mcts.so"))
     L.az_last_error.restype = C.c_char_p
     vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
@@ -212,7 +212,7 @@ def test_c_abi_alone_via_ctypes(env):
     for key, game_id in (("c4", 0), ("ot", 1)):
         game = GAMES[key]
         A, R, Cc, S = GEOMETRY[game]
-        buf = golden_buffer(SP, key, "cuda")
+        buf = golden_buffer(RP, key, "cuda")
         idx, expected = golden_batch(key)
         n = len(idx)
         order = np.random.default_rng(1).permutation(n)
@@ -334,11 +334,11 @@ def test_the_index_check_rejects_a_biased_draw():
 # ---------------------------------------------------------------------------------------- 6. interleaving
 
 def test_batches_between_steps_and_exports_on_one_stream(env):
-    torch, SP = env["torch"], env["SP"]
+    torch, SP, RP = env["torch"], env["SP"], env["RP"]
     game = "Connect4"
     sp = SP.NativeSelfPlay(hash_net(env, game), 512, n_playout=16, vl_batch=4, seed=6, temp_decay_moves=10, record=True,
                            td_steps=2, refill=True, game=game)
-    buf = SP.ReplayTensors(game, 4001, "cuda")
+    buf = RP.ReplayTensors(game, 4001, "cuda")
     sp.step(12)
     sp.export(buf)
     taken = []
@@ -351,7 +351,7 @@ def test_batches_between_steps_and_exports_on_one_stream(env):
         assert len(buf) > 0
         idx = torch.randint(0, len(buf), (700,), device="cuda", generator=gen)
         loader = buf.batches(idx, 512)
-        snap = SP.ReplayTensors(game, 4001, "cuda")
+        snap = RP.ReplayTensors(game, 4001, "cuda")
         for t in TENSORS:
             getattr(snap, t).copy_(getattr(buf, t))
         snap._ptr = buf._ptr
@@ -370,14 +370,14 @@ def test_batches_between_steps_and_exports_on_one_stream(env):
 
 @pytest.mark.parametrize("key", sorted(GAMES))
 def test_sample_on_the_device_end_to_end(env, key):
-    torch, SP = env["torch"], env["SP"]
+    torch, RP = env["torch"], env["RP"]
     game = GAMES[key]
     S = GEOMETRY[game][3]
-    buf = golden_buffer(SP, key, "cuda", cls=SP.SampledReplayTensors)
+    buf = golden_buffer(RP, key, "cuda", cls=RP.SampledReplayTensors)
     buf.aux_target[:, 0] = torch.arange(len(buf), dtype=torch.int16, device="cuda")       # tag every ring row with its index
     loader = buf.sample(50, seed=4)
     assert loader.route == "kernel" and loader.indices.is_cuda and loader.indices.numel() == len(buf)
-    twin = golden_buffer(SP, key, "cuda", cls=SP.SampledReplayTensors)
+    twin = golden_buffer(RP, key, "cuda", cls=RP.SampledReplayTensors)
     assert torch.equal(twin.sample(50, seed=4).indices, loader.indices)
     assert not torch.equal(twin.sample(50, seed=4).indices, loader.indices) and twin.sample_calls == 2
     sampled = np.sort(loader.indices.cpu().numpy())
@@ -395,4 +395,4 @@ def test_sample_on_the_device_end_to_end(env, key):
     assert not np.array_equal(epochs[0], epochs[1])
     full = buf.sample(50, full_batches=True, seed=4)
     assert len(full) == len(buf) // 50 and all(b[0].shape[0] == S * 50 for b in full)
-    assert SP.augmented(batch) is batch
+    assert RP.augmented(batch) is batch

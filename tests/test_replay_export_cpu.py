@@ -1,4 +1,4 @@
-"""The host route into the replay-buffer tensors (`ReplayTensors.store_games` in src/selfplay.py) against the
+"""The host route into the replay-buffer tensors (`ReplayTensors.store_games` in src/replay.py) against the
 reference's own `ReplayBuffer.store` (fixture G15, tests/golden/make_golden_replay.py), and the Python mirror of
 az_replay_tensors against the size the header asserts.  No GPU."""
 import ctypes as C
@@ -28,6 +28,12 @@ def SP():
         sys.path.insert(0, PKG)
     from src import selfplay
     return selfplay
+
+
+@pytest.fixture(scope="module")
+def RP(SP):
+    from src import replay
+    return replay
 
 
 def fixture_games(name):
@@ -69,9 +75,9 @@ def golden(key):
     return {t: g[f"{key}_{t}"] for t in TENSORS}, int(g[f"{key}_ptr"][0]), int(g[f"{key}_capacity"][0])
 
 
-def naive_store(SP, game, capacity, games):
+def naive_store(RP, game, capacity, games):
     """Row by row, one assignment per tuple and column: the ring rule spelled out."""
-    buf = SP.ReplayTensors(game, capacity, "cpu")
+    buf = RP.ReplayTensors(game, capacity, "cpu")
     arr = buffer_arrays(buf)
     ptr = 0
     for _w, play, _s in games:
@@ -90,11 +96,11 @@ def naive_store(SP, game, capacity, games):
 
 
 @pytest.mark.parametrize("key", sorted(GOLDEN_CASES))
-def test_store_games_equals_the_reference_buffer(SP, key):
+def test_store_games_equals_the_reference_buffer(RP, key):
     """1 + 6: every tensor, every ring slot, `_ptr`; and the comparison notices one flipped byte anywhere."""
     game, names = GOLDEN_CASES[key]
     expected, ptr, cap = golden(key)
-    buf = SP.ReplayTensors(game, cap, "cpu")
+    buf = RP.ReplayTensors(game, cap, "cpu")
     rows = sum(buf.store_games(fixture_games(n)) for n in names)
     assert rows == ptr > cap
     got = buffer_arrays(buf)
@@ -109,10 +115,10 @@ def test_store_games_equals_the_reference_buffer(SP, key):
         assert differences(got, broken) == [t], (t, at)
 
 
-def test_fresh_tensors_have_the_reference_layout(SP):
+def test_fresh_tensors_have_the_reference_layout(RP):
     import torch
     for game, (A, R, Cc) in (("Connect4", (7, 6, 7)), ("Othello", (65, 8, 8))):
-        b = SP.ReplayTensors(game, 50, "cpu")
+        b = RP.ReplayTensors(game, 50, "cpu")
         want = dict(state=(torch.int8, (50, 3, R, Cc)), prob=(torch.float32, (50, A)), winner=(torch.int8, (50, 1)),
                     steps_to_end=(torch.int16, (50, 1)), aux_target=(torch.int16, (50, 1)), root_wdl=(torch.float32, (50, 3)),
                     valid_mask=(torch.bool, (50, A)), future_root_wdl=(torch.float32, (50, 3)))
@@ -126,10 +132,10 @@ def test_fresh_tensors_have_the_reference_layout(SP):
         assert not hasattr(b, "sample") and not hasattr(b, "save") and not hasattr(b, "replay_ratio")
 
 
-def test_td_steps_zero_leaves_the_future_column_zero(SP):
+def test_td_steps_zero_leaves_the_future_column_zero(RP):
     games = fixture_games("g11_selfplay_plain_search")                  # recorded with td_steps = 0: seven columns
     assert all(len(t) == 7 for _w, play, _s in games for t in play)
-    buf = SP.ReplayTensors("Connect4", 97, "cpu")
+    buf = RP.ReplayTensors("Connect4", 97, "cpu")
     buf.future_root_wdl.fill_(7.0)                                       # whatever was there before
     buf.store_games(games)
     assert buf._ptr > 97 and not buf.future_root_wdl.any()
@@ -137,22 +143,22 @@ def test_td_steps_zero_leaves_the_future_column_zero(SP):
 
 @pytest.mark.parametrize("game,name,capacity", [("Connect4", "g10_selfplay_numpy_rng", 61), ("Connect4", "g10_selfplay_numpy_rng", 19),
                                                 ("Othello", "g12_selfplay_othello", 50)])
-def test_more_rows_than_capacity_equals_one_by_one(SP, game, name, capacity):
+def test_more_rows_than_capacity_equals_one_by_one(RP, game, name, capacity):
     """One call with several times the ring's rows (capacity 19 and 50: less than ONE game's rows) against the
     same games stored one at a time, and against row-by-row assignment."""
     games = fixture_games(name)
     assert sum(len(p) for _w, p, _s in games) > 3 * capacity
-    at_once = SP.ReplayTensors(game, capacity, "cpu")
+    at_once = RP.ReplayTensors(game, capacity, "cpu")
     at_once.store_games(games)
-    singly = SP.ReplayTensors(game, capacity, "cpu")
+    singly = RP.ReplayTensors(game, capacity, "cpu")
     for g in games:
         singly.store_games([g])
-    naive, ptr = naive_store(SP, game, capacity, games)
+    naive, ptr = naive_store(RP, game, capacity, games)
     assert differences(buffer_arrays(at_once), naive) == [] and differences(buffer_arrays(singly), naive) == []
     assert at_once._ptr == singly._ptr == ptr
 
 
-def test_tensor_struct_mirror_has_the_size_the_header_asserts(SP):
+def test_tensor_struct_mirror_has_the_size_the_header_asserts(SP, RP):
     hdr = open(os.path.join(ROOT, "include", "az_mcts.h")).read()
     m = re.search(r"#define\s+AZ_REPLAY_TENSORS_BYTES\s+(\d+)", hdr)
     assert m and "sizeof(az_replay_tensors) == AZ_REPLAY_TENSORS_BYTES" in hdr
@@ -160,6 +166,6 @@ def test_tensor_struct_mirror_has_the_size_the_header_asserts(SP):
     body = re.search(r"typedef struct az_replay_tensors \{(.*?)\} az_replay_tensors;", hdr, re.S).group(1)
     declared = re.findall(r"\b(\w+);", body)
     assert declared == [f[0] for f in SP.ReplayTensorsC._fields_] == list(TENSORS) + ["capacity"]
-    assert tuple(SP.ReplayTensors.TENSORS) == TENSORS
+    assert tuple(RP.ReplayTensors.TENSORS) == TENSORS
     body = re.search(r"typedef struct az_selfplay_export_info \{(.*?)\} az_selfplay_export_info;", hdr, re.S).group(1)
     assert re.findall(r"\*?(\w+)[,;]", body) == [f[0] for f in SP.SelfPlayExportInfo._fields_]

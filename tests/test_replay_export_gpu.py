@@ -37,8 +37,8 @@ def env():
     if PKG not in sys.path:
         sys.path.insert(0, PKG)
     import torch
-    from src import fused, hash_eval, selfplay
-    return dict(torch=torch, F=fused, H=hash_eval, SP=selfplay, L=selfplay.selfplay_lib())
+    from src import fused, hash_eval, replay, selfplay
+    return dict(torch=torch, F=fused, H=hash_eval, SP=selfplay, RP=replay, L=fused.lib())
 
 
 def hash_net(env, game):
@@ -120,7 +120,7 @@ def check_emptied(sp):
 def test_exported_fixture_games_equal_the_reference_buffer(env, key):
     game, names = GOLDEN_CASES[key]
     expected, ptr, cap = golden(key)
-    buf = env["SP"].ReplayTensors(game, cap, "cuda")
+    buf = env["RP"].ReplayTensors(game, cap, "cuda")
     rows = 0
     for name in names:
         sp = played_fixture(env, name)
@@ -144,8 +144,8 @@ def test_exported_noise_decay_games_equal_the_host_route(env):
     name = "g14_selfplay_noise_decay"
     game = FIXTURE_CASES[name][1]
     a, b = played_fixture(env, name), played_fixture(env, name)
-    dev = env["SP"].ReplayTensors(game, 101, "cuda")
-    host = env["SP"].ReplayTensors(game, 101, "cpu")
+    dev = env["RP"].ReplayTensors(game, 101, "cuda")
+    host = env["RP"].ReplayTensors(game, 101, "cpu")
     dev._ptr = host._ptr = 77                                           # a buffer in use
     a.export(dev)
     host.store_games(b.drain())
@@ -159,11 +159,11 @@ def test_exported_noise_decay_games_equal_the_host_route(env):
 @pytest.mark.parametrize("game,n_games,plies,every,capacity,at_least", [
     ("Connect4", 4096, 40, 8, 20011, 2000), ("Othello", 256, 140, 10, 4099, 300)])
 def test_export_at_scale_equals_drain_and_store_games(env, game, n_games, plies, every, capacity, at_least):
-    SP = env["SP"]
+    SP, RP = env["SP"], env["RP"]
     kw = dict(n_playout=16, vl_batch=4, seed=21, temp_decay_moves=10, record=True, td_steps=3, refill=True, game=game)
     net = hash_net(env, game)
     a, b = SP.NativeSelfPlay(net, n_games, **kw), SP.NativeSelfPlay(net, n_games, **kw)
-    dev, host = SP.ReplayTensors(game, capacity, "cuda"), SP.ReplayTensors(game, capacity, "cpu")
+    dev, host = RP.ReplayTensors(game, capacity, "cuda"), RP.ReplayTensors(game, capacity, "cpu")
     exported = 0
     for _ in range(plies // every):
         a.step(every)
@@ -181,7 +181,7 @@ def test_export_at_scale_equals_drain_and_store_games(env, game, n_games, plies,
 
 @pytest.mark.parametrize("game,n_games,plies", [("Connect4", 256, 40), ("Othello", 32, 130)])
 def test_dev_store_on_uploaded_games(env, game, n_games, plies):
-    torch, SP, L, F = env["torch"], env["SP"], env["L"], env["F"]
+    torch, SP, RP, L, F = env["torch"], env["SP"], env["RP"], env["L"], env["F"]
     td = 2
     sp = SP.NativeSelfPlay(hash_net(env, game), n_games, n_playout=16, vl_batch=4, seed=9, temp_decay_moves=10, record=True,
                            td_steps=td, game=game)
@@ -210,10 +210,10 @@ def test_dev_store_on_uploaded_games(env, game, n_games, plies):
     games_dev = SP.SelfPlayGames(slot=None, length=length.data_ptr(), winner=winner.data_ptr(), finish_ply=None, row_start=None,
                                  **{k: up[k].data_ptr() for k in ("bb_p1", "bb_p2", "turn", "prob", "wdl", "mask")})
     for capacity, ptr in ((total + 57, 0), (total + 57, total + 30), (total // 3 + 1, 12345), (101, 7), (19, 0)):
-        dev, host = SP.ReplayTensors(game, capacity, "cuda"), SP.ReplayTensors(game, capacity, "cpu")
+        dev, host = RP.ReplayTensors(game, capacity, "cuda"), RP.ReplayTensors(game, capacity, "cpu")
         dev._ptr = host._ptr = ptr
         F.check(L.az_replay_dev_store(sp.game_id, C.byref(games_dev), src.data_ptr(), dst.data_ptr(), n,
-                                      C.byref(SP.replay_tensors_c(dev, game, "cuda")), ptr, td, F._stream()))
+                                      C.byref(RP.replay_tensors_c(dev, game, "cuda")), ptr, td, F._stream()))
         dev._ptr += total
         host.store_games(games)
         same_buffers(dev, host)
@@ -222,10 +222,10 @@ def test_dev_store_on_uploaded_games(env, game, n_games, plies):
 # ---------------------------------------------------------------------------------------- 4. conservation
 
 def test_no_game_lost_or_doubled_across_interleaved_steps_and_exports(env):
-    SP = env["SP"]
+    SP, RP = env["SP"], env["RP"]
     sp = SP.NativeSelfPlay(hash_net(env, "Connect4"), 512, n_playout=16, vl_batch=4, seed=2, temp_decay_moves=10, record=True,
                            td_steps=1, max_finished_games=96)
-    buf = SP.ReplayTensors("Connect4", 5003, "cuda")
+    buf = RP.ReplayTensors("Connect4", 5003, "cuda")
     seen, exported, rows = set(), 0, 0
     for chunk in (3, 1, 4, 1, 5, 9, 2, 6, 5, 3, 5, 8, 9, 7):
         sp.step(chunk)                                                   # nothing between the two calls
@@ -286,7 +286,7 @@ def raw_drain_games(SP, L, sp, game, A, td):
 
 
 def test_c_abi_alone_via_ctypes(env):
-    torch, SP = env["torch"], env["SP"]
+    torch, SP, RP = env["torch"], env["SP"], env["RP"]
     L = C.CDLL(os.path.join(PKG, "lib", "libaz_mcts.so"))
     L.az_last_error.restype = C.c_char_p
     vp, i64 = C.c_void_p, C.c_int64
@@ -307,8 +307,8 @@ def test_c_abi_alone_via_ctypes(env):
     td = 2
     for game_id, game, n, n_playout, A, plies in ((0, "Connect4", 96, 16, 7, 30), (1, "Othello", 24, 8, 65, 70)):
         cap = 1009
-        dev = SP.ReplayTensors(game, cap, "cuda")
-        host = SP.ReplayTensors(game, cap, "cpu")
+        dev = RP.ReplayTensors(game, cap, "cuda")
+        host = RP.ReplayTensors(game, cap, "cpu")
         torch.cuda.synchronize()
         tensors = RawTensors(*(getattr(dev, t).data_ptr() for t in TENSORS), cap)
         engines = []
@@ -385,12 +385,12 @@ def test_c_abi_alone_via_ctypes(env):
 # ---------------------------------------------------------------------------------------- 6. streams
 
 def test_streamed_export_equals_its_drivers_exported_alone(env):
-    SP = env["SP"]
+    SP, RP = env["SP"], env["RP"]
     net = hash_net(env, "Connect4")
     kw = dict(n_playout=24, vl_batch=4, temp_decay_moves=6, record=True, td_steps=2)
     plies, cap = 30, 3001
     sp = SP.StreamedSelfPlay(net, 1300, streams=2, seed=3, driver="native", **kw)
-    together, alone_buf = SP.ReplayTensors("Connect4", cap, "cuda"), SP.ReplayTensors("Connect4", cap, "cuda")
+    together, alone_buf = RP.ReplayTensors("Connect4", cap, "cuda"), RP.ReplayTensors("Connect4", cap, "cuda")
     sp.step(plies)
     info = sp.export(together)
     sp.synchronize()

@@ -36,12 +36,6 @@ def env():
     net = az_net.Connect4Net(device="cuda").eval()
     az_net.load_reference_weights(net, {k: wts[k] for k in wts.files})
     L = glue()
-    vp, i64 = C.c_void_p, C.c_int64
-    # (other test modules declare these two with a structure class of their own: declared again here, for this one)
-    L.az_nn_stem_folded_positions.argtypes = [C.POINTER(Positions), vp, vp, vp, i64, vp, vp, vp]
-    L.az_nn_model_forward_positions.argtypes = [vp, C.POINTER(Positions), vp, vp, vp, vp, i64, vp, vp, vp, C.c_uint64, vp]
-    L.az_nn_model_profile.argtypes = [C.c_int]
-    L.az_nn_model_profile_read_kernels.argtypes = [C.POINTER(C.c_double * 4), C.POINTER(C.c_int64 * 4)]
     return dict(torch=torch, net=net, FastNet=FastConnect4Net, Positions=Positions, L=L)
 
 

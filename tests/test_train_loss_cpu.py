@@ -182,7 +182,7 @@ def test_config_struct_mirror_has_the_size_and_fields_the_header_asserts(TL):
     for name in ("az_train_dev_loss", "az_train_dev_loss_grad"):
         assert re.search(r"\bint\s+%s\(" % name, hdr), name
     assert re.search(r"\bint64_t\s+az_train_loss_workspace_bytes\(", hdr)
-    L = TL.train_lib()
+    L = TL.lib()
     assert L.az_train_loss_workspace_bytes(0, 128) > 0 and L.az_train_loss_workspace_bytes(1, 192) > 0
     assert L.az_train_loss_workspace_bytes(2, 128) == -1 and L.az_train_loss_workspace_bytes(0, 0) == -1
     assert L.az_train_loss_workspace_bytes(0, 2 ** 30 + 1) == -1 and L.az_train_loss_workspace_bytes(1, 2 ** 30) > 0

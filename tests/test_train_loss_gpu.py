@@ -51,8 +51,8 @@ def env():
     ge.build()
     if PKG not in sys.path:
         sys.path.insert(0, PKG)
-    from src import fused, selfplay, train_loss
-    return dict(torch=torch, F=fused, SP=selfplay, TL=train_loss, L=train_loss.train_lib())
+    from src import fused, replay, train_loss
+    return dict(torch=torch, F=fused, RP=replay, TL=train_loss, L=fused.lib())
 
 
 # ---------------------------------------------------------------------------------------- inputs and the reference
@@ -145,7 +145,7 @@ def raw_route(env, key, batch, heads, cfg, upstream=(1.0, 1.0, 1.0)):
     slabs = {k: torch.full((GUARD + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda") for k, n in nbytes.items()}
     at = {k: s.data_ptr() + GUARD for k, s in slabs.items()}
     assert all(p % 16 == 0 for p in at.values())
-    c_batch = env["SP"].ReplayBatchC(*(t.data_ptr() for t in d_batch))
+    c_batch = env["RP"].ReplayBatchC(*(t.data_ptr() for t in d_batch))
     c_heads = TL.TrainHeadsC(*(h.data_ptr() for h in d_heads))
     c_cfg = TL.config_c(TL.LossConfig(**cfg), R.OFFSET[key])
     c_out = TL.TrainLossOutC(at["losses"], at["counts"], at["workspace"])
@@ -302,9 +302,9 @@ def test_through_autograd_from_a_small_head(env):
 def test_ring_to_gradients_on_one_stream(env):
     """A ring filled from fixture G15 -> ReplayBatches -> a three-head net -> training_loss -> backward, every batch of
     the sample enqueued without a wait in between; the kernel routes against the torch routes."""
-    torch, SP, TL = env["torch"], env["SP"], env["TL"]
+    torch, RP, TL = env["torch"], env["RP"], env["TL"]
     cfg = TL.LossConfig(**R.CONFIGS["b"])
-    buf = golden_buffer(SP, "c4", "cuda")
+    buf = golden_buffer(RP, "c4", "cuda")
     idx, _ = golden_rows("c4")
     net, exact_net = tiny_net(torch).cuda(), tiny_net(torch).double()
     side = torch.cuda.Stream()

@@ -81,10 +81,10 @@ def summary(v, digits=3):
             "all": [round(x, digits) for x in v]}
 
 
-def fill_ring(torch, SP, game, capacity, dev, seed):
+def fill_ring(torch, RP, game, capacity, dev, seed):
     """A full ring with the value ranges self-play leaves, from a seeded device generator."""
     A, cells, _S = GEOMETRY[game]
-    buf = SP.SampledReplayTensors(game, capacity, dev)
+    buf = RP.SampledReplayTensors(game, capacity, dev)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
     z = dict(device=dev, generator=gen)
@@ -132,12 +132,12 @@ def main():
     assert 0 < args.sample <= args.capacity and args.batch > 0 and args.epochs > 0 and args.updates > 0
 
     import torch
-    from src import selfplay as SP
+    from src import abi, replay as RP
     assert torch.cuda.is_available(), "measure_batch needs a GPU"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     t0 = time.perf_counter()
-    buf = fill_ring(torch, SP, game, args.capacity, dev, 1234 + args.seed)
+    buf = fill_ring(torch, RP, game, args.capacity, dev, 1234 + args.seed)
     torch.cuda.synchronize()
     log("%s ring of %d rows filled in %.2f s" % (game, args.capacity, time.perf_counter() - t0))
     # the sample size the learner would draw from this ring is the reference's rule; the tool pins it to --sample
@@ -150,9 +150,8 @@ def main():
         for u in range(args.updates):
             key = call * args.updates + u
             idx = torch.empty(args.sample, dtype=torch.int64, device=dev)
-            SP.F.check(SP.selfplay_lib().az_replay_dev_sample_indices(args.seed, key, len(buf), idx.data_ptr(), args.sample,
-                                                                      SP.F._stream()))
-            loader = SP.ReplayBatches(buf, idx, args.batch, route=route, shuffle=True, seed=key)
+            abi.check(abi.lib().az_replay_dev_sample_indices(args.seed, key, len(buf), idx.data_ptr(), args.sample, abi._stream()))
+            loader = RP.ReplayBatches(buf, idx, args.batch, route=route, shuffle=True, seed=key)
             for _ in range(args.epochs):
                 for batch in loader:
                     n_batches += 1

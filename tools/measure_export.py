@@ -97,7 +97,7 @@ def main():
     assert args.reps >= 3, "at least three repetitions per route"
 
     import torch
-    from src import selfplay as SP
+    from src import replay as RP, selfplay as SP
     assert torch.cuda.is_available(), "measure_export needs a GPU"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -112,8 +112,8 @@ def main():
     if args.othello:
         kw.update(game="Othello", score_utility_factor=0.15, score_scale=8.0)
     sp = SP.NativeSelfPlay(net, args.games, **kw)
-    on_dev = SP.ReplayTensors(game, args.capacity, dev)
-    on_host = SP.ReplayTensors(game, args.capacity, "cpu")
+    on_dev = RP.ReplayTensors(game, args.capacity, dev)
+    on_host = RP.ReplayTensors(game, args.capacity, "cpu")
 
     def route_export():
         return int(sp.export(on_dev)["length"].sum())
@@ -126,7 +126,7 @@ def main():
         cap = args.capacity
         lo, hi = at % cap, (at + min(n, cap)) % cap
         spans = [(lo, hi)] if lo < hi else [(lo, cap), (0, hi)]
-        for name in SP.ReplayTensors.TENSORS:
+        for name in RP.ReplayTensors.TENSORS:
             for a, b in spans:
                 if b > a:
                     getattr(on_dev, name)[a:b].copy_(getattr(on_host, name)[a:b])

@@ -20,8 +20,6 @@ from src.fast_net import FastConnect4Net, Positions, glue  # noqa: E402
 from src.az_net import Connect4Net  # noqa: E402
 
 L = glue()
-L.az_nn_debug.argtypes = [C.c_int]
-L.az_nn_stem_folded_positions.argtypes = [C.POINTER(Positions)] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3
 
 
 def random_positions(B, gen):
@@ -160,7 +158,6 @@ def heads():
 
 
 feat = (torch.rand(B, 3, 6, 7, device=dev) > 0.5).float()
-L.az_nn_stem_embed.argtypes = [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3
 
 
 def stem_embed():
@@ -223,7 +220,6 @@ def stem_conv_report():
     stem_conv()
     torch.cuda.synchronize()
     buf = np.zeros(2048 * 8, dtype=np.uint64)
-    L.az_nn_conv_profile.argtypes = [C.c_void_p, C.c_int]
     L.az_nn_conv_profile(buf.ctypes.data, buf.size)
     L.az_nn_debug(0)
     ph = buf.reshape(2048, 8)[:, :7].astype(np.float64)
@@ -251,7 +247,6 @@ else:
     print("conv with phase stamps      %7.1f us" % timed(conv))
     import numpy as np
     buf = np.zeros(2048 * 8, dtype=np.uint64)
-    L.az_nn_conv_profile.argtypes = [C.c_void_p, C.c_int]
     L.az_nn_conv_profile(buf.ctypes.data, buf.size)
     ph = buf.reshape(2048, 8)[:, :6].astype(np.float64)
     names = ("P1 norm->img", "barrier 1", "MFMA+epilogue", "wait staged tile", "barrier 2", "P3 store")

@@ -12,7 +12,6 @@ from src.fast_net import glue  # noqa: E402
 from src.fast_othello import pack_conv_weight  # noqa: E402
 
 L = glue()
-L.az_nn_othello_conv.argtypes = [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 x = torch.randn(B, 10, 10, 256, device="cuda").to(torch.bfloat16)
 w = pack_conv_weight(torch.randn(256, 256, 3, 3, device="cuda") * 0.03)

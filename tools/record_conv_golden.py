@@ -188,8 +188,6 @@ def run_group(group):
     from src.fast_net import Positions, glue
     L = glue()
     assert L is not None, "no library in " + PKG
-    vp, i64 = C.c_void_p, C.c_int64
-    L.az_nn_stem_embed_positions.argtypes = [C.POINTER(Positions), vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
     return {n: run_case(torch, L, Positions, n) for n in case_names(group)}
 
 

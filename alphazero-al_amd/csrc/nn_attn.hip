@@ -9,9 +9,9 @@
 // 196-wide GEMM + split/normalise + SDPA + gate + out-projection (six kernels, 1.8 ms per 32768-leaf iteration in
 // the first profile).
 //
-// Three workgroups of four wavefronts per CU (three wavefronts per SIMD): 158 registers, the per-sample constants and
-// the gates in LDS (37 KB per workgroup).  k_attn_block<true> is the earlier gate arrangement (attn::attn_sample's
-// GATE4; 46 KB), launched when az_nn_debug bit 8 is set: same bytes, for A/B runs and as the tests' oracle.
+// Three workgroups of four wavefronts per CU (three wavefronts per SIMD): 167 registers, the per-sample constants and
+// the gates in LDS (37 KB per workgroup).  k_attn_block<true> is the same kernel with rsqrtf() for its reciprocal square
+// roots (attn::attn_sample's GUARDED), launched when eps < FLT_MIN.
 #include <cfloat>
 
 #include "az_nn.h"
@@ -21,7 +21,7 @@ namespace {
 
 using namespace attn;
 
-template <bool GATE4>
+template <bool GUARDED>
 __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg,
                                                        const uint16_t *qn_w, const uint16_t *kn_w, const uint16_t *o_w,
                                                        uint16_t *y, int64_t B, float eps, const int64_t *batch_dev)
@@ -33,10 +33,10 @@ __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const 
 
     __shared__ V8 s_w32[W32_N];
     __shared__ V4 s_w16[W16_N];
-    __shared__ f32x4 s_gate[GATE4 ? 4 * GATE_N : GATE_N];   // [wave]: GATE_N floats (GATE4: f32x4)
+    __shared__ __align__(16) float s_gate[4 * GATE_N];     // [wave][GATE_N]
     __shared__ float s_pw[C];
     __shared__ float s_qk[2 * HD];
-    stage_weights<GATE4>(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
+    stage_weights(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
     __syncthreads();
     const bool bounded = scores_bounded(s_qk, l4);
 
@@ -44,8 +44,7 @@ __global__ void __launch_bounds__(256, 3) k_attn_block(const uint16_t *x, const 
     for (int64_t b = static_cast<int64_t>(blockIdx.x) * 4 + wave; b < B; b += stride) {
         const uint16_t *xs = x + b * (CELLS * C);
         f32x4 out[4][TT];
-        attn_sample<GATE4>(xs, s_w32, s_w16, s_pw, s_qk, s_gate + wave * (GATE4 ? GATE_N : GATE_N / 4), bounded, eps, lane, l15, l4,
-                           out);
+        attn_sample<GUARDED>(xs, s_w32, s_w16, s_pw, s_qk, s_gate + wave * GATE_N, bounded, eps, lane, l15, l4, out);
 
         // ---- y = out + x : lane holds 4 consecutive output channels of token qt*16 + lane&15
         uint16_t *ys = y + b * (CELLS * C);
@@ -80,7 +79,7 @@ int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, c
     const unsigned cap = 256u * 3u * 2u;       // two rounds of resident workgroups
     const unsigned grid = static_cast<unsigned>(wgs < cap ? wgs : cap);
     // the default form takes its reciprocal square roots bare (rsq_normal): a smaller eps goes to the form that guards them
-    const auto kern = ((az_nn_debug_flags() & AZ_NN_DEBUG_LEGACY_TAIL) || !(eps >= FLT_MIN)) ? k_attn_block<true> : k_attn_block<false>;
+    const auto kern = !(eps >= FLT_MIN) ? k_attn_block<true> : k_attn_block<false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(prenorm_w),
                        static_cast<const uint16_t *>(qkvg_w), static_cast<const uint16_t *>(q_norm_w),

@@ -23,11 +23,7 @@
 //
 // The gate tile has 4 distinct rows (one per head) on a 16-row MFMA.  Staged as row 4 g + r = head g, lane group g
 // ends up with head g of its token in every accumulator register: it computes ONE sigmoid and stores one float, and
-// the head loop reads gate (token tile, head h, token l15) from the slot lane group h wrote.  GATE4 = true is the
-// earlier arrangement (row 4 g + r = head r: every lane computes all four sigmoids and reads back its own), kept as
-// a second instantiation for A/B runs; the dot products, and so the bits, are the same.  GATE4 also keeps the
-// instruction sequences the default form shortened - rsqrtf() with its denormal-range guard, one col_sum per value, the
-// query tiles one at a time - where the default takes rsq_normal(), col_sum2 and the three tiles' scores side by side.
+// the head loop reads gate (token tile, head h, token l15) from the slot lane group h wrote.
 #pragma once
 
 #include "nn_common.h"
@@ -39,14 +35,13 @@ namespace attn {
 constexpr int CELLS = 42, C = 64, HEADS = 4, HD = 16, TT = 3;     // 3 token tiles of 16
 constexpr int W32_N = (3 * HEADS * 2 + 2) * 64;                    // V8: wq, wk, wv [h][s], wg [s]
 constexpr int W16_N = 4 * HEADS * 64;                              // V4: wo [ot][h]
-constexpr int GATE_N = TT * 64;                                    // per wavefront: float [token tile][head][token] (GATE4: f32x4 [token tile][lane])
+constexpr int GATE_N = TT * 64;                                    // per wavefront: float [token tile][head][token]
 constexpr float QSCALE = 0.25f * 1.44269504f;     // 1/sqrt(16) of the scores and log2(e) of their softmax ride on q
 
 // The weights, staged once per workgroup into LDS in exactly the order the lanes read them (fragment f, lane l ->
 // 16 or 8 contiguous bytes at f*64+l), so every operand fetch is one conflict-free ds_read.  The caller's
 // __syncthreads() follows.  qkvg: (196, 64) row-major [out][in]: rows 0-63 Q, 64-127 K, 128-191 V, 192-195 gate.
 // s_pw [64]: pre-norm weight; s_qk [32]: q norm weight x QSCALE, k norm weight.
-template <bool GATE4 = false>
 __device__ __forceinline__ void stage_weights(const uint16_t *qkvg, const uint16_t *o_w, const uint16_t *pre_w,
                                               const uint16_t *qn_w, const uint16_t *kn_w, V8 *s_w32, V4 *s_w16, float *s_pw,
                                               float *s_qk)
@@ -59,8 +54,8 @@ __device__ __forceinline__ void stage_weights(const uint16_t *qkvg, const uint16
             v = *reinterpret_cast<const V8 *>(qkvg + (part * C + h * HD + ll15) * C + 32 * sk + 8 * ll4);
         } else {
             // the 4 gate rows over the tile's 16 rows: row 4 g + r = head g, so every accumulator register of lane
-            // group g is head g of the lane's token (GATE4: head r, the same four in every lane group)
-            v = *reinterpret_cast<const V8 *>(qkvg + (3 * C + (GATE4 ? ll15 & 3 : ll15 >> 2)) * C + 32 * (f & 1) + 8 * ll4);
+            // group g is head g of the lane's token
+            v = *reinterpret_cast<const V8 *>(qkvg + (3 * C + (ll15 >> 2)) * C + 32 * (f & 1) + 8 * ll4);
         }
         s_w32[i] = v;
     }
@@ -85,29 +80,16 @@ __device__ __forceinline__ bool scores_bounded(const float *s_qk, int l4)
         mq = fmaxf(mq, fabsf(s_qk[4 * l4 + r]));
         mk = fmaxf(mk, fabsf(s_qk[HD + 4 * l4 + r]));
     }
-    return 16.0f * col_max(mq) * col_max(mk) < 100.0f;
-}
-// The same with both maxima through one set of swaps (col_max2), for the default form of k_attn_heads.  k_attn_block
-// stays on scores_bounded(): with this one in its default form the compiler schedules the prologue of the OTHER
-// instantiation in the same file differently, and that one is kept as it compiles today.
-__device__ __forceinline__ bool scores_bounded_paired(const float *s_qk, int l4)
-{
-    float mq = 0.0f, mk = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        mq = fmaxf(mq, fabsf(s_qk[4 * l4 + r]));
-        mk = fmaxf(mk, fabsf(s_qk[HD + 4 * l4 + r]));
-    }
     col_max2(mq, mk);
     return 16.0f * mq * mk < 100.0f;
 }
 
 // One sample: xs = its 42 x 64 residual-stream rows (bf16), out = out^T in the MFMA C layout (lane holds channels
-// 16 ot + 4 l4 + r of token qt*16 + l15).  s_gate: this wavefront's gate store (GATE_N floats; GATE4: GATE_N f32x4),
-// written and read here.
-template <bool GATE4 = false>
+// 16 ot + 4 l4 + r of token qt*16 + l15).  s_gate: this wavefront's gate store (GATE_N floats), written and read here.
+// GUARDED: the reciprocal square roots as rsqrtf(), which takes any eps, where the default takes rsq_normal().
+template <bool GUARDED = false>
 __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32, const V4 *s_w16, const float *s_pw,
-                                            const float *s_qk, f32x4 *s_gate, bool bounded, float eps, int lane, int l15,
+                                            const float *s_qk, float *s_gate, bool bounded, float eps, int lane, int l15,
                                             int l4, f32x4 (&out)[4][TT])
 {
     // (the head loop below is not unrolled and indexes these by the runtime head number, so the
@@ -120,25 +102,22 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
     };
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     // 1 / sqrt of an RMS statistic, sum / n + eps.  The default form is launched with eps >= FLT_MIN only (the host
-    // entry points see to it), which is rsq_normal()'s precondition; GATE4 keeps rsqrtf() and takes any eps.
+    // entry points see to it), which is rsq_normal()'s precondition.
     auto rsq = [](float v) {
-        if constexpr (GATE4) return rsqrtf(v);
+        if constexpr (GUARDED) return rsqrtf(v);
         else return rsq_normal(v);
     };
 
     // ---- H = RMSNorm(x) * w, as MFMA fragments (token = tile*16 + lane&15, 8 channels per k-step)
     // The sample's six row vectors are requested together and without a branch: a padding token reads row 41 and is
     // zeroed once the vector is in, so the first tile's statistics start when its two vectors have arrived while the
-    // later tiles' are in flight - one memory latency per sample.  GATE4 keeps the earlier order (tile 2 behind an
-    // exec-mask branch, requested after tiles 0 and 1 have arrived): the same bytes, the oracle of this one.
+    // later tiles' are in flight - one memory latency per sample.
     V8 xv[TT][2];
-    if constexpr (!GATE4) {
 #pragma unroll
-        for (int tt = 0; tt < TT; ++tt) {
-            const int tok = tt * 16 + l15, row = tok < CELLS ? tok : CELLS - 1;
+    for (int tt = 0; tt < TT; ++tt) {
+        const int tok = tt * 16 + l15, row = tok < CELLS ? tok : CELLS - 1;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) xv[tt][s] = *reinterpret_cast<const V8 *>(xs + row * C + 32 * s + 8 * l4);
-        }
+        for (int s = 0; s < 2; ++s) xv[tt][s] = *reinterpret_cast<const V8 *>(xs + row * C + 32 * s + 8 * l4);
     }
     bf16x8 hf[TT][2];
 #pragma unroll
@@ -147,13 +126,9 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
         f32x2 f[2][4], ss2 = {0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            V8 v; v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
-            if constexpr (GATE4) {
-                if (tok < CELLS) v = *reinterpret_cast<const V8 *>(xs + tok * C + 32 * s + 8 * l4);
-            } else {
+            V8 v;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v.w[i] = tok < CELLS ? xv[tt][s].w[i] : 0u;
-            }
+            for (int i = 0; i < 4; ++i) v.w[i] = tok < CELLS ? xv[tt][s].w[i] : 0u;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 f[s][i] = unpack2(v.w[i]);
@@ -173,22 +148,14 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             hf[tt][s] = as_bf16x8(o);
         }
     }
-    // ---- sigmoid gates of every token: lane group l4 holds head l4 (GATE4: register h of every lane is head h)
-    float *s_gate1 = reinterpret_cast<float *>(s_gate);
+    // ---- sigmoid gates of every token: lane group l4 holds head l4
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
         f32x4 g = MFMA32(frag32(24), hf[tt][0], zero);
         g = MFMA32(frag32(25), hf[tt][1], g);
-        if constexpr (GATE4) {
-            f32x4 gs;
-#pragma unroll
-            for (int h = 0; h < HEADS; ++h) gs[h] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[h]));
-            s_gate[tt * 64 + lane] = gs;
-        } else {
-            s_gate1[tt * 64 + lane] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[0]));
-        }
+        s_gate[tt * 64 + lane] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * g[0]));
     }
-    if constexpr (!GATE4) wave_lds_sync();          // a gate is read by the lanes of other lane groups
+    wave_lds_sync();          // a gate is read by the lanes of other lane groups
 
 #pragma unroll
     for (int ot = 0; ot < 4; ++ot)
@@ -211,13 +178,8 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             f32x2 q2[2] = {{q[0], q[1]}, {q[2], q[3]}}, k2[2] = {{k[0], k[1]}, {k[2], k[3]}};
             const f32x2 qq = __builtin_elementwise_fma(q2[1], q2[1], q2[0] * q2[0]);
             const f32x2 kk = __builtin_elementwise_fma(k2[1], k2[1], k2[0] * k2[0]);
-            float qs, ks;
-            if constexpr (GATE4) {
-                qs = col_sum(qq.x + qq.y), ks = col_sum(kk.x + kk.y);
-            } else {
-                qs = qq.x + qq.y, ks = kk.x + kk.y;
-                col_sum2(qs, ks);
-            }
+            float qs = qq.x + qq.y, ks = kk.x + kk.y;
+            col_sum2(qs, ks);
             const float qr = rsq(qs * (1.0f / HD) + eps), kr = rsq(ks * (1.0f / HD) + eps);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
@@ -229,142 +191,79 @@ __device__ __forceinline__ void attn_sample(const uint16_t *xs, const V8 *s_w32,
             kb[tt] = to_s16x4(f32x4{k2[0].x, k2[0].y, k2[1].x, k2[1].y});
             vb[tt] = to_s16x4(v);
         }
-        if constexpr (GATE4) {
-            // the earlier form, one query tile at a time, as it stood: the oracle of the one below
+        // E^T = exp2(S^T - max) of query tile qt against every key, as the bf16 B operands of the next product (S^T tile
+        // rows = keys, column = query lane&15); returns this lane's share of the column's softmax denominator
+        auto scores = [&](int qt, s16x4 (&pb)[TT]) {
+            f32x4 st[TT];
+            f32x2 den2 = {0.0f, 0.0f};
+            if (bounded) {
+                // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
+                // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
 #pragma unroll
-            for (int qt = 0; qt < TT; ++qt) {
-                // S^T tile rows = keys, column = query lane&15
-                f32x4 st[TT];
-                float den;
-                if (bounded) {
-                    // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
-                    // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
-                    f32x2 den2 = {0.0f, 0.0f};
+                for (int kt = 0; kt < TT; ++kt) {
+                    st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
 #pragma unroll
-                    for (int kt = 0; kt < TT; ++kt) {
-                        st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
-#pragma unroll
-                        for (int r = 0; r < 4; r += 2) {
-                            const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
-                            st[kt][r] = e.x;
-                            st[kt][r + 1] = e.y;
-                            den2 += e;
-                        }
+                    for (int r = 0; r < 4; r += 2) {
+                        const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
+                        st[kt][r] = e.x;
+                        st[kt][r + 1] = e.y;
+                        den2 += e;
                     }
-                    den = col_sum(den2.x + den2.y) - static_cast<float>(TT * 16 - CELLS);
-                } else {
-                    float m = -INFINITY;
-#pragma unroll
-                    for (int kt = 0; kt < TT; ++kt) {
-                        st[kt] = MFMA16(kb[kt], qb[qt], zero);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
-                            m = fmaxf(m, st[kt][r]);
-                        }
-                    }
-                    m = col_max(m);
-                    f32x2 den2 = {0.0f, 0.0f};
-                    const f32x2 nm = {-m, -m};
-#pragma unroll
-                    for (int kt = 0; kt < TT; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; r += 2) {
-                            const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
-                            const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
-                            st[kt][r] = e.x;
-                            st[kt][r + 1] = e.y;
-                            den2 += e;
-                        }
-                    den = col_sum(den2.x + den2.y);
                 }
-                // normalise after the product: O^T = (V^T . E^T) / den, one scale per output element
-                const float gq = GATE4 ? reinterpret_cast<const float *>(&s_gate[qt * 64 + lane])[h] : s_gate1[qt * 64 + h * 16 + l15];
-                const float scale = __builtin_amdgcn_rcpf(den) * gq;
-                f32x4 o = zero;                                  // O^T rows = d, column = query
+            } else {
+                float m = -INFINITY;
 #pragma unroll
-                for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], to_s16x4(st[kt]), o);
+                for (int kt = 0; kt < TT; ++kt) {
+                    st[kt] = MFMA16(kb[kt], qb[qt], zero);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] *= scale;
-                const s16x4 ob = to_s16x4(o);
+                    for (int r = 0; r < 4; ++r) {
+                        if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
+                        m = fmaxf(m, st[kt][r]);
+                    }
+                }
+                m = col_max(m);
+                const f32x2 nm = {-m, -m};
 #pragma unroll
-                for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
+                for (int kt = 0; kt < TT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; r += 2) {
+                        const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
+                        const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
+                        st[kt][r] = e.x;
+                        st[kt][r + 1] = e.y;
+                        den2 += e;
+                    }
             }
-        } else {
-            // E^T = exp2(S^T - max) of query tile qt against every key, as the bf16 B operands of the next product (S^T tile
-            // rows = keys, column = query lane&15); returns this lane's share of the column's softmax denominator
-            auto scores = [&](int qt, s16x4 (&pb)[TT]) {
-                f32x4 st[TT];
-                f32x2 den2 = {0.0f, 0.0f};
-                if (bounded) {
-                    // No running maximum.  The six padding keys have k = 0, i.e. score 0 and weight exp2(0) = 1 exactly,
-                    // and their V rows are 0: they add nothing to the product and exactly 6 to the denominator.
 #pragma unroll
-                    for (int kt = 0; kt < TT; ++kt) {
-                        st[kt] = MFMA16(kb[kt], qb[qt], zero);      // already in log2 units (QSCALE)
+            for (int kt = 0; kt < TT; ++kt) pb[kt] = to_s16x4(st[kt]);
+            return den2.x + den2.y;
+        };
+        // O^T = (V^T . E^T) / den, gated, and its contribution to the output projection.  den: the column's sum of
+        // scores()' shares; the bounded form counted the six padding keys into it.
+        auto attend = [&](int qt, const s16x4 (&pb)[TT], float den) {
+            if (bounded) den -= static_cast<float>(TT * 16 - CELLS);
+            // normalise after the product: one scale per output element
+            const float scale = __builtin_amdgcn_rcpf(den) * s_gate[qt * 64 + h * 16 + l15];
+            f32x4 o = zero;                                  // O^T rows = d, column = query
 #pragma unroll
-                        for (int r = 0; r < 4; r += 2) {
-                            const f32x2 e = {__builtin_amdgcn_exp2f(st[kt][r]), __builtin_amdgcn_exp2f(st[kt][r + 1])};
-                            st[kt][r] = e.x;
-                            st[kt][r + 1] = e.y;
-                            den2 += e;
-                        }
-                    }
-                } else {
-                    float m = -INFINITY;
+            for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], pb[kt], o);
 #pragma unroll
-                    for (int kt = 0; kt < TT; ++kt) {
-                        st[kt] = MFMA16(kb[kt], qb[qt], zero);
+            for (int r = 0; r < 4; ++r) o[r] *= scale;
+            const s16x4 ob = to_s16x4(o);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if (kt == TT - 1 && kt * 16 + 4 * l4 + r >= CELLS) st[kt][r] = -INFINITY;   // padding keys
-                            m = fmaxf(m, st[kt][r]);
-                        }
-                    }
-                    m = col_max(m);
-                    const f32x2 nm = {-m, -m};
+            for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
+        };
+        // the three query tiles' denominators are independent: tiles 0 and 1 share one set of swaps, and the
+        // tiles' exp2 / add chains stand next to each other for the scheduler to interleave
+        static_assert(TT == 3, "denominators paired as (0, 1), 2");
+        s16x4 pb[TT][TT];
+        float den[TT];
 #pragma unroll
-                    for (int kt = 0; kt < TT; ++kt)
+        for (int qt = 0; qt < TT; ++qt) den[qt] = scores(qt, pb[qt]);
+        col_sum2(den[0], den[1]);
+        den[2] = col_sum(den[2]);
 #pragma unroll
-                        for (int r = 0; r < 4; r += 2) {
-                            const f32x2 d = f32x2{st[kt][r], st[kt][r + 1]} + nm;
-                            const f32x2 e = {__builtin_amdgcn_exp2f(d.x), __builtin_amdgcn_exp2f(d.y)};
-                            st[kt][r] = e.x;
-                            st[kt][r + 1] = e.y;
-                            den2 += e;
-                        }
-                }
-#pragma unroll
-                for (int kt = 0; kt < TT; ++kt) pb[kt] = to_s16x4(st[kt]);
-                return den2.x + den2.y;
-            };
-            // O^T = (V^T . E^T) / den, gated, and its contribution to the output projection.  den: the column's sum of
-            // scores()' shares; the bounded form counted the six padding keys into it.
-            auto attend = [&](int qt, const s16x4 (&pb)[TT], float den) {
-                if (bounded) den -= static_cast<float>(TT * 16 - CELLS);
-                // normalise after the product: one scale per output element
-                const float scale = __builtin_amdgcn_rcpf(den) * s_gate1[qt * 64 + h * 16 + l15];
-                f32x4 o = zero;                                  // O^T rows = d, column = query
-#pragma unroll
-                for (int kt = 0; kt < TT; ++kt) o = MFMA16(vb[kt], pb[kt], o);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] *= scale;
-                const s16x4 ob = to_s16x4(o);
-#pragma unroll
-                for (int ot = 0; ot < 4; ++ot) out[ot][qt] = MFMA16(frag16(ot * HEADS + h), ob, out[ot][qt]);
-            };
-            // the three query tiles' denominators are independent: tiles 0 and 1 share one set of swaps, and the
-            // tiles' exp2 / add chains stand next to each other for the scheduler to interleave
-            static_assert(TT == 3, "denominators paired as (0, 1), 2");
-            s16x4 pb[TT][TT];
-            float den[TT];
-#pragma unroll
-            for (int qt = 0; qt < TT; ++qt) den[qt] = scores(qt, pb[qt]);
-            col_sum2(den[0], den[1]);
-            den[2] = col_sum(den[2]);
-#pragma unroll
-            for (int qt = 0; qt < TT; ++qt) attend(qt, pb[qt], den[qt]);
-        }
+        for (int qt = 0; qt < TT; ++qt) attend(qt, pb[qt], den[qt]);
     }
 }
 

@@ -18,10 +18,8 @@
 // tail per wavefront where the per-pair form ran four or five with 2 live columns of 16.  The value head's 18 A
 // fragments are read from the weights (L2) in that one pass; their 18 KB of LDS hold the mean slots instead.
 //
-// LEGACY = true is the earlier form (value head once per pair, in columns 7 and 15 next to the policy columns; gates
-// as attn::attn_sample's GATE4; rsqrtf() and one column reduction per value where the default form takes a bare
-// v_rsq_f32 and reduces in pairs), launched when az_nn_debug bit 8 is set or eps < FLT_MIN: same bytes, for A/B runs and
-// as the tests' oracle.
+// k_attn_heads<true> (GUARDED) is the same kernel with rsqrtf() for every reciprocal square root where the default
+// takes a bare v_rsq_f32 (rsq_normal), launched when eps < FLT_MIN.
 //
 // Rounding points are those of k_attn_block followed by k_heads: results differ from the two launches only
 // through f32 summation order (token mean, RMS statistics) - the two token passes are the only code not shared.
@@ -44,36 +42,27 @@ constexpr int WPB = 12;         // wavefronts per workgroup: one workgroup per C
 constexpr int VS = 64;          // bf16 row stride of the B-operand buffer
 
 // dynamic LDS layout (bytes)
-template <bool LEGACY>
-struct Lds {
-    static constexpr int A_FRAGS = LEGACY ? 26 : 8;                  // heads' A fragments kept in LDS: all, or the policy's
-    static constexpr int MEAN_B = LEGACY ? 2 * C * 4 : 16 * C * 2;   // per wave: float [2][64] means of the pair, or bf16 [16][64] slots
-    static constexpr int L_W32 = 0;                                 // V8 [attn::W32_N]
-    static constexpr int L_W16 = L_W32 + attn::W32_N * 16;          // V4 [attn::W16_N]
-    static constexpr int L_A = L_W16 + attn::W16_N * 8;             // V8 [A_FRAGS * 64]
-    static constexpr int L_C = L_A + A_FRAGS * 64 * 16;             // float [K_N][64]
-    static constexpr int L_PW = L_C + K_N * C * 4;                  // float [64]: attention pre-norm weight
-    static constexpr int L_QK = L_PW + C * 4;                       // float [32]: q norm weight x QSCALE, k norm weight
-    static constexpr int L_PN = L_QK + 2 * attn::HD * 4;            // per wave: u16 [42*64] normalised tokens | the attention's gates
-    static constexpr int L_VEC = L_PN + WPB * CELLS * C * 2;        // per wave: u16 [16*VS] B operand, row n = column n of V^T
-    static constexpr int L_SCORE = L_VEC + WPB * 16 * VS * 2;       // per wave: float [48] row-gate scores, then weights
-    static constexpr int L_MEAN = L_SCORE + WPB * 48 * 4;           // per wave: MEAN_B
-    static constexpr int L_TOTAL = L_MEAN + WPB * MEAN_B;
-    static_assert(L_TOTAL <= 160 * 1024, "LDS of one CU");
-};
-static_assert(CELLS * C * 2 >= attn::GATE_N * 16, "the gate store fits in the token image");
-static_assert(Lds<true>::L_TOTAL == Lds<false>::L_TOTAL, "one dynamic-LDS size for both forms");
-constexpr int L_TOTAL = Lds<false>::L_TOTAL;
+constexpr int A_FRAGS = 8;                                       // heads' A fragments kept in LDS: the policy's
+constexpr int L_W32 = 0;                                         // V8 [attn::W32_N]
+constexpr int L_W16 = L_W32 + attn::W32_N * 16;                  // V4 [attn::W16_N]
+constexpr int L_A = L_W16 + attn::W16_N * 8;                     // V8 [A_FRAGS * 64]
+constexpr int L_C = L_A + A_FRAGS * 64 * 16;                     // float [K_N][64]
+constexpr int L_PW = L_C + K_N * C * 4;                          // float [64]: attention pre-norm weight
+constexpr int L_QK = L_PW + C * 4;                               // float [32]: q norm weight x QSCALE, k norm weight
+constexpr int L_PN = L_QK + 2 * attn::HD * 4;                    // per wave: u16 [42*64] normalised tokens | the attention's gates
+constexpr int L_VEC = L_PN + WPB * CELLS * C * 2;                // per wave: u16 [16*VS] B operand, row n = column n of V^T
+constexpr int L_SCORE = L_VEC + WPB * 16 * VS * 2;               // per wave: float [48] row-gate scores, then weights
+constexpr int L_SLOT = L_SCORE + WPB * 48 * 4;                   // per wave: bf16 [16][64] token means awaiting their value tail
+constexpr int L_TOTAL = L_SLOT + WPB * 16 * C * 2;
+static_assert(L_TOTAL <= 160 * 1024, "LDS of one CU");
+static_assert(CELLS * C * 2 >= attn::GATE_N * 4, "the gate store fits in the token image");
 
-template <bool LEGACY>
+template <bool GUARDED>
 __global__ void __launch_bounds__(64 * WPB, 1)
 k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, const uint16_t *qn_w, const uint16_t *kn_w,
              const uint16_t *o_w, az_nn_heads_weights w, const uint8_t *mask, float *probs, float *wdl, float *moves_left,
              int64_t B, float eps, const int32_t *scatter, const int64_t *batch_dev)
 {
-    using L = Lds<LEGACY>;
-    constexpr int L_W32 = L::L_W32, L_W16 = L::L_W16, L_A = L::L_A, L_C = L::L_C, L_PW = L::L_PW, L_QK = L::L_QK, L_PN = L::L_PN,
-                  L_VEC = L::L_VEC, L_SCORE = L::L_SCORE, L_MEAN = L::L_MEAN;
     const int64_t rows_total = B;                 // rows of mask / outputs: a compact list may name any of them
     if (batch_dev != nullptr && *batch_dev < B) B = *batch_dev;
     extern __shared__ __align__(16) uint8_t smem[];
@@ -94,15 +83,14 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
     float *s_pw = reinterpret_cast<float *>(smem + L_PW);
     float *s_qk = reinterpret_cast<float *>(smem + L_QK);
     uint16_t *s_pn = reinterpret_cast<uint16_t *>(smem + L_PN + wave * CELLS * C * 2);
-    f32x4 *s_gate = reinterpret_cast<f32x4 *>(smem + L_PN + wave * CELLS * C * 2);      // [token tile][lane], attention only
+    float *s_gate = reinterpret_cast<float *>(smem + L_PN + wave * CELLS * C * 2);      // [token tile][head][token], attention only
     uint16_t *s_vec = reinterpret_cast<uint16_t *>(smem + L_VEC + wave * 16 * VS * 2);
     float *s_score = reinterpret_cast<float *>(smem + L_SCORE + wave * 48 * 4);
-    float *s_mean = reinterpret_cast<float *>(smem + L_MEAN + wave * L::MEAN_B);             // LEGACY
-    uint16_t *s_slot = reinterpret_cast<uint16_t *>(smem + L_MEAN + wave * L::MEAN_B);       // bf16 [16][64]
+    uint16_t *s_slot = reinterpret_cast<uint16_t *>(smem + L_SLOT + wave * 16 * C * 2);
 
     // ---- weights, staged once per workgroup in fragment order
-    attn::stage_weights<LEGACY>(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
-    stage_weights<L::A_FRAGS>(w, s_a, s_c);
+    attn::stage_weights(qkvg, o_w, pre_w, qn_w, kn_w, s_w32, s_w16, s_pw, s_qk);
+    stage_weights<A_FRAGS>(w, s_a, s_c);
     if (threadIdx.x < C) {
         const int i = threadIdx.x;
         const float nw = bf1(static_cast<const uint16_t *>(w.p_norm) + i);
@@ -113,11 +101,11 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
     __syncthreads();
     // 1 / sqrt of an RMS statistic: the default form is launched with eps >= FLT_MIN only (rsq_normal()'s precondition)
     auto rsq = [](float v) {
-        if constexpr (LEGACY) return rsqrtf(v);
+        if constexpr (GUARDED) return rsqrtf(v);
         else return rsq_normal(v);
     };
     auto cvec4 = [&](int which, int ot) { return *reinterpret_cast<const f32x4 *>(&s_c[which][16 * ot + 4 * l4]); };
-    const bool bounded = LEGACY ? attn::scores_bounded(s_qk, l4) : attn::scores_bounded_paired(s_qk, l4);
+    const bool bounded = attn::scores_bounded(s_qk, l4);
 
     // a wavefront's samples: b0, b0 + S, b0 + 2S, ... (S = wavefronts in the grid), taken two at a time.  nslot of them
     // wait for their value tail, in slots 0 .. nslot - 1: samples fbase, fbase + S, ...
@@ -140,25 +128,23 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                 const int64_t bs = hs == 0 ? b0 : b1;
                 if (bs >= B) break;
                 refresh_lane();
-                if constexpr (!LEGACY) {
-                    if (hs == 0) {
-                        const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
-                        if (scatter != nullptr && bc < B) srow = scatter[bc];
-                    }
+                if (hs == 0) {
+                    const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+                    if (scatter != nullptr && bc < B) srow = scatter[bc];
                 }
                 const uint16_t *xs = x + bs * (CELLS * C);
 
                 f32x4 out[4][TT];
-                attn::attn_sample<LEGACY>(xs, s_w32, s_w16, s_pw, s_qk, s_gate, bounded, eps, lane, l15, l4, out);
+                attn::attn_sample<GUARDED>(xs, s_w32, s_w16, s_pw, s_qk, s_gate, bounded, eps, lane, l15, l4, out);
                 // the residual rows the token pass adds, requested one token tile ahead of the tile that consumes them
-                // (a padding token reads row 41 and is zeroed on arrival); LEGACY loads each where it is used
+                // (a padding token reads row 41 and is zeroed on arrival)
                 V4 xq[TT][4];
                 auto request_rows = [&](int qt) {
                     const int tok = qt * 16 + l15, row = tok < CELLS ? tok : CELLS - 1;
 #pragma unroll
                     for (int ot = 0; ot < 4; ++ot) xq[qt][ot] = *reinterpret_cast<const V4 *>(xs + row * C + ot * 16 + 4 * l4);
                 };
-                if constexpr (!LEGACY) request_rows(0);
+                request_rows(0);
                 wave_lds_sync();                     // the gates are read: the token image may overwrite them
 
                 // ======== token pass on y = bf16(x + out): lane = token qt*16 + l15, channels 16 ot + 4 l4 + r ========
@@ -170,21 +156,15 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                     const int tok = qt * 16 + l15;
                     const bool live = tok < CELLS;
                     f32x2 f[4][2], ss2 = {0.0f, 0.0f}, sc2 = {0.0f, 0.0f};
-                    if constexpr (!LEGACY) {
-                        if (qt + 1 < TT) {
-                            request_rows(qt + 1);
-                            asm volatile("" ::: "memory");       // the requests stay ahead of this tile's arithmetic
-                        }
+                    if (qt + 1 < TT) {
+                        request_rows(qt + 1);
+                        asm volatile("" ::: "memory");       // the requests stay ahead of this tile's arithmetic
                     }
 #pragma unroll
                     for (int ot = 0; ot < 4; ++ot) {
-                        V4 xr; xr.w[0] = xr.w[1] = 0;
-                        if constexpr (LEGACY) {
-                            if (live) xr = *reinterpret_cast<const V4 *>(xs + tok * C + ot * 16 + 4 * l4);
-                        } else {
-                            xr.w[0] = live ? xq[qt][ot].w[0] : 0u;
-                            xr.w[1] = live ? xq[qt][ot].w[1] : 0u;
-                        }
+                        V4 xr;
+                        xr.w[0] = live ? xq[qt][ot].w[0] : 0u;
+                        xr.w[1] = live ? xq[qt][ot].w[1] : 0u;
                         const f32x4 ngw = cvec4(K_PNGW, ot);
                         f[ot][0] = unpack2(pack2(out[ot][qt][0] + bf_lo(xr.w[0]), out[ot][qt][1] + bf_hi(xr.w[0])));
                         f[ot][1] = unpack2(pack2(out[ot][qt][2] + bf_lo(xr.w[1]), out[ot][qt][3] + bf_hi(xr.w[1])));
@@ -195,13 +175,8 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                             if (live) msum[ot][j] += f[ot][j];
                         }
                     }
-                    float ss, sc;
-                    if constexpr (LEGACY) {
-                        ss = col_sum(ss2.x + ss2.y), sc = col_sum(sc2.x + sc2.y);
-                    } else {
-                        ss = ss2.x + ss2.y, sc = sc2.x + sc2.y;
-                        col_sum2(ss, sc);
-                    }
+                    float ss = ss2.x + ss2.y, sc = sc2.x + sc2.y;
+                    col_sum2(ss, sc);
                     const float r = rsq(ss * (1.0f / C) + eps);
                     if (live) {
 #pragma unroll
@@ -217,113 +192,77 @@ k_attn_heads(const uint16_t *x, const uint16_t *pre_w, const uint16_t *qkvg, con
                         if (l4 == 0) s_score[tok] = sc * r + w.p_gate_b;
                     }
                 }
-                // ---- token mean (bf16, like the reference's mean of a bf16 tensor): sums over the 16 lanes of a row
-                if constexpr (LEGACY) {
-                    // kept for the residual, and its pool_norm goes to this sample's value column 8 hs + 7
-                    f32x2 g0[4][2], q2 = {0.0f, 0.0f};
+                // ---- token mean (bf16, like the reference's mean of a bf16 tensor): sums over the 16 lanes of a row,
+                // parked in the sample's slot; everything else about the value head waits for the flush
 #pragma unroll
-                    for (int ot = 0; ot < 4; ++ot)
+                for (int ot = 0; ot < 4; ++ot) {
+                    V4 o;
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const f32x2 m = {sum16(msum[ot][j].x), sum16(msum[ot][j].y)};
-                            g0[ot][j] = rbf2(m * f32x2{1.0f / CELLS, 1.0f / CELLS});
-                            q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
-                        }
-                    const float rn = rsqrtf(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
-                    if (l15 == 0) {
-#pragma unroll
-                        for (int ot = 0; ot < 4; ++ot) {
-                            *reinterpret_cast<f32x4 *>(&s_mean[hs * C + 16 * ot + 4 * l4]) = f32x4{g0[ot][0].x, g0[ot][0].y, g0[ot][1].x, g0[ot][1].y};
-                            const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
-                            const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
-                            const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
-                            V4 o;
-                            o.w[0] = pack2(v0.x, v0.y);
-                            o.w[1] = pack2(v1.x, v1.y);
-                            *reinterpret_cast<V4 *>(&s_vec[(8 * hs + 7) * VS + 16 * ot + 4 * l4]) = o;
-                        }
+                    for (int j = 0; j < 2; ++j) {
+                        const f32x2 m = f32x2{sum16_dpp(msum[ot][j].x), sum16_dpp(msum[ot][j].y)} * f32x2{1.0f / CELLS, 1.0f / CELLS};
+                        o.w[j] = pack2(m.x, m.y);
                     }
-                } else {
-                    // parked in the sample's slot; everything else about the value head waits for the flush
-#pragma unroll
-                    for (int ot = 0; ot < 4; ++ot) {
-                        V4 o;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const f32x2 m = f32x2{sum16_dpp(msum[ot][j].x), sum16_dpp(msum[ot][j].y)} * f32x2{1.0f / CELLS, 1.0f / CELLS};
-                            o.w[j] = pack2(m.x, m.y);
-                        }
-                        if (l15 == 0) *reinterpret_cast<V4 *>(&s_slot[(nslot + hs) * C + 16 * ot + 4 * l4]) = o;
-                    }
+                    if (l15 == 0) *reinterpret_cast<V4 *>(&s_slot[(nslot + hs) * C + 16 * ot + 4 * l4]) = o;
                 }
-                if constexpr (!LEGACY) {
-                    if (hs == 0) {
-                        // the rows are in (they came back with the first sample's): the mask bytes of the pair.  The guard
-                        // comes before the address: an index outside the rows is never dereferenced.
-                        const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
-                        int32_t sr = srow;
-                        asm volatile("" : "+v"(sr));
-                        const int64_t b = scatter != nullptr ? sr : bc;
-                        if ((l15 & 7) != 7 && bc < B && b >= 0 && b < rows_total && mask != nullptr) mbyte = mask[b * COLS + (l15 & 7)];
-                    }
+                if (hs == 0) {
+                    // the rows are in (they came back with the first sample's): the mask bytes of the pair.  The guard
+                    // comes before the address: an index outside the rows is never dereferenced.
+                    const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+                    int32_t sr = srow;
+                    asm volatile("" : "+v"(sr));
+                    const int64_t b = scatter != nullptr ? sr : bc;
+                    if ((l15 & 7) != 7 && bc < B && b >= 0 && b < rows_total && mask != nullptr) mbyte = mask[b * COLS + (l15 & 7)];
                 }
                 wave_lds_sync();
                 pool_columns<VS>(s_score, s_pn, s_vec, hs, lane);
             }
 
             refresh_lane();
-            if constexpr (LEGACY) {
-                heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, b0, b1, B, rows_total, scatter, eps,
-                                    lane, l15, l4);
-            } else {
-                const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
-                asm volatile("" : "+v"(srow));
-                const int64_t b = scatter != nullptr ? srow : bc;
-                const bool real = bc < B && b >= 0 && b < rows_total;
-                policy_tail_at<VS>(s_a, s_c, s_vec, w, probs, b, real, real && mask != nullptr && mbyte == 0, lane, l15, l4);
-                nslot += b1 < B ? 2 : 1;
-            }
+            const int64_t bc = (l15 >> 3) == 0 ? b0 : b1;
+            asm volatile("" : "+v"(srow));
+            const int64_t b = scatter != nullptr ? srow : bc;
+            const bool real = bc < B && b >= 0 && b < rows_total;
+            policy_tail_at<VS>(s_a, s_c, s_vec, w, probs, b, real, real && mask != nullptr && mbyte == 0, lane, l15, l4);
+            nslot += b1 < B ? 2 : 1;
         }
-        if constexpr (!LEGACY) {
-            // ======== value tail of the parked samples: the slots are full, or this was the last pair ========
-            if (nslot == 16 || (!more && nslot > 0)) {
-                refresh_lane();
-                // Columns nslot .. 15 are dead: they read slot bytes nobody wrote and carry that garbage (NaN included)
-                // through the MFMAs on purpose - a column never meets another one (MFMA columns are independent, col_sum
-                // stays inside a column) and every store below is guarded by col_live.  Keep it so: no reduction ACROSS
-                // columns belongs in this block.
-                const bool col_live = l15 < nslot;
-                const int64_t bc = fbase + l15 * S;        // column = slot: the slot's sample (< B where the column is live)
-                const int64_t b = (col_live && scatter != nullptr) ? scatter[bc] : bc;
-                const bool real = col_live && b >= 0 && b < rows_total;
-                // pool_norm of the slot's mean -> row l15 of the B operand (s_vec is free: the policy tail has read it)
-                f32x2 g0[4][2], q2 = {0.0f, 0.0f};
+        // ======== value tail of the parked samples: the slots are full, or this was the last pair ========
+        if (nslot == 16 || (!more && nslot > 0)) {
+            refresh_lane();
+            // Columns nslot .. 15 are dead: they read slot bytes nobody wrote and carry that garbage (NaN included)
+            // through the MFMAs on purpose - a column never meets another one (MFMA columns are independent, col_sum
+            // stays inside a column) and every store below is guarded by col_live.  Keep it so: no reduction ACROSS
+            // columns belongs in this block.
+            const bool col_live = l15 < nslot;
+            const int64_t bc = fbase + l15 * S;        // column = slot: the slot's sample (< B where the column is live)
+            const int64_t b = (col_live && scatter != nullptr) ? scatter[bc] : bc;
+            const bool real = col_live && b >= 0 && b < rows_total;
+            // pool_norm of the slot's mean -> row l15 of the B operand (s_vec is free: the policy tail has read it)
+            f32x2 g0[4][2], q2 = {0.0f, 0.0f};
 #pragma unroll
-                for (int ot = 0; ot < 4; ++ot) {
-                    const V4 mv = *reinterpret_cast<const V4 *>(&s_slot[l15 * C + 16 * ot + 4 * l4]);
+            for (int ot = 0; ot < 4; ++ot) {
+                const V4 mv = *reinterpret_cast<const V4 *>(&s_slot[l15 * C + 16 * ot + 4 * l4]);
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        g0[ot][j] = unpack2(mv.w[j]);
-                        q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
-                    }
+                for (int j = 0; j < 2; ++j) {
+                    g0[ot][j] = unpack2(mv.w[j]);
+                    q2 = __builtin_elementwise_fma(g0[ot][j], g0[ot][j], q2);
                 }
-                const float rn = rsq_normal(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
-#pragma unroll
-                for (int ot = 0; ot < 4; ++ot) {
-                    const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
-                    const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
-                    const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
-                    V4 o;
-                    o.w[0] = pack2(v0.x, v0.y);
-                    o.w[1] = pack2(v1.x, v1.y);
-                    *reinterpret_cast<V4 *>(&s_vec[l15 * VS + 16 * ot + 4 * l4]) = o;
-                }
-                wave_lds_sync();
-                auto mean2 = [&](int m, int hh) { return g0[m][hh]; };
-                value_tail<VS, true>(AFragGlobal{w, l15, l4}, s_c, s_vec, mean2, w, wdl, moves_left, col_live, b, real, eps, l15, l4);
-                fbase += nslot * S;
-                nslot = 0;
             }
+            const float rn = rsq(col_sum(q2.x + q2.y) * (1.0f / C) + eps);
+#pragma unroll
+            for (int ot = 0; ot < 4; ++ot) {
+                const f32x4 pw = cvec4(K_DPOOL_NORM, ot);
+                const f32x2 v0 = g0[ot][0] * f32x2{rn, rn} * f32x2{pw[0], pw[1]};
+                const f32x2 v1 = g0[ot][1] * f32x2{rn, rn} * f32x2{pw[2], pw[3]};
+                V4 o;
+                o.w[0] = pack2(v0.x, v0.y);
+                o.w[1] = pack2(v1.x, v1.y);
+                *reinterpret_cast<V4 *>(&s_vec[l15 * VS + 16 * ot + 4 * l4]) = o;
+            }
+            wave_lds_sync();
+            auto mean2 = [&](int m, int hh) { return g0[m][hh]; };
+            value_tail<VS, !GUARDED>(AFragGlobal{w, l15, l4}, s_c, s_vec, mean2, w, wdl, moves_left, col_live, b, real, eps, l15, l4);
+            fbase += nslot * S;
+            nslot = 0;
         }
         if (!more) break;
     }
@@ -340,10 +279,10 @@ extern "C" int az_nn_attn_heads(const void *x, const void *prenorm_w, const void
     static DeviceSetup setup;
     int cus = setup.cus({reinterpret_cast<const void *>(k_attn_heads<false>), reinterpret_cast<const void *>(k_attn_heads<true>)}, L_TOTAL);
     if (cus == 0) return 2;
-    // az_nn_debug: bit 8 the earlier form, bits 16-27 a cap on the grid (tests: many samples per wavefront)
-    const int dbg = az_nn_debug_flags(), cap = (dbg >> 16) & 0xfff;
+    // az_nn_debug: bits 16-27 a cap on the grid (tests: many samples per wavefront)
+    const int cap = (az_nn_debug_flags() >> 16) & 0xfff;
     // the default form takes its reciprocal square roots bare (rsq_normal): a smaller eps goes to the form that guards them
-    const auto kern = ((dbg & AZ_NN_DEBUG_LEGACY_TAIL) || !(eps >= FLT_MIN)) ? k_attn_heads<true> : k_attn_heads<false>;
+    const auto kern = !(eps >= FLT_MIN) ? k_attn_heads<true> : k_attn_heads<false>;
     if (cap > 0 && cap < cus) cus = cap;
     // one workgroup per CU, each wavefront on every S-th sample (S = wavefronts in the grid)
     const int64_t want = (batch + WPB - 1) / WPB;

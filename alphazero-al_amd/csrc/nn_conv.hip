@@ -32,7 +32,6 @@
 // it: no x is read at all, each wavefront builds the raw tile of its sample from the leaf's position.
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 
 #include "az_nn.h"
 #include "nn_common.h"
@@ -157,8 +156,8 @@ __global__ void __launch_bounds__(256, 2) k_stem_conv_block(StemIn st, const uin
 }
 
 // az_nn_debug: timing experiments (1 skips the MFMA loop, 2 skips the store, ...: bits 0-7 go to the kernels of this file)
-// and the launch-time choices of nn_attn.hip / nn_attn_heads.hip (az_nn_debug_flags)
-int g_dbg = [] { const char *e = getenv("AZ_VALUE_TAIL_DEFERRED"); return e != nullptr && strcmp(e, "0") == 0 ? AZ_NN_DEBUG_LEGACY_TAIL : 0; }();
+// and the grid cap of nn_attn_heads.hip (az_nn_debug_flags)
+int g_dbg = 0;
 
 // What a launch of either kernel does once its pointer and its dynamic LDS bytes are known: the once-per-device set-up
 // (with AZ_NN_VERBOSE: the occupancy line; c_in 0 words it for k_stem_conv_block), then the grid - one workgroup per

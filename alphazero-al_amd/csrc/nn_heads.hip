@@ -47,8 +47,6 @@ constexpr int L_SCORE = L_PART + WPB * 8 * C * 4;        // per wave: float [48]
 constexpr int L_MEAN = L_SCORE + WPB * 48 * 4;           // per wave: float [2][64] token means of the pair
 constexpr int L_TOTAL = L_MEAN + WPB * 2 * C * 4;
 
-// LEGACY: the unsplit pair tail (az_nn_debug bit 8; same bytes)
-template <bool LEGACY>
 __global__ void __launch_bounds__(64 * WPB) k_heads(const uint16_t *tok, az_nn_heads_weights w, const uint8_t *mask,
                                                     float *probs, float *wdl, float *moves_left, int64_t B, float eps,
                                                     const int32_t *scatter, const int64_t *batch_dev)
@@ -140,12 +138,8 @@ __global__ void __launch_bounds__(64 * WPB) k_heads(const uint16_t *tok, az_nn_h
 #pragma unroll
             for (int k = 0; k < 6; ++k) cur[k] = nxt[k];
         }
-        if constexpr (LEGACY)
-            heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, 2 * pr, 2 * pr + 1, B, rows_total,
-                                scatter, eps, lane, l15, l4);
-        else
-            heads_pair_tail_split<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, 2 * pr, 2 * pr + 1, B,
-                                      rows_total, scatter, eps, lane, l15, l4);
+        heads_pair_tail<VS>(s_a, s_c, s_vec, s_mean, w, mask, probs, wdl, moves_left, 2 * pr, 2 * pr + 1, B, rows_total,
+                            scatter, eps, lane, l15, l4);
     }
 }
 
@@ -157,12 +151,11 @@ extern "C" int az_nn_heads(const void *tokens, const az_nn_heads_weights *w, con
 {
     if (batch <= 0 || w == nullptr || tokens == nullptr || probs == nullptr || wdl == nullptr || moves_left == nullptr) return 1;
     static DeviceSetup setup;
-    if (setup.cus({reinterpret_cast<const void *>(k_heads<false>), reinterpret_cast<const void *>(k_heads<true>)}, L_TOTAL) == 0) return 2;
-    const auto kern = (az_nn_debug_flags() & AZ_NN_DEBUG_LEGACY_TAIL) ? k_heads<true> : k_heads<false>;
+    if (setup.cus({reinterpret_cast<const void *>(k_heads)}, L_TOTAL) == 0) return 2;
     // 70 KB of LDS per workgroup: two workgroups (8 wavefronts) per CU, each walking its sample pairs
     const int64_t want = ((batch + 1) / 2 + WPB - 1) / WPB;
     const unsigned grid = static_cast<unsigned>(want < 512 ? want : 512);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WPB), L_TOTAL, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(k_heads, dim3(grid), dim3(64 * WPB), L_TOTAL, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(tokens), *w, mask, probs, wdl, moves_left, batch, eps, scatter, batch_dev);
     return 0;
 }

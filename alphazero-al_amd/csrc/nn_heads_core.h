@@ -16,8 +16,8 @@
 // on all of them, each lane on the column it holds in the MFMA C layout.  MFMA columns are independent and col_sum stays
 // inside a column, so a sample's outputs do not depend on the column it sits in nor on what the other columns hold.
 // The callers differ in which columns are live:
-//   per pair (k_heads, and the legacy form of k_attn_heads): columns 7 and 15 of the pair's B operand, next to the
-//       policy columns; the token pass leaves the mean in s_mean[hs] and its pool_norm in column 8 hs + 7;
+//   per pair (k_heads): columns 7 and 15 of the pair's B operand, next to the policy columns; the token pass leaves
+//       the mean in s_mean[hs] and its pool_norm in column 8 hs + 7;
 //   deferred (k_attn_heads): the token pass only parks the bf16 token mean in one of 16 slots; once per 16 samples (and
 //       after the last one) the wavefront fills ALL 16 columns with value vectors and runs the three stages once, where
 //       the per-pair form runs them eight times for the same samples.
@@ -281,10 +281,10 @@ __device__ __forceinline__ void value_tail(const AFrag &afrag, const float (*s_c
 
 // policy_tail() and value_tail() of a pair whose value vectors sit in columns 7 and 15 (means in s_mean[2][64])
 template <int VS>
-__device__ __forceinline__ void heads_pair_tail_split(const V8 *s_a, const float (*s_c)[C], uint16_t *s_vec, const float *s_mean,
-                                                const az_nn_heads_weights &w, const uint8_t *mask, float *probs, float *wdl,
-                                                float *moves_left, int64_t b0, int64_t b1, int64_t B, int64_t rows_total,
-                                                const int32_t *scatter, float eps, int lane, int l15, int l4)
+__device__ __forceinline__ void heads_pair_tail(const V8 *s_a, const float (*s_c)[C], uint16_t *s_vec, const float *s_mean,
+                                          const az_nn_heads_weights &w, const uint8_t *mask, float *probs, float *wdl,
+                                          float *moves_left, int64_t b0, int64_t b1, int64_t B, int64_t rows_total,
+                                          const int32_t *scatter, float eps, int lane, int l15, int l4)
 {
     policy_tail<VS>(s_a, s_c, s_vec, w, mask, probs, b0, b1, B, rows_total, scatter, lane, l15, l4);
     const int half = l15 >> 3;
@@ -293,132 +293,6 @@ __device__ __forceinline__ void heads_pair_tail_split(const V8 *s_a, const float
     const bool real = bc < B && b >= 0 && b < rows_total;
     auto mean2 = [&](int m, int hh) { return *reinterpret_cast<const f32x2 *>(&s_mean[half * C + 16 * m + 4 * l4 + 2 * hh]); };
     value_tail<VS>(AFragLds{s_a, lane}, s_c, s_vec, mean2, w, wdl, moves_left, (l15 & 7) == 7, b, real, eps, l15, l4);
-}
-
-// The pair tail as ONE piece, as it was before the split into policy_tail() and value_tail() (policy fc and value pool_fc
-// share one operand fetch): what the LEGACY instantiations of k_heads and k_attn_heads run, kept as the oracle the split
-// form is tested against byte for byte.  Both samples of a pair, b0 and b1 (b1 >= B: a half-empty pair): columns 0-6 | 7 and 8-14 | 15 of the B operand.
-// Compact batch: sample b stands for row scatter[b] of the mask and of the outputs; an index outside the rows (a list
-// longer than what was written) is dropped, never dereferenced.
-template <int VS>
-__device__ __forceinline__ void heads_pair_tail(const V8 *s_a, const float (*s_c)[C], uint16_t *s_vec, const float *s_mean,
-                                                const az_nn_heads_weights &w, const uint8_t *mask, float *probs, float *wdl,
-                                                float *moves_left, int64_t b0, int64_t b1, int64_t B, int64_t rows_total,
-                                                const int32_t *scatter, float eps, int lane, int l15, int l4)
-{
-    auto afrag = [&](int f) { return as_bf16x8(s_a[f * 64 + lane]); };
-    auto bfrag = [&](int ks) { return as_bf16x8(*reinterpret_cast<const V8 *>(&s_vec[l15 * VS + 32 * ks + 8 * l4])); };
-    auto cvec2 = [&](int which, int m, int h) { return *reinterpret_cast<const f32x2 *>(&s_c[which][16 * m + 4 * l4 + 2 * h]); };
-    const bool dual = (l15 & 7) == 7;          // this lane's accumulator column is a value-head vector
-    const int half = l15 >> 3;                 // which sample of the pair the column belongs to
-    // a dual lane's 16 accumulator values (channel 16m+4*l4+reg) -> its own B-operand row
-    auto put_dual = [&](const f32x2 (&v)[4][2]) {
-        if (dual) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                uint32_t *p = reinterpret_cast<uint32_t *>(&s_vec[l15 * VS + 16 * m + 4 * l4]);
-                p[0] = pack2(v[m][0].x, v[m][0].y);
-                p[1] = pack2(v[m][1].x, v[m][1].y);
-            }
-        }
-    };
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int64_t bc = half == 0 ? b0 : b1;       // the sample this lane's column belongs to
-    const int64_t b = (bc < B && scatter != nullptr) ? scatter[bc] : bc;
-    const bool real = bc < B && b >= 0 && b < rows_total;
-    f32x4 ap[4], ad[4];
-    {
-        const bf16x8 v0 = bfrag(0), v1 = bfrag(1);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            ap[m] = MFMA32(afrag(2 * m), v0, zero);
-            ap[m] = MFMA32(afrag(2 * m + 1), v1, ap[m]);
-            ad[m] = MFMA32(afrag(8 + 2 * m), v0, zero);
-            ad[m] = MFMA32(afrag(8 + 2 * m + 1), v1, ad[m]);
-        }
-    }
-    // policy: logit[c] = out . silu(fc(col_c) + b), masked softmax over the 7 columns of a sample
-    {
-        f32x2 part2 = {0.0f, 0.0f};
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const f32x2 xv = rbf2(f32x2{ap[m][2 * hh], ap[m][2 * hh + 1]} + cvec2(K_PFC_B, m, hh));
-                part2 = __builtin_elementwise_fma(rbf2(silu2(xv)), cvec2(K_POUT_W, m, hh), part2);
-            }
-        float logit = col_sum(part2.x + part2.y) + w.p_out_b;
-        const bool live = !dual;
-        if (live && real && mask != nullptr && mask[b * COLS + (l15 & 7)] == 0) logit = -1e9f;
-        if (!live) logit = -INFINITY;
-        const float mx = max8(logit);
-        const float e = live ? fast_exp(logit - mx) : 0.0f;
-        const float den = sum8(e);
-        if (live && real && l4 == 0) probs[b * COLS + (l15 & 7)] = e * __builtin_amdgcn_rcpf(den);
-    }
-    // value head, stage 1 (dual columns): g = mean + silu(pool_fc(pool_norm(mean)) + b); n2 = norm(g)
-    f32x2 g[4][2];
-    {
-        f32x2 ss2 = {0.0f, 0.0f};
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const f32x2 mean = *reinterpret_cast<const f32x2 *>(&s_mean[half * C + 16 * m + 4 * l4 + 2 * hh]);
-                const f32x2 xv = rbf2(f32x2{ad[m][2 * hh], ad[m][2 * hh + 1]} + cvec2(K_DPOOL_B, m, hh));
-                g[m][hh] = rbf2(mean + rbf2(silu2(xv)));
-                ss2 = __builtin_elementwise_fma(g[m][hh], g[m][hh], ss2);
-            }
-        const float rn = rsqrtf(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) g[m][hh] = g[m][hh] * f32x2{rn, rn} * cvec2(K_DNORM, m, hh);
-    }
-    wave_lds_sync();
-    put_dual(g);
-    wave_lds_sync();
-    // stage 2: h = out_norm(silu(fc(n2) + b))
-    {
-        const bf16x8 v0 = bfrag(0), v1 = bfrag(1);
-        f32x2 ss2 = {0.0f, 0.0f};
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            f32x4 acc = MFMA32(afrag(16 + 2 * m), v0, zero);
-            acc = MFMA32(afrag(16 + 2 * m + 1), v1, acc);
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const f32x2 xv = rbf2(f32x2{acc[2 * hh], acc[2 * hh + 1]} + cvec2(K_DFC_B, m, hh));
-                g[m][hh] = rbf2(silu2(xv));
-                ss2 = __builtin_elementwise_fma(g[m][hh], g[m][hh], ss2);
-            }
-        }
-        const float rn = rsqrtf(col_sum(ss2.x + ss2.y) * (1.0f / C) + eps);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) g[m][hh] = g[m][hh] * f32x2{rn, rn} * cvec2(K_DOUT_NORM, m, hh);
-    }
-    wave_lds_sync();
-    put_dual(g);
-    wave_lds_sync();
-    // stage 3: rows 0-2 = value logits, row 3 = moves-left logit, in the dual lanes with l4 == 0
-    {
-        f32x4 acc = MFMA32(afrag(24), bfrag(0), zero);
-        acc = MFMA32(afrag(25), bfrag(1), acc);
-        if (dual && l4 == 0 && real) {
-            const f32x2 v01 = rbf2(f32x2{acc[0] + s_c[K_DVAL_B][0], acc[1] + s_c[K_DVAL_B][1]});
-            const float v2 = rbf2(f32x2{acc[2] + s_c[K_DVAL_B][2], 0.0f}).x;
-            const float mx = fmaxf(v01.x, fmaxf(v01.y, v2));
-            const float e0 = fast_exp(v01.x - mx), e1 = fast_exp(v01.y - mx), e2 = fast_exp(v2 - mx);
-            const float inv = 1.0f / (e0 + e1 + e2);
-            wdl[b * 3 + 0] = e0 * inv;
-            wdl[b * 3 + 1] = e1 * inv;
-            wdl[b * 3 + 2] = e2 * inv;
-            moves_left[b] = w.aux_scale / (1.0f + fast_exp(-(acc[3] + w.d_aux_b)));
-        }
-    }
-    wave_lds_sync();
 }
 
 }  // namespace heads

@@ -84,8 +84,8 @@ int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void
  * 0-63 Q, 64-127 K, 128-191 V, 192-195 gate; o_w (64, 64) [out][in]; 4 heads of 16.
  * eps is the RMSNorms' epsilon (1e-5 in the reference).  The default forms of this kernel and of az_nn_attn_heads take
  * 1 / sqrt(mean square + eps) as one bare v_rsq_f32, which is exact only for arguments >= FLT_MIN; a call with
- * eps < FLT_MIN (0 included; NaN too) is therefore launched as the form bit 8 of az_nn_debug selects, whose rsqrtf()
- * carries the denormal-range guard.  Same output bytes either way. */
+ * eps < FLT_MIN (0 included; NaN too) is therefore launched as a second instantiation of the same kernel that takes
+ * rsqrtf() there, with its denormal-range guard.  Same output bytes either way. */
 int az_nn_attn_block(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w,
                      const void *k_norm_w, const void *o_w, void *y, int64_t batch, float eps, const int64_t *batch_dev,
                      void *stream);
@@ -110,7 +110,7 @@ int az_nn_heads(const void *tokens, const az_nn_heads_weights *w, const uint8_t 
  * and the weights of both, as those two take them, in; probs, wdl, moves_left out, with mask / scatter / batch_dev as
  * az_nn_heads reads them.  The block's output stays on chip (no token tensor is written); the rounding points are
  * those of the two kernels, so results differ from them only through f32 summation order.  eps: as for
- * az_nn_attn_block (below FLT_MIN the guarded form is launched). */
+ * az_nn_attn_block (below FLT_MIN the rsqrtf() instantiation is launched). */
 int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, const void *q_norm_w, const void *k_norm_w,
                      const void *o_w, const az_nn_heads_weights *w, const uint8_t *mask, float *probs, float *wdl,
                      float *moves_left, int64_t batch, float eps, const int32_t *scatter, const int64_t *batch_dev,
@@ -195,15 +195,9 @@ int az_nn_model_profile_read_kernels(double out_ms[4], int64_t out_launches[4]);
  * stores, bit 4 records per-wavefront cycle totals of its phases (az_nn_conv_profile: 8 values
  * per wavefront - P1, barrier, MFMA + epilogue, staging wait, barrier, store, and for
  * az_nn_stem_conv_block_positions the stem phase - for the first n / 8 wavefronts of the last launch). */
-/* Bit 8 (AZ_NN_DEBUG_LEGACY_TAIL) selects, at launch time, the earlier forms of az_nn_attn_heads (the value head once per
- * sample pair) and of the attention's gate tile (four sigmoids per lane) in az_nn_attn_block / az_nn_attn_heads: second
- * instantiations of the same kernels, same output bytes - for A/B runs and as the tests' oracle.  The bit starts set when
- * AZ_VALUE_TAIL_DEFERRED=0 is in the environment (read once, when the library is loaded); the variable is named after the
- * largest of the changes it undoes, and it also undoes the gate tile (az_nn_attn_block too) and the split tail of az_nn_heads.
- * az_nn_debug() REPLACES all flags: a later az_nn_debug(0), as the probes under tools/ make, clears the bit the environment set.
+/* Bit 8 is unused.  az_nn_debug() REPLACES all flags.
  * Bits 16-27 (AZ_NN_DEBUG_GRID_CAP(n)): at most n workgroups in az_nn_attn_heads' grid (0 = one per CU), so that tests
  * reach many samples per wavefront with few samples. */
-#define AZ_NN_DEBUG_LEGACY_TAIL 256
 #define AZ_NN_DEBUG_GRID_CAP(n) (((n) & 0xfff) << 16)
 int az_nn_debug(int flags);
 int az_nn_debug_flags(void);

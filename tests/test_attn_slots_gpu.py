@@ -1,27 +1,23 @@
 """The fused attention kernel with fewer issue slots (nn_common.h rsq_normal / col_sum2 / col_max2 / sum16_dpp, used by
-the default forms of az_nn_attn_heads and az_nn_attn_block): bare reciprocal square roots, two column sums through one
-set of lane swaps, the token means as DPP adds.  None of it may change a byte: every case compares the raw output arrays
-of the default forms with those of az_nn_debug bit 8, which keeps rsqrtf() and the single reductions as they compiled
-before.  Bits 16-27 of az_nn_debug cap az_nn_attn_heads' grid: one workgroup is 12 wavefronts, each on every 12th sample.
-
-The weights are random in the checkpoint's shapes; the activations carry rows of exact zeros (the reciprocal square root's
-smallest argument, eps itself) and rows of magnitude 1e18 (squares near 1e36, their sums still finite in f32)."""
+az_nn_attn_heads and az_nn_attn_block): bare reciprocal square roots, two column sums through one set of lane swaps, the
+token means as DPP adds.  None of it may change a byte: the cases of tests/golden/g19_attn_bytes.npz that guard it, against
+the record of the commit that still had rsqrtf() and the single reductions as a second form (tests/test_attn_bytes_gpu.py,
+tools/record_attn_golden.py): random weights in the checkpoint's shapes, activations with rows of exact zeros (the
+reciprocal square root's smallest argument, eps itself) and rows of magnitude 1e18 (squares near 1e36, their sums still
+finite in f32).  Two tests need no record: an eps below FLT_MIN, which launches the rsqrtf() instantiation, against the
+two launches (az_nn_attn_block, az_nn_heads) at the same eps, and the paired column reductions against the single ones."""
 import ctypes as C
 import os
 import sys
 
 import pytest
 
+from test_attn_bytes_gpu import check, runner  # noqa: F401  (runner: the fixture)
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "alphazero-al_amd")
-LEGACY = 256                    # AZ_NN_DEBUG_LEGACY_TAIL
-EPS = 1e-5
-
-
-def _cap(n):                    # AZ_NN_DEBUG_GRID_CAP
-    return (n & 0xfff) << 16
 
 
 def _random_net(torch, az_net):
@@ -54,145 +50,79 @@ def env():
     from src.fast_net import FastConnect4Net, glue
     net = _random_net(torch, az_net)
     L = glue()
-    twins = {}
-    for sharp in (False, True):
-        fast = FastConnect4Net.from_module(net)
-        if sharp:       # sharpened q-norm weights: scores outside the bound, the max-subtracting softmax runs
-            fast.qn_w = (fast.qn_w.float() * 40.0).to(fast.qn_w.dtype).contiguous()
-        twins[sharp] = fast
-    initial = L.az_nn_debug_flags()
-    yield dict(torch=torch, L=L, twins=twins)
-    L.az_nn_debug(initial)
+    return dict(torch=torch, L=L, fast=FastConnect4Net.from_module(net))
 
 
-def _inputs(torch, B, seed, extremes=True):
-    """x (B, 42, 64) bf16 and a mask.  extremes: about one token row in eight is exactly zero and one in eight has
-    entries +-1e18 x [0.5, 1); sample 0 gets both kinds in its first and its last token tile, a whole zero sample follows
-    when there is room for one."""
+def _inputs(torch, B, seed):
+    """x (B, 42, 64) bf16 and a mask with column 3 open"""
     gen = torch.Generator(device="cuda").manual_seed(seed)
     x = torch.randn((B, 42, 64), device="cuda", generator=gen) * 1.5
-    if extremes:
-        kind = torch.randint(0, 8, (B, 42), device="cuda", generator=gen)
-        kind[0, 0], kind[0, 1], kind[0, 40], kind[0, 41] = 0, 1, 1, 0
-        big = (torch.rand((B, 42, 64), device="cuda", generator=gen) * 0.5 + 0.5) * 1e18
-        big = torch.where(torch.rand((B, 42, 64), device="cuda", generator=gen) < 0.5, -big, big)
-        x = torch.where((kind == 1)[..., None], big, x)
-        x = torch.where((kind == 0)[..., None], torch.zeros_like(x), x)
-        if B > 1:
-            x[1] = 0.0
     mask = torch.rand((B, 7), device="cuda", generator=gen) > 0.25
     mask[:, 3] = True
-    return x.to(torch.bfloat16).contiguous(), mask.to(torch.uint8).contiguous(), gen
+    return x.to(torch.bfloat16).contiguous(), mask.to(torch.uint8).contiguous()
 
 
-def _attn_heads(env, fast, x, m8, B, flags, eps=EPS, rows=None, n_rows=None):
+def _attn_heads(env, fast, x, m8, B, eps):
     torch, L = env["torch"], env["L"]
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     out = [torch.full(shape, float("nan"), device="cuda") for shape in ((B, 7), (B, 3), (B,))]
-    before = L.az_nn_debug_flags()
-    L.az_nn_debug(flags)
-    try:
-        assert L.az_nn_attn_heads(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
-                                  fast.kn_w.data_ptr(), fast.o_w.data_ptr(), C.byref(fast._heads_w),
-                                  None if m8 is None else m8.data_ptr(), *[t.data_ptr() for t in out], B, eps,
-                                  None if rows is None else rows.data_ptr(), None if n_rows is None else n_rows.data_ptr(), s) == 0
-        torch.cuda.synchronize()
-    finally:
-        L.az_nn_debug(before)
+    assert L.az_nn_attn_heads(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
+                              fast.kn_w.data_ptr(), fast.o_w.data_ptr(), C.byref(fast._heads_w), m8.data_ptr(),
+                              *[t.data_ptr() for t in out], B, eps, None, None, s) == 0
+    torch.cuda.synchronize()
     return out
 
 
-def _attn_block(env, fast, x, B, flags, eps=EPS):
+def _attn_block(env, fast, x, B, eps):
     torch, L = env["torch"], env["L"]
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     y = torch.full_like(x, float("nan"))
-    before = L.az_nn_debug_flags()
-    L.az_nn_debug(flags)
-    try:
-        assert L.az_nn_attn_block(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
-                                  fast.kn_w.data_ptr(), fast.o_w.data_ptr(), y.data_ptr(), B, eps, None, s) == 0
-        torch.cuda.synchronize()
-    finally:
-        L.az_nn_debug(before)
+    assert L.az_nn_attn_block(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
+                              fast.kn_w.data_ptr(), fast.o_w.data_ptr(), y.data_ptr(), B, eps, None, s) == 0
+    torch.cuda.synchronize()
     return y
 
 
-def _same_bytes(torch, a, b, tag):
-    for name, u, v in zip(("probs", "wdl", "moves_left"), a, b):
-        assert torch.equal(u.view(torch.int32), v.view(torch.int32)), (tag, name)
-
-
-def _heads_both_ways(env, fast, x, m8, B, cap, **kw):
-    """az_nn_attn_heads under the default and under bit 8: the first is returned, the two are equal as bytes"""
-    new = _attn_heads(env, fast, x, m8, B, _cap(cap), **kw)
-    old = _attn_heads(env, fast, x, m8, B, _cap(cap) | LEGACY, **kw)
-    _same_bytes(env["torch"], new, old, ("bit 8", B, cap))
-    return new
+SHARP = {False: "soft", True: "sharp"}
 
 
 @pytest.mark.parametrize("sharp", [False, True])
 @pytest.mark.parametrize("B", [1, 2, 3, 25])
-def test_attn_heads(env, B, sharp):
+def test_attn_heads(runner, B, sharp):
     """one sample; a full pair; a half-empty pair after a full one (3); 25: two wavefronts per workgroup with a second
     pair, uncapped and with everything in one workgroup"""
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    x, m8, _ = _inputs(torch, B, 1500 + B)
     for cap in (0, 1):
-        for mk in (m8, None):
-            for t in _heads_both_ways(env, fast, x, mk, B, cap):
-                assert torch.isfinite(t).all()
+        for mask in ("mask", "nomask"):
+            check(runner, "heads/w2/extreme/b%d/cap%d/%s/%s" % (B, cap, mask, SHARP[sharp]))
 
 
 @pytest.mark.parametrize("sharp", [False, True])
 @pytest.mark.parametrize("B", [1, 2, 3, 25])
-def test_attn_block(env, B, sharp):
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    x, _, _ = _inputs(torch, B, 1600 + B)
-    new, old = _attn_block(env, fast, x, B, 0), _attn_block(env, fast, x, B, LEGACY)
-    assert torch.isfinite(new.float()).all()
-    assert torch.equal(new.view(torch.int16), old.view(torch.int16)), (B, sharp)
+def test_attn_block(runner, B, sharp):
+    check(runner, "block/w2/extreme/b%d/cap0/nomask/%s" % (B, SHARP[sharp]))
 
 
 @pytest.mark.parametrize("sharp", [False, True])
-def test_attn_heads_flush_twice(env, sharp):
+def test_attn_heads_flush_twice(runner, sharp):
     """one workgroup and 12 x 17 + 1 samples: every wavefront fills its 16 mean slots and flushes, then parks one more
     sample (the first wavefront two) and flushes a partial set"""
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    B = 12 * 17 + 1
-    x, m8, _ = _inputs(torch, B, 1700)
-    for t in _heads_both_ways(env, fast, x, m8, B, 1):
-        assert torch.isfinite(t).all()
+    check(runner, "heads/w2/extreme/b205/cap1/mask/" + SHARP[sharp])
 
 
 @pytest.mark.parametrize("sharp", [False, True])
-def test_attn_heads_compact_list(env, sharp):
-    """25 samples scattered into 40 output rows: the listed rows equal bit 8's and are finite, the other 15 keep their
-    NaN prefill; the samples past the device-side count are NaN and must not reach a listed row"""
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    B, live = 40, 25
-    x, m8, gen = _inputs(torch, B, 1800)
-    x[live:] = float("nan")
-    rows = torch.randperm(B, device="cuda", generator=gen).to(torch.int32).contiguous()
-    n_rows = torch.tensor([live], dtype=torch.int64, device="cuda")
-    new = _heads_both_ways(env, fast, x, m8, B, 0, rows=rows, n_rows=n_rows)
-    listed = torch.zeros(B, dtype=torch.bool, device="cuda")
-    listed[rows[:live].long()] = True
-    assert listed.sum().item() == live
-    for t in new:
-        assert torch.isfinite(t[listed]).all()
-        assert torch.isnan(t[~listed]).all()
+def test_attn_heads_compact_list(runner, sharp):
+    """25 samples scattered into 40 output rows: the listed rows have the recorded bytes and are finite, the other 15 keep
+    their NaN prefill; the samples past the device-side count are NaN and must not reach a listed row"""
+    check(runner, "heads/w2/extreme/b40l25/cap0/mask/" + SHARP[sharp])
 
 
 @pytest.mark.parametrize("eps", [0.0, 1e-40])
 def test_eps_below_flt_min_runs_the_guarded_form(env, eps):
-    """An eps below FLT_MIN is outside rsq_normal()'s range: both settings launch the rsqrtf() form, so their bytes are
-    equal, and the results are those of the two launches (az_nn_attn_block, az_nn_heads) at the same eps.
+    """An eps below FLT_MIN is outside rsq_normal()'s range: the rsqrtf() instantiations are launched (their bytes are in
+    tests/test_attn_bytes_gpu.py's record), and the results are those of the two launches (az_nn_attn_block, az_nn_heads)
+    at the same eps.
     eps = 1e-40 (a denormal) is where the guard matters: every output is finite.  eps = 0 is no working setting of
-    either form, before this change or after it: the six padding tokens of a sample are rows of zeros, their statistic
+    either form: the six padding tokens of a sample are rows of zeros, their statistic
     is 1 / sqrt(0 + 0) = inf and 0 x inf = NaN reaches every key - what is pinned is that the fused kernel and the two
     launches still agree, NaN for NaN.
     Bounds against the two launches where the values are finite: those of tests/test_attn_heads_gpu.py's _close (same
@@ -200,15 +130,14 @@ def test_eps_below_flt_min_runs_the_guarded_form(env, eps):
     moves an output by a few bf16 ulps of a logit) - maxima only, a mean over 25 samples says nothing about how rare such
     flips are."""
     torch, L = env["torch"], env["L"]
-    fast = env["twins"][False]
+    fast = env["fast"]
     B = 25
-    x, m8, _ = _inputs(torch, B, 1900, extremes=False)
-    fused = _heads_both_ways(env, fast, x, m8, B, 0, eps=eps)
-    y_new, y_old = _attn_block(env, fast, x, B, 0, eps=eps), _attn_block(env, fast, x, B, LEGACY, eps=eps)
-    assert torch.equal(y_new.view(torch.int16), y_old.view(torch.int16))
+    x, m8 = _inputs(torch, B, 1900)
+    fused = _attn_heads(env, fast, x, m8, B, eps)
+    y = _attn_block(env, fast, x, B, eps)
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     two = [torch.full(shape, float("nan"), device="cuda") for shape in ((B, 7), (B, 3), (B,))]
-    assert L.az_nn_heads(y_new.data_ptr(), C.byref(fast._heads_w), m8.data_ptr(), *[t.data_ptr() for t in two], B, eps,
+    assert L.az_nn_heads(y.data_ptr(), C.byref(fast._heads_w), m8.data_ptr(), *[t.data_ptr() for t in two], B, eps,
                          None, None, s) == 0
     torch.cuda.synchronize()
     for name, a, b, bound in zip(("probs", "wdl", "moves_left"), fused, two, (5e-3, 5e-3, 0.05)):

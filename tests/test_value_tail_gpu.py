@@ -1,213 +1,51 @@
 """The deferred value tail of az_nn_attn_heads and the one-sigmoid gate tile of the attention body (nn_heads_core.h,
-nn_attn_core.h), byte for byte against the earlier forms of the same kernels, which az_nn_debug bit 8 selects at launch
-time.  Bits 16-27 of az_nn_debug cap az_nn_attn_heads' grid: with one workgroup (12 wavefronts) a few hundred samples
-reach the 16-slot flush of a wavefront."""
-import ctypes as C
-import os
-import sys
-
-import numpy as np
+nn_attn_core.h): the cases of tests/golden/g19_attn_bytes.npz that guard them, byte for byte against the record of the
+commit that still had the earlier forms (tests/test_attn_bytes_gpu.py, tools/record_attn_golden.py).  With the grid capped
+to one workgroup (12 wavefronts) a few hundred samples reach the 16-slot flush of a wavefront."""
 import pytest
 
-from test_oracle_golden import load
+from test_attn_bytes_gpu import check, runner  # noqa: F401  (runner: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "alphazero-al_amd")
-LEGACY = 256                    # AZ_NN_DEBUG_LEGACY_TAIL
-
-
-def _cap(n):                    # AZ_NN_DEBUG_GRID_CAP
-    return (n & 0xfff) << 16
-
-
-@pytest.fixture(scope="module")
-def env():
-    sys.path.insert(0, ROOT)
-    import torch  # noqa: F401  (before the engine library: one HIP runtime per process)
-    import __graft_entry__ as ge
-    ge.build()
-    if PKG not in sys.path:
-        sys.path.insert(0, PKG)
-    from src import az_net
-    from src.fast_net import FastConnect4Net, glue
-    wts = load("g7_checkpoint_weights")
-    net = az_net.Connect4Net(device="cuda").eval()
-    az_net.load_reference_weights(net, {k: wts[k] for k in wts.files})
-    L = glue()
-    twins = {}
-    for sharp in (False, True):
-        fast = FastConnect4Net.from_module(net)
-        if sharp:       # sharpened q-norm weights: scores outside the bound, the max-subtracting softmax runs
-            fast.qn_w = (fast.qn_w.float() * 40.0).to(fast.qn_w.dtype).contiguous()
-        twins[sharp] = fast
-    initial = L.az_nn_debug_flags()
-    yield dict(torch=torch, net=net, FastNet=FastConnect4Net, L=L, twins=twins)
-    L.az_nn_debug(initial)
-
-
-def _inputs(torch, B, seed):
-    gen = torch.Generator(device="cuda").manual_seed(seed)
-    x = (torch.randn((B, 42, 64), device="cuda", generator=gen) * 1.5).to(torch.bfloat16)
-    mask = (torch.rand((B, 7), device="cuda", generator=gen) > 0.25)
-    mask[:, 3] = True
-    return x, mask, gen
-
-
-def _attn_heads(env, fast, x, m8, B, flags, rows=None, n_rows=None):
-    torch, L = env["torch"], env["L"]
-    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    probs = torch.full((B, 7), float("nan"), device="cuda")
-    wdl = torch.full((B, 3), float("nan"), device="cuda")
-    ml = torch.full((B,), float("nan"), device="cuda")
-    L.az_nn_debug(flags)
-    assert L.az_nn_attn_heads(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
-                              fast.kn_w.data_ptr(), fast.o_w.data_ptr(), C.byref(fast._heads_w),
-                              None if m8 is None else m8.data_ptr(), probs.data_ptr(), wdl.data_ptr(), ml.data_ptr(), B, 1e-5,
-                              None if rows is None else rows.data_ptr(), None if n_rows is None else n_rows.data_ptr(), s) == 0
-    torch.cuda.synchronize()
-    L.az_nn_debug(0)
-    return probs, wdl, ml
-
-
-def _same_bytes(torch, a, b, tag):
-    for name, u, v in zip(("probs", "wdl", "moves_left"), a, b):
-        assert torch.equal(u.view(torch.int32), v.view(torch.int32)), (tag, name)
+SHARP = {False: "soft", True: "sharp"}
 
 
 @pytest.mark.parametrize("sharp", [False, True])
 @pytest.mark.parametrize("B", [1, 13, 192, 193, 401])
-def test_attn_heads_one_workgroup(env, B, sharp):
+def test_attn_heads_one_workgroup(runner, B, sharp):
     """one workgroup: 0, 1-2, exactly 16, 16-17 and 33-34 samples per wavefront"""
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    x, mask, _ = _inputs(torch, B, 100 + B)
-    m8 = mask.to(torch.uint8).contiguous()
-    for mk in (m8, None):
-        new = _attn_heads(env, fast, x, mk, B, _cap(1))
-        old = _attn_heads(env, fast, x, mk, B, _cap(1) | LEGACY)
-        for t in new:
-            assert torch.isfinite(t).all()
-        _same_bytes(torch, new, old, (B, sharp, mk is None))
+    for mask in ("mask", "nomask"):
+        check(runner, "heads/w1/plain/b%d/cap1/%s/%s" % (B, mask, SHARP[sharp]))
 
 
 @pytest.mark.parametrize("sharp", [False, True])
 @pytest.mark.parametrize("B", [777, 4099])
-def test_attn_heads_uncapped(env, B, sharp):
-    torch = env["torch"]
-    fast = env["twins"][sharp]
-    x, mask, _ = _inputs(torch, B, 200 + B)
-    m8 = mask.to(torch.uint8).contiguous()
-    for mk in (m8, None):
-        new = _attn_heads(env, fast, x, mk, B, 0)
-        old = _attn_heads(env, fast, x, mk, B, LEGACY)
-        for t in new:
-            assert torch.isfinite(t).all()
-        _same_bytes(torch, new, old, (B, sharp, mk is None))
+def test_attn_heads_uncapped(runner, B, sharp):
+    for mask in ("mask", "nomask"):
+        check(runner, "heads/w1/plain/b%d/cap0/%s/%s" % (B, mask, SHARP[sharp]))
 
 
 @pytest.mark.parametrize("B,live,cap,stray", [(9, 5, 0, False), (401, 260, 1, False), (401, 260, 1, True), (9, 9, 0, True)])
-def test_attn_heads_compact_list(env, B, live, cap, stray):
-    """batch_dev < B and shuffled scatter rows: listed rows equal, every other row still NaN; stray: some listed
+def test_attn_heads_compact_list(runner, B, live, cap, stray):
+    """batch_dev < B and shuffled scatter rows: listed rows as recorded, every other row still NaN; stray: some listed
     indices lie outside the batch (negative, B, far beyond) and are dropped, never written"""
-    torch = env["torch"]
-    fast = env["twins"][False]
-    x, mask, gen = _inputs(torch, B, 300 + B + live)
-    m8 = mask.to(torch.uint8).contiguous()
-    rows = torch.randperm(B, device="cuda", generator=gen).to(torch.int32)
-    if stray:
-        bad = torch.tensor([-1, B, B + 7, 2**31 - 1, -2**31], dtype=torch.int32, device="cuda")
-        at = torch.arange(0, live, max(1, live // len(bad)), device="cuda")[:len(bad)]
-        rows[at] = bad[:len(at)]
-    rows = rows.contiguous()
-    n_rows = torch.tensor([live], dtype=torch.int64, device="cuda")
-    new = _attn_heads(env, fast, x, m8, B, _cap(cap), rows, n_rows)
-    old = _attn_heads(env, fast, x, m8, B, _cap(cap) | LEGACY, rows, n_rows)
-    named = rows[:live].long()
-    named = named[(named >= 0) & (named < B)]
-    listed = torch.zeros(B, dtype=torch.bool, device="cuda")
-    listed[named] = True
-    assert listed.sum().item() == live - (min(5, live) if stray else 0)
-    for t in new:
-        assert torch.isfinite(t[listed]).all()
-        assert torch.isnan(t[~listed]).all()
-    _same_bytes(torch, new, old, ("compact", B, live, cap, stray))
+    check(runner, "heads/w1/plain/b%dl%d%s/cap%d/mask/soft" % (B, live, "s" if stray else "", cap))
 
 
 @pytest.mark.parametrize("sharp", [False, True])
-def test_attn_block_gate_tile(env, sharp):
-    """az_nn_attn_block: the gate change alone"""
-    torch, L = env["torch"], env["L"]
-    fast = env["twins"][sharp]
-    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def test_attn_block_gate_tile(runner, sharp):
+    """az_nn_attn_block: the gate tile alone"""
     for B in (1, 3, 50):
-        x, _, _ = _inputs(torch, B, 400 + B)
-        ys = []
-        for flags in (0, LEGACY):
-            y = torch.full_like(x, float("nan"))
-            L.az_nn_debug(flags)
-            assert L.az_nn_attn_block(x.data_ptr(), fast.pre_w.data_ptr(), fast.qkvg_w.data_ptr(), fast.qn_w.data_ptr(),
-                                      fast.kn_w.data_ptr(), fast.o_w.data_ptr(), y.data_ptr(), B, 1e-5, None, s) == 0
-            torch.cuda.synchronize()
-            L.az_nn_debug(0)
-            ys.append(y)
-        assert torch.isfinite(ys[0].float()).all()
-        assert torch.equal(ys[0].view(torch.int16), ys[1].view(torch.int16)), (B, sharp)
+        check(runner, "block/w1/plain/b%d/cap0/nomask/%s" % (B, SHARP[sharp]))
 
 
-def test_heads_split_tail(env):
-    """az_nn_heads: the pair tail as policy_tail + value_tail against the tail in one piece"""
-    torch, L = env["torch"], env["L"]
-    fast = env["twins"][False]
-    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def test_heads_split_tail(runner):
+    """az_nn_heads: the pair tail as policy_tail + value_tail"""
     for B in (1, 2, 3, 9):
-        tok, mask, _ = _inputs(torch, B, 500 + B)
-        m8 = mask.to(torch.uint8).contiguous()
-        outs = []
-        for flags in (0, LEGACY):
-            probs = torch.full((B, 7), float("nan"), device="cuda")
-            wdl = torch.full((B, 3), float("nan"), device="cuda")
-            ml = torch.full((B,), float("nan"), device="cuda")
-            L.az_nn_debug(flags)
-            assert L.az_nn_heads(tok.data_ptr(), C.byref(fast._heads_w), m8.data_ptr(), probs.data_ptr(), wdl.data_ptr(),
-                                 ml.data_ptr(), B, 1e-5, None, None, s) == 0
-            torch.cuda.synchronize()
-            L.az_nn_debug(0)
-            outs.append((probs, wdl, ml))
-        for t in outs[0]:
-            assert torch.isfinite(t).all()
-        _same_bytes(torch, outs[0], outs[1], ("heads", B))
+        check(runner, "pair/w1/plain/b%d/cap0/mask/soft" % B)
 
 
-def test_native_model_forward(env):
-    """az_nn_model_forward on about 3000 positions: all three outputs equal under both settings"""
-    torch, L = env["torch"], env["L"]
-    g = load("g7_network")
-    boards, turns = g["boards"], g["turns"]
-    planes = np.stack([(boards == turns[:, None, None]), (boards == -turns[:, None, None]),
-                       np.ones_like(boards) * turns[:, None, None]], 1).astype(np.float32)
-    reps = -(-3000 // len(planes))
-    feats = torch.from_numpy(np.concatenate([planes] * reps)).cuda().contiguous()
-    B = feats.shape[0]
-    mask = torch.from_numpy(np.concatenate([(boards[:, 0, :] == 0)] * reps).astype(np.uint8)).cuda().contiguous()
-    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fast = env["FastNet"].from_module(env["net"])
-    model = fast.native_model()
-    assert model is not None
-    nb = int(L.az_nn_model_scratch_bytes(model, B))
-    scratch = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    outs = []
-    for flags in (0, LEGACY):
-        probs = torch.full((B, 7), float("nan"), device="cuda")
-        wdl = torch.full((B, 3), float("nan"), device="cuda")
-        ml = torch.full((B,), float("nan"), device="cuda")
-        L.az_nn_debug(flags)
-        assert L.az_nn_model_forward(model, feats.data_ptr(), mask.data_ptr(), probs.data_ptr(), wdl.data_ptr(),
-                                     ml.data_ptr(), B, None, None, scratch.data_ptr(), nb, s) == 0
-        torch.cuda.synchronize()
-        L.az_nn_debug(0)
-        outs.append((probs, wdl, ml))
-    for t in outs[0]:
-        assert torch.isfinite(t).all()
-    _same_bytes(torch, outs[0], outs[1], "model")
+def test_native_model_forward(runner):
+    """az_nn_model_forward on about 3000 positions"""
+    check(runner, "model/w1/planes/b0/cap0/mask/soft")

@@ -56,7 +56,7 @@ def build_engine(force=False):
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(LIB, "libaz_mcts.so")
-    names = ("kernels", "select_kernels", "backup_kernels", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "nn_othello", "nn_othello_heads", "nn_selftest")
+    names = ("kernels", "select_kernels", "backup_kernels", "rollout_search", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "nn_othello", "nn_othello_heads", "nn_selftest")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = _headers()
     jobs = []
@@ -89,7 +89,10 @@ def build_module(name, source, link_engine, force=False):
                "-I", INC, "-I", pybind11.get_include(), "-I", sysconfig.get_paths()["include"],
                src, "-o", out]
         if link_engine:
-            cmd += ["-L", LIB, "-laz_mcts", "-Wl,-rpath,$ORIGIN/../lib"]
+            # the module uploads roots for the device entry points: the HIP runtime API (host side only) next to the engine
+            rocm = os.path.dirname(os.path.dirname(os.path.realpath(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))))
+            cmd[1:1] = ["-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include")]
+            cmd += ["-L", LIB, "-laz_mcts", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib"]
         _run(cmd)
     return out
 

@@ -270,6 +270,34 @@ int az_mcts_dev_search_more(az_mcts *m, const az_nn_model *model, int n_sims, in
     return dev_search_impl(m, model, n_sims, K, use_table, false, stream);
 }
 
+// One launch of k_rollout_search must stay far below a second for Othello at depth.  Measured on an MI355X
+// (profiles/r21_measure_elo.jsonl: 1000 playouts from the initial position, the longest playouts a game has): a
+// simulation costs a launch 114 us with 1 or 256 Othello trees and 329 us with 4096 (four wavefronts per SIMD, each
+// playing its tree's playout in every lane); Connect4 15-25 us.  256 x 329 us = 84 ms per launch at the worst measured
+// point, and a 1000-playout move is four launches and the bump instead of 4000.
+constexpr int kRolloutChunk = 256;
+
+int az_mcts_dev_rollout_search(az_mcts *m, int n_playout, int sims_per_launch, void *stream)
+{
+    return guarded([&] {
+        require(m != nullptr, "dev_rollout_search: null engine");
+        require(n_playout >= 0, "dev_rollout_search: n_playout must be >= 0");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        // what rollout_common_begin does for the host route, minus the upload: pending resets, the leaf store (its
+        // path rows take the depths past a lane group; the kernel shows every leaf under symmetry id 0 and reads no
+        // id), the tables, room for n_playout expansions per tree - waiting for `s` only when one of them touches
+        // memory the stream's kernels use
+        dev_prepare(m, 1, n_playout, s, false);
+        m->last_select_vl = false;
+        const az::SearchParams p = m->params();
+        const int chunk = sims_per_launch > 0 ? sims_per_launch : kRolloutChunk;
+        for (int at = 0; at < n_playout; at += chunk)
+            az::launch_rollout_search(m->game, m->arena(), m->roots(), m->plain_leaf.view(), p, std::min(chunk, n_playout - at),
+                                      static_cast<uint64_t>(at), m->counters.p, m->err.p, s);
+        if (n_playout > 0) az::launch_bump_call(m->call_ctr.p, s, static_cast<uint64_t>(n_playout));
+    });
+}
+
 // ---- device transposition table ------------------------------------------------------------
 int az_mcts_dev_tt_create(az_mcts *m, int log2_entries)
 {

@@ -1,5 +1,5 @@
 // kernels.h - launch interface between the host engine (engine.hip) and the gfx950 kernels
-// (kernels.hip, select_kernels.hip, backup_kernels.hip and the *_kernels.hip of the drivers).  Everything here is plain data: device pointers and sizes.
+// (kernels.hip, select_kernels.hip, backup_kernels.hip, rollout_search.hip and the *_kernels.hip of the drivers).  Everything here is plain data: device pointers and sizes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,7 +106,7 @@ static_assert(CNT_N == 8, "one counter stripe is one 64-byte line");
 void launch_import(int game, const int8_t *boards, const int32_t *turns, RootState rs, int B, hipStream_t s);
 void launch_set_roots(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, RootState rs,
                       int B, hipStream_t s);
-void launch_bump_call(uint64_t *call_ctr, hipStream_t s);
+void launch_bump_call(uint64_t *call_ctr, hipStream_t s, uint64_t amount = 1);
 // bump_call: the device generator's call counter, incremented once by the launch (nullptr: not)
 // returns the name of the kernel it launched (a string literal)
 const char *launch_select(int game, TreeArena ar, RootState rs, LeafBuf lf, SearchParams p, int K, bool vl,
@@ -133,6 +133,11 @@ void launch_root_stats(int game, TreeArena ar, float *stats, hipStream_t s);
 void launch_init_trees(TreeArena ar, hipStream_t s);
 void launch_rollout(int game, LeafBuf lf, SearchParams p, int B, float *policy, float *d, float *p1w, float *p2w,
                     float *ml, uint8_t *is_term, hipStream_t s);
+// n_sims whole pure-MCTS simulations of every tree in one launch (k_rollout_search, rollout_search.hip): descent, random
+// playout, expansion + backup; simulation i draws from call number *p.call_ptr + call_off + i, the counter itself is not
+// written; lf: only `path` is used (depths past the lane group)
+void launch_rollout_search(int game, TreeArena ar, RootState rs, LeafBuf lf, SearchParams p, int n_sims, uint64_t call_off,
+                           unsigned long long *counters, int *err, hipStream_t s);
 void launch_game_step(int game, uint64_t *bb0, uint64_t *bb1, int32_t *turns, int32_t *aux, const int32_t *actions,
                       uint8_t *done, int32_t *winner, int64_t n, bool reset_finished, hipStream_t s);
 void launch_game_valid_mask(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, const int32_t *aux,

@@ -455,16 +455,7 @@ __global__ void __launch_bounds__(256) k_rollout(LeafBuf lf, SearchParams p, int
     if (!term) {
         GameState s;
         s.bb0 = lf.bb0[t]; s.bb1 = lf.bb1[t]; s.turn = lf.turn[t]; s.aux = lf.aux[t];
-        DevRng g(p.seed, *p.call_ptr, static_cast<uint64_t>(t), 3);
-        int res = G::result(s);
-        for (int ply = 0; res < 0 && ply < 4 * G::CELLS; ++ply) {
-            const int nv = G::num_valid(s);
-            if (nv <= 0) break;
-            const int pick = static_cast<int>((static_cast<uint64_t>(g.next()) * static_cast<uint64_t>(nv)) >> 32);
-            G::step(s, G::nth_valid(s, pick));
-            res = G::result(s);
-        }
-        code = res < 0 ? 0 : res;
+        code = random_playout<G>(s, p.seed, *p.call_ptr, static_cast<uint64_t>(t));
     }
     is_term[t] = term ? 1 : 0;
     d[t] = code == 0 ? 1.0f : 0.0f;
@@ -516,7 +507,7 @@ __global__ void __launch_bounds__(256) k_game_valid_mask(const uint64_t *bb0, co
     mask[gid] = G::valid_in_frame(s, 0, a) ? 1 : 0;
 }
 
-__global__ void k_bump_call(uint64_t *ctr) { *ctr += 1; }
+__global__ void k_bump_call(uint64_t *ctr, uint64_t amount) { *ctr += amount; }
 
 }  // namespace
 
@@ -533,9 +524,9 @@ void launch_set_roots(int game, const uint64_t *bb0, const uint64_t *bb1, const 
     AZ_DISPATCH(game, hipLaunchKernelGGL(k_set_roots<G>, dim3((B + 255) / 256), dim3(256), 0, s, bb0, bb1, turns, rs, B));
 }
 
-void launch_bump_call(uint64_t *call_ctr, hipStream_t s)
+void launch_bump_call(uint64_t *call_ctr, hipStream_t s, uint64_t amount)
 {
-    hipLaunchKernelGGL(k_bump_call, dim3(1), dim3(1), 0, s, call_ctr);
+    hipLaunchKernelGGL(k_bump_call, dim3(1), dim3(1), 0, s, call_ctr, amount);
 }
 
 void launch_export(int game, LeafBuf lf, SearchParams p, int n_leaves, bool gen_sym, int8_t *boards,

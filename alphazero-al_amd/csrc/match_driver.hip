@@ -12,6 +12,7 @@ struct az_match {
     DevBuf<uint64_t> bb0, bb1;
     DevBuf<int32_t> turn, aux, length, actions, winner, counts, moves;
     DevBuf<uint8_t> done, dead;
+    DevBuf<uint8_t> ones;                   // a reset mask that names every tree (fresh-tree players)
     DevBuf<unsigned long long> totals;      // won by +1, won by -1, drawn, finished
     unsigned long long *fin_host = nullptr; // pinned: `finished` as of the newest ply that has completed
     int64_t ply = 0;                        // plies finished: the sampler's call counter and the move record's row
@@ -36,6 +37,16 @@ struct az_match {
         az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
         ply_open = true;
         return true;
+    }
+
+    // The mover's trees start this search empty (game.py:41 resets both players after every move).  Enqueued; the
+    // host-side occupancy bound starts over with the trees, or it would add a search's worth per ply and grow arenas
+    // that never hold more than one search.
+    void reset_mover_trees(hipStream_t s)
+    {
+        az_mcts *m = mover_engine();
+        az::launch_reset_masked(m->arena(), ones.p, s);
+        m->used_bound = 1;
     }
 
     void finish_ply(void *stream)
@@ -127,6 +138,8 @@ int az_match_create(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_confi
         mt->bb0.ensure(B); mt->bb1.ensure(B); mt->turn.ensure(B); mt->aux.ensure(B); mt->length.ensure(B);
         mt->actions.ensure(B, true); mt->winner.ensure(B); mt->done.ensure(B, true); mt->dead.ensure(B);
         mt->counts.ensure(B * engine_p1->geo.actions, true);
+        mt->ones.ensure(B);
+        HIP_OK(hipMemset(mt->ones.p, 1, B));
         mt->totals.ensure(4);
         if (c->record_moves) {
             mt->moves.ensure(B * engine_p1->geo.max_plies);
@@ -171,6 +184,24 @@ int az_match_step(az_match *mt, const az_nn_model *model_p1, const az_nn_model *
         for (int i = 0; i < n_plies; ++i) {
             if (!mt->begin_ply(static_cast<hipStream_t>(stream))) return;
             check_rc(az_mcts_dev_search(mt->mover_engine(), mt->mover > 0 ? model_p1 : model_p2, n_playout, K, use_table, stream));
+            mt->finish_ply(stream);
+        }
+    });
+}
+
+int az_match_step_players(az_match *mt, const az_nn_model *model_p1, const az_nn_model *model_p2, int n_playout_p1, int n_playout_p2,
+                          int K, int use_table, int fresh_trees, int n_plies, void *stream)
+{
+    return guarded([&] {
+        require(mt != nullptr && n_plies >= 0 && n_playout_p1 >= 0 && n_playout_p2 >= 0, "az_match_step_players: bad argument");
+        for (int i = 0; i < n_plies; ++i) {
+            if (!mt->begin_ply(static_cast<hipStream_t>(stream))) return;
+            const int side = mt->mover > 0 ? 0 : 1;
+            const az_nn_model *model = side == 0 ? model_p1 : model_p2;
+            const int n_playout = side == 0 ? n_playout_p1 : n_playout_p2;
+            if ((fresh_trees >> side) & 1) mt->reset_mover_trees(static_cast<hipStream_t>(stream));
+            if (model != nullptr) check_rc(az_mcts_dev_search(mt->mover_engine(), model, n_playout, K, use_table, stream));
+            else check_rc(az_mcts_dev_rollout_search(mt->mover_engine(), n_playout, 0, stream));
             mt->finish_ply(stream);
         }
     });

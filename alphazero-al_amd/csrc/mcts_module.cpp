@@ -3,6 +3,7 @@
 // include/az_mcts.h.  Same class / method / keyword names, same dtypes, shapes and error
 // behaviour, so `from src import mcts_cpp` in the reference's src/MCTS_cpp.py, player.py and
 // GUI code binds to the HIP engine unchanged.  This file holds no search logic.
+#include <hip/hip_runtime_api.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -47,6 +48,36 @@ private:
     az_mcts *h_ = nullptr;
 };
 
+// a host array in device memory for the length of one call (the device entry points read their roots from HBM)
+struct Upload {
+    void *p = nullptr;
+    Upload(const void *src, size_t bytes)
+    {
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) throw std::runtime_error("search: hipMalloc failed");
+        if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(p);
+            throw std::runtime_error("search: upload of the roots failed");
+        }
+    }
+    ~Upload() { (void)hipFree(p); }
+    Upload(const Upload &) = delete;
+    Upload &operator=(const Upload &) = delete;
+};
+
+// RolloutEvaluator with device_rng and one_launch: roots into the engine, the whole search as one kernel per chunk
+// (az_mcts_dev_rollout_search), then wait - the blocking call the reference's search() is
+int rollout_one_launch(az_mcts *h, const int8_t *boards, size_t board_bytes, const int *turns, size_t n, int n_playout)
+{
+    int rc = az_mcts_dev_prepare(h, 1, 0);              // waits for the device and makes the engine's device current
+    if (rc != AZ_OK) return rc;
+    Upload b(boards, board_bytes), t(turns, n * sizeof(int));
+    if ((rc = az_mcts_dev_import_roots(h, static_cast<const int8_t *>(b.p), static_cast<const int32_t *>(t.p), nullptr)) != AZ_OK) return rc;
+    if ((rc = az_mcts_dev_rollout_search(h, n_playout, 0, nullptr)) != AZ_OK) return rc;
+    if ((rc = az_mcts_dev_check(h, nullptr)) != AZ_OK) return rc;       // asks for the error word ...
+    if (hipStreamSynchronize(nullptr) != hipSuccess) throw std::runtime_error("search: the device reported an error");
+    return az_mcts_dev_check(h, nullptr);                               // ... and reads it once it has arrived
+}
+
 std::vector<py::ssize_t> leaf_shape(py::ssize_t n, const std::vector<py::ssize_t> &board)
 {
     std::vector<py::ssize_t> s{n};
@@ -63,12 +94,15 @@ void register_game(py::module_ &m, const char *suffix)
     // a tag object here - the random playouts run inside the engine.
     // `device_rng` (an addition): False = playout moves from the reference's random stream on the host
     // (bit-exact, az_mcts_search_rollout), True = playouts on the device (az_mcts_search_rollout_dev).
-    struct IEval { bool device_rng = false; };
+    // `one_launch` (an addition, read only with device_rng): the same search as one kernel per chunk of simulations
+    // (az_mcts_dev_rollout_search) - same trees, counts and statistics as device_rng alone.
+    struct IEval { bool device_rng = false; bool one_launch = false; };
     struct RolloutEval : IEval {};
     py::class_<IEval>(m, (std::string("IEvaluator_") + suffix).c_str());
     py::class_<RolloutEval, IEval>(m, (std::string("RolloutEvaluator_") + suffix).c_str())
         .def(py::init<>())
-        .def_readwrite("device_rng", &RolloutEval::device_rng);
+        .def_readwrite("device_rng", &RolloutEval::device_rng)
+        .def_readwrite("one_launch", &RolloutEval::one_launch);
 
     py::class_<BM>(m, cls.c_str())
         .def(py::init<int>(), py::arg("n_envs"))
@@ -238,8 +272,13 @@ void register_game(py::module_ &m, const char *suffix)
                      auto *pin = static_cast<const int8_t *>(bi.ptr);
                      auto *ptn = turns.data();
                      py::gil_scoped_release rel;
-                     rc = ev.device_rng ? az_mcts_search_rollout_dev(self.h(), pin, ptn, n, n_playout)
-                                        : az_mcts_search_rollout(self.h(), pin, ptn, n, n_playout);
+                     if (ev.device_rng && ev.one_launch) {
+                         if (n_playout < 0) throw std::runtime_error("search: n_playout must be >= 0");
+                         rc = rollout_one_launch(self.h(), pin, static_cast<size_t>(n) * BM::board_size(), ptn, static_cast<size_t>(n), n_playout);
+                     } else {
+                         rc = ev.device_rng ? az_mcts_search_rollout_dev(self.h(), pin, ptn, n, n_playout)
+                                            : az_mcts_search_rollout(self.h(), pin, ptn, n, n_playout);
+                     }
                  }
                  check(rc);
              },

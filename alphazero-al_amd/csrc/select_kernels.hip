@@ -5,70 +5,6 @@
 namespace az {
 namespace {
 
-template <int L>
-__device__ __forceinline__ HotRec group_bcast(const HotRec &c, int src)
-{
-    HotRec r;
-    r.n_visits   = __shfl(c.n_visits, src, L);
-    r.n_inflight = __shfl(c.n_inflight, src, L);
-    r.w_p1       = __shfl(c.w_p1, src, L);
-    r.w_p2       = __shfl(c.w_p2, src, L);
-    r.m_sum      = __shfl(c.m_sum, src, L);
-    r.prior      = __shfl(c.prior, src, L);
-    r.child_off  = __shfl(c.child_off, src, L);
-    r.meta       = static_cast<uint32_t>(__shfl(static_cast<int>(c.meta), src, L));
-    return r;
-}
-
-// ---- one tree per wavefront (Othello: 64 lanes, up to 33 edges): the group-wide exchanges without the LDS crossbar.
-// A __shfl with a runtime lane is a ds_bpermute (address VGPR, LDS round trip, wait); in a loop bounded by the edge
-// count that is one dependent round trip per edge.  With the whole wavefront as the group the source lane is
-// wave-uniform, so v_readlane_b32 (a scalar result, no LDS) does it, and reductions run on the DPP network.
-
-// maximum of an unsigned key over the wavefront (0 = the identity of lanes switched off)
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
-{
-    auto mv = [](unsigned x, auto ctrl, auto rmask) {
-        return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), decltype(ctrl)::value, decltype(rmask)::value, 0xf, false));
-    };
-    auto mx = [](unsigned a, unsigned b) { return a > b ? a : b; };
-    v = mx(v, mv(v, std::integral_constant<int, 0xB1>{}, std::integral_constant<int, 0xf>{}));     // quad_perm [1,0,3,2]
-    v = mx(v, mv(v, std::integral_constant<int, 0x4E>{}, std::integral_constant<int, 0xf>{}));     // quad_perm [2,3,0,1]
-    v = mx(v, mv(v, std::integral_constant<int, 0x141>{}, std::integral_constant<int, 0xf>{}));    // row_half_mirror
-    v = mx(v, mv(v, std::integral_constant<int, 0x140>{}, std::integral_constant<int, 0xf>{}));    // row_mirror
-    v = mx(v, mv(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{}));    // row_bcast:15 into rows 1 and 3
-    v = mx(v, mv(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{}));    // row_bcast:31 into rows 2 and 3
-    return static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
-}
-// strict '>' over ascending edges == highest score, lowest lane on ties; NaN and -inf never win (MCTS.h:172,226-231):
-// an order-preserving integer key of the score (0 for lanes that cannot win), its wave-wide maximum, the lowest lane
-// that holds it.  Returns -1 when no lane can win.
-__device__ __forceinline__ int wave_argmax(float score, bool can_win)
-{
-    const uint32_t b = __float_as_uint(score);
-    uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);             // monotone in the float order; -inf -> 0x007fffff
-    if (!can_win || !(score > -INFINITY)) key = 0u;                         // NaN fails the comparison too
-    const unsigned mx = wave_max_u32(key);
-    if (mx == 0u) return -1;
-    const unsigned long long hit = __ballot(key == mx);
-    return static_cast<int>(__builtin_ctzll(hit));
-}
-template <>
-__device__ __forceinline__ HotRec group_bcast<WAVE>(const HotRec &c, int src)
-{
-    const int u = __builtin_amdgcn_readfirstlane(src);                      // the winner's lane is the same in every lane
-    HotRec r;
-    r.n_visits   = __builtin_amdgcn_readlane(c.n_visits, u);
-    r.n_inflight = __builtin_amdgcn_readlane(c.n_inflight, u);
-    r.w_p1       = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.w_p1), u));
-    r.w_p2       = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.w_p2), u));
-    r.m_sum      = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.m_sum), u));
-    r.prior      = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.prior), u));
-    r.child_off  = __builtin_amdgcn_readlane(c.child_off, u);
-    r.meta       = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(c.meta), u));
-    return r;
-}
-
 // ------------------------------------------------------------------ selection
 
 // MCTS.h:242-322 (VL=false) / 443-545 (VL=true) for K consecutive descents of every tree,

@@ -167,6 +167,7 @@ PROTOTYPES = (
     ("az_mcts_dev_live_leaves", i32, [vp, i32, vp, vp, vp]),
     ("az_mcts_dev_search", i32, [vp, vp, i32, i32, i32, vp]),
     ("az_mcts_dev_search_more", i32, [vp, vp, i32, i32, i32, vp]),
+    ("az_mcts_dev_rollout_search", i32, [vp, i32, i32, vp]),
     ("az_selfplay_create", i32, [vp, P(SelfPlayConfig), P(vp)]),
     ("az_selfplay_destroy", None, [vp]),
     ("az_selfplay_step", i32, [vp, vp, i32, i32, i32, i32, vp]),
@@ -184,6 +185,7 @@ PROTOTYPES = (
     ("az_match_destroy", None, [vp]),
     ("az_match_set_positions", i32, [vp, vp, vp, vp]),
     ("az_match_step", i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    ("az_match_step_players", i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     ("az_match_begin_ply", i32, [vp, vp, P(i32)]),
     ("az_match_finish_ply", i32, [vp, vp]),
     ("az_match_set_action_tape", i32, [vp, vp, i64]),

@@ -20,8 +20,13 @@ Departures from the reference, both deliberate:
     goes on searching finished games and discards the move.
 
 `select_best(net, best_net, n_games, threshold)` is pipeline.py:241-262 without the bookkeeping: two halves with
-colours swapped, `gate_win_rate` for the arithmetic.  The Elo rating loop against a rollout player, logging and
-the best-network bookkeeping stay with the caller.
+colours swapped, `gate_win_rate` for the arithmetic.
+
+The rating step (`TrainPipeline.update_elo`, pipeline.py:219-239) is here too: `RolloutPlayer` marks a side as the
+pure-MCTS rollout player (`MCTSPlayer`, player.py:73-103; searched by k_rollout_search, one launch per search),
+`fresh_trees` makes a side start every search from empty trees as `Game.play` does (game.py:41), and
+`rating_games(net, ...)` plays the two colour-swapped matches; src/elo.py turns their results into ratings.  Logging
+and the best-network bookkeeping stay with the caller.
 """
 import ctypes as C
 
@@ -30,6 +35,7 @@ import torch
 
 from src import fused as F
 from src.abi import MatchConfig, lib as match_lib      # noqa: F401  (match_lib: the name callers written before src/abi.py use)
+from src.MCTS_cpp import BatchedMCTS
 from src.selfplay import _reserve_arenas, _setup_search
 
 
@@ -49,8 +55,31 @@ def gate_decision(results_first, results_second, n_games, threshold):
     return bool(rate >= threshold), rate
 
 
+class RolloutPlayer:
+    """Marker for `EvaluationMatch`: this side is the reference's pure-MCTS player (`MCTSPlayer`, player.py:73-103) -
+    uniform priors, the value of a leaf is the result of a random playout.  Defaults: MCTSPlayer's n_playout and the
+    c_puct that `update_elo` passes (pipeline.py:233)."""
+
+    def __init__(self, n_playout=1000, c_puct=1.0):
+        self.n_playout, self.c_puct = int(n_playout), float(c_puct)
+
+
 class _Side:
     """One player's engine and evaluator binding (what selfplay._setup_search builds)."""
+
+
+def _setup_rollout(self, player, n_games, seed, game, device):
+    """A rollout player's side: an engine only, configured as MCTSPlayer configures it (player.py:84-88)."""
+    self.B, self.n_playout, self.vl_batch = int(n_games), player.n_playout, 1
+    self.game, self.game_id = game, 0 if game == "Connect4" else 1
+    self.MAX_PLIES = 42 if game == "Connect4" else 126
+    with torch.cuda.device(device):
+        self.search = BatchedMCTS(self.B, c_init=player.c_puct, c_base=500, alpha=0, n_playout=player.n_playout, game_name=game,
+                                  noise_epsilon=0.0, fpu_reduction=0.0, use_symmetry=False)
+    self.search.seed(seed)
+    self.fused = None
+    self.h = C.c_void_p(self.search.mcts.handle)
+    self.device = device
 
 
 def _pair(v):
@@ -63,26 +92,40 @@ class EvaluationMatch:
     fpu_reduction.  `c_init` may be a pair (player +1, player -1): search parameters live in each engine's own
     config.  positions: (bb_p1, bb_p2, turns) as integer arrays of n_games entries, one side to move throughout -
     an opening suite instead of the initial position.  `play()` runs to the end and returns the winners
-    (int32, +1 / -1 / 0) like the reference; `step(n)`, `remaining()`, `results()`, `moves()` are the pieces."""
+    (int32, +1 / -1 / 0) like the reference; `step(n)`, `remaining()`, `results()`, `moves()` are the pieces.
+    Either side may be a `RolloutPlayer` (its own n_playout and c_puct; the other arguments configure network sides).
+    fresh_trees (a flag or a pair): that side starts every one of its searches from empty trees instead of the
+    subtree its re-rooting kept (game.py:41)."""
 
     def __init__(self, net_p1, net_p2, n_games, n_playout=200, vl_batch=1, c_init=1.25, c_base=500, alpha=0.3,
                  eval_noise_eps=0.05, eval_temp=0.2, use_symmetry=True, mlh_slope=0.0, mlh_cap=0.2,
                  score_utility_factor=0.0, score_scale=8.0, value_decay=1.0, fpu_reduction=0.4, seed=0, game="Connect4",
-                 table_log2=0, positions=None, record_moves=False, reserve_slots=None):
+                 table_log2=0, positions=None, record_moves=False, reserve_slots=None, fresh_trees=False):
         self._mt = None
         self.B, self.n_playout, self.vl_batch = int(n_games), int(n_playout), int(vl_batch)
         self.game = game
-        self.sides = []
-        for i, (net, ci) in enumerate(zip((net_p1, net_p2), _pair(c_init))):
+        self.fresh_trees = sum((1 << i) for i, f in enumerate(_pair(fresh_trees)) if f)
+        self.sides = [None, None]
+        nets = (net_p1, net_p2)
+        for i, (net, ci) in enumerate(zip(nets, _pair(c_init))):
+            if isinstance(net, RolloutPlayer):
+                continue
             s = _Side()
             _setup_search(s, net, n_games, n_playout, vl_batch, ci, c_base, alpha, eval_noise_eps, fpu_reduction, use_symmetry,
                           mlh_slope, mlh_cap, value_decay, eval_temp, 0, eval_temp, int(seed) + i, table_log2, game,
                           score_utility_factor, score_scale)
+            self.sides[i] = s
+        dev = next((s.device for s in self.sides if s is not None), torch.device("cuda", torch.cuda.current_device()))
+        for i, net in enumerate(nets):                        # rollout players go where the network side is
+            if self.sides[i] is None:
+                self.sides[i] = _Side()
+                _setup_rollout(self.sides[i], net, n_games, int(seed) + i, game, dev)
+        for s in self.sides:
             _reserve_arenas(s, reserve_slots)
-            self.sides.append(s)
         self.device = self.sides[0].device
         self.MAX_PLIES = self.sides[0].MAX_PLIES
         self.A = self.sides[0].search.action_size
+        self._ones = None                                     # reset mask of the begin / search / finish route
         self.L = F.lib()
         self.config = MatchConfig(float(eval_temp), int(bool(record_moves)))
         self.record_moves = bool(record_moves)
@@ -124,20 +167,32 @@ class EvaluationMatch:
         F.check(self.L.az_match_set_action_tape(self._mt, t.data_ptr(), t.shape[0]))
 
     def native_models(self):
-        """(model of +1, model of -1) when both evaluators have a native model object, else None."""
+        """(model of +1, model of -1) when every network side has a native model object (None stands for a rollout
+        player's side), else None."""
         models = []
         for s in self.sides:
+            if s.fused is None:
+                models.append(None)
+                continue
             s.fused._sync_fast_net()
-            models.append(s.fused._native_model())
-        return None if any(m is None for m in models) else tuple(models)
+            m = s.fused._native_model()
+            if m is None:
+                return None
+            models.append(m)
+        return tuple(models)
 
     def step(self, n=1):
         """n plies in every game that is still running."""
         models = self.native_models()
         s = F._stream()
+        nets = [x.fused for x in self.sides if x.fused is not None]
+        table = 1 if nets and nets[0].table_log2 else 0
         with torch.cuda.device(self.device):
+            if models is not None and (self.fresh_trees or None in models):
+                F.check(self.L.az_match_step_players(self._mt, models[0], models[1], self.sides[0].n_playout, self.sides[1].n_playout,
+                                                     max(1, self.vl_batch), table, self.fresh_trees, int(n), s))
+                return
             if models is not None:
-                table = 1 if self.sides[0].fused.table_log2 else 0
                 F.check(self.L.az_match_step(self._mt, models[0], models[1], self.n_playout, max(1, self.vl_batch), table,
                                              int(n), s))
                 return
@@ -146,7 +201,16 @@ class EvaluationMatch:
                 F.check(self.L.az_match_begin_ply(self._mt, s, C.byref(mover)))
                 if mover.value == 0:
                     return
-                self.sides[0 if mover.value > 0 else 1].fused.search(self.n_playout, self.vl_batch)
+                i = 0 if mover.value > 0 else 1
+                side = self.sides[i]
+                if (self.fresh_trees >> i) & 1:
+                    if self._ones is None:
+                        self._ones = torch.ones(self.B, dtype=torch.uint8, device=self.device)
+                    F.check(self.L.az_mcts_dev_reset_masked(side.h, self._ones.data_ptr(), s))
+                if side.fused is None:
+                    F.check(self.L.az_mcts_dev_rollout_search(side.h, side.n_playout, 0, s))
+                else:
+                    side.fused.search(self.n_playout, self.vl_batch)
                 F.check(self.L.az_match_finish_ply(self._mt, s))
 
     def remaining(self):
@@ -182,6 +246,21 @@ class EvaluationMatch:
 
     def engine_counters(self):
         return tuple(F.counters(s.h) for s in self.sides)
+
+
+def rating_games(net, n_games, n_playout, pure_mcts_n_playout, **kw):
+    """The games of one rating round (`TrainPipeline.update_elo`, pipeline.py:219-239): `n_games` with `net` as +1
+    against the rollout player, then `n_games` with the colours swapped, both sides starting every search from empty
+    trees.  Returns (winners with net as +1, winners with net as -1), int32 +1 / -1 / 0 each.  The network side
+    searches as `update_elo` configures it - no root noise, the most visited move, c_base 500; other keyword
+    arguments go to EvaluationMatch (the second match uses seed + 2).  n_games = 1 is the reference's round; with
+    more, the rollout player's randomness makes the games differ.  src/elo.py's `rate` turns the pair into ratings."""
+    seed = int(kw.pop("seed", 0))
+    kw = dict(dict(eval_noise_eps=0.0, eval_temp=0.0, c_base=500, fresh_trees=True), **kw)
+    rollout = RolloutPlayer(pure_mcts_n_playout, 1.0)
+    first = EvaluationMatch(net, rollout, n_games, n_playout=n_playout, seed=seed, **kw).play()
+    second = EvaluationMatch(rollout, net, n_games, n_playout=n_playout, seed=seed + 2, **kw).play()
+    return first, second
 
 
 def select_best(net, best_net, n_games, threshold, **kw):

@@ -249,6 +249,17 @@ int az_mcts_dev_search(az_mcts *m, const struct az_nn_model *model, int n_playou
 int az_mcts_dev_search_more(az_mcts *m, const struct az_nn_model *model, int n_sims, int K, int use_table,
                             void *stream);
 
+/* BatchedMCTS::search with RolloutEvaluator (BatchedMCTS.h:339-407) on the roots set by az_mcts_dev_set_roots /
+ * import_roots: n_playout plain simulations per tree, playouts and root noise from the device generator, as ONE
+ * search kernel per chunk of sims_per_launch simulations (<= 0: the library's default) plus the call counter's
+ * bump - same trees, counts and root statistics, bit for bit, as az_mcts_search_rollout_dev from the same seed
+ * and call counter.  Reserves its own arena room (n_playout x the game's largest block of children); only
+ * enqueues on `stream` unless a buffer must grow.  No selection or backup launch is issued: az_mcts_counters [6]
+ * and [7] do not move, [0..5] count the same work as the launch-per-simulation route.  The leaves stay in
+ * registers: what az_mcts_dev_leaves / az_mcts_dev_leaf_syms report after this call is unspecified.
+ * AZ_ERR_ARG: n_playout < 0; AZ_ERR_CAPACITY arrives through az_mcts_dev_check. */
+int az_mcts_dev_rollout_search(az_mcts *m, int n_playout, int sims_per_launch, void *stream);
+
 /* ---- self-play from C: whole plies, recording included (alphazero-al_amd/csrc/selfplay_kernels.hip) -------
  * The reference's driver is Python per game and per ply (src/game.py:65-164 with src/player.py:333-375);
  * here a driver object owns the positions, ply counters, trajectories and the store of finished games in
@@ -455,6 +466,15 @@ int az_match_set_positions(az_match *mt, const uint64_t *bb_p1, const uint64_t *
  * remaining plies are not played: the call changes nothing.  AZ_ERR_ARG: a null model. */
 int az_match_step(az_match *mt, const struct az_nn_model *model_p1, const struct az_nn_model *model_p2, int n_playout,
                   int K, int use_table, int n_plies, void *stream);
+/* az_match_step with players of either kind: a NULL model makes that side the rollout player (searched with
+ * az_mcts_dev_rollout_search, n_playout_pX simulations; K and use_table apply to network sides only).
+ * fresh_trees: bit 0 player +1, bit 1 player -1 - that player's engine starts every one of its searches from
+ * empty trees (game.py:41, player.py:102,279-281) instead of the subtree kept by the re-rooting; the reset is
+ * enqueued in front of the search (az_mcts_dev_reset_masked with a mask of ones that the match owns).
+ * AZ_ERR_ARG: a null match, a negative count. */
+int az_match_step_players(az_match *mt, const struct az_nn_model *model_p1, const struct az_nn_model *model_p2,
+                          int n_playout_p1, int n_playout_p2, int K, int use_table, int fresh_trees,
+                          int n_plies, void *stream);
 /* The two halves of a ply, for an evaluator that is not an az_nn_model: begin_ply puts the positions into the
  * mover's engine as roots and reports the mover (+1: search engine_p1, -1: engine_p2; 0: the match is over, nothing
  * was done and finish_ply will do nothing); the caller searches that engine (az_mcts_dev_prepare_stream and the

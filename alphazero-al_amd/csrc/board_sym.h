@@ -46,4 +46,38 @@ __host__ __device__ inline uint64_t othello_sym(uint64_t b, int sym)
     return b;
 }
 
+// ---- actions under the same symmetries.  All of them are involutions, so one map serves both directions.
+// Connect4, symmetry 1: column a -> 6 - a
+__host__ __device__ inline int mirror_action(int a, int sym) { return sym ? 6 - a : a; }
+
+// Othello: square a = 8 * row + col moves as the stones do; the pass (64) stays
+__host__ __device__ inline int othello_sym_action(int a, int sym)
+{
+    if (a >= 64 || sym == 0) return a;
+    const int r = a >> 3, c = a & 7;
+    if (sym == 2) return 63 - a;
+    if (sym == 6) return c * 8 + r;
+    if (sym == 7) return (7 - c) * 8 + (7 - r);
+    return a;
+}
+
+// ---- a game's symmetry ensemble (symmetry.py:21,46; the order of az_replay_dev_batch): member j of
+// az_game_num_augment(game) is Connect4's symmetry j and Othello's {0, 2, 6, 7}[j].  G: a game of games.h.
+__host__ __device__ inline int othello_ensemble_sym(int j) { return j == 0 ? 0 : (j == 1 ? 2 : (j == 2 ? 6 : 7)); }
+
+template <class G>
+__host__ __device__ inline uint64_t ensemble_board(uint64_t b, int j)
+{
+    if (G::GAME_ID == 0) return j ? mirror_columns(b) : b;
+    return othello_sym(b, othello_ensemble_sym(j));
+}
+
+// action a of the game's frame in member j's frame, and back
+template <class G>
+__host__ __device__ inline int ensemble_action(int a, int j)
+{
+    if (G::GAME_ID == 0) return mirror_action(a, j);
+    return othello_sym_action(a, othello_ensemble_sym(j));
+}
+
 }  // namespace az

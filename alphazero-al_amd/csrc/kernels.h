@@ -235,26 +235,41 @@ void launch_sp_export(int game, SpExport a, hipStream_t s);
 // ---- evaluation matches between two engines (match_kernels.hip) -------------------------------------
 // One ply's tail of a match (k_match_ply; az_match_* in az_mcts.h): the mover engine's root counts -> the move, the
 // stepped position, what both engines' re-rooting and resets read, results, the move record, totals.
+// A player's trees of one game are its team: tree j of game g is tree g * trees + j of that player's engine; in an
+// ensemble team, tree j works in the frame of the game's j-th symmetry (board_sym.h).
+struct MatchTeam {
+    int32_t *actions;        // [n * trees] out: what this engine's prune reads, the move in each tree's own frame
+    uint8_t *done;           // [n * trees] out: 1 iff the tree's game ended on this ply (this engine's reset reads it)
+    int      trees, ensemble;
+};
 struct MatchPly {
-    const int32_t *counts;   // [n][A] root visit counts of the engine that searched
+    const int32_t *counts;   // [n * trees][A] root visit counts of the engine that searched (trees: the mover's)
+    int      trees, ensemble;    // the mover's team: its rows are summed per game, through the symmetries of an ensemble
     const int32_t *tape;     // [n] or nullptr: this ply's actions, read instead of picked
     uint64_t *bb0, *bb1;     // [n] positions, stepped in place
     int32_t  *turn, *aux;
     int32_t  *length;        // [n] plies played
     uint8_t  *dead;          // [n] the game is over: action -1 from then on
-    int32_t  *actions;       // [n] out: what both prunes read
-    uint8_t  *done;          // [n] out: 1 iff the game ended on this ply (both resets read it)
+    MatchTeam team[2];       // the trees of player +1 / -1
     int32_t  *winner;        // [n] +1 / -1 / 0, written when the game ends
-    int32_t  *moves;         // [max_plies][n] or nullptr: row `ply` is written
+    int32_t  *moves;         // [max_plies][n] or nullptr: row `ply` is written (the game's frame)
     unsigned long long *totals;   // won by +1, won by -1, drawn, finished
     float    temperature;
     uint64_t seed, ply;      // generator key: engine_p1's seed and the match's ply counter
-    int64_t  n;
+    int64_t  n;              // games
 };
 void launch_match_ply(int game, MatchPly a, hipStream_t s);
 // the pick alone on caller-supplied counts (az_match_sample): counts [n][A] -> actions [n], same generator stream
 void launch_match_sample(int game, const int32_t *counts, float temperature, uint64_t seed, uint64_t ply, int32_t *actions,
                          int64_t n, hipStream_t s);
+// the team form of it (az_match_team_sample): counts [n * trees][A] -> summed [n][A] (or nullptr), actions [n], and the
+// move in the frames of a team of out_trees trees, tree_actions [n * out_trees] (or nullptr)
+void launch_match_team_sample(int game, const int32_t *counts, int trees, int ensemble, float temperature, uint64_t seed,
+                              uint64_t ply, int32_t *summed, int32_t *actions, int out_trees, int out_ensemble,
+                              int32_t *tree_actions, int64_t n, hipStream_t s);
+// positions [n] -> a team's roots [n * trees], symmetrised for an ensemble (k_match_team_roots); rs.aux may be nullptr
+void launch_match_team_roots(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, int trees, int ensemble,
+                             RootState rs, int64_t n, hipStream_t s);
 
 // ---- training batches from the replay ring (replay_kernels.hip) -------------------------------------
 // Ring rows -> one augmented batch (k_replay_batch; az_replay_batch in az_mcts.h).  Sample b of the batch is the

@@ -2,17 +2,21 @@
 // Two engines, two models, one set of games (pipeline.py:264-335): the side to move searches in its own engine, the
 // tail of the ply is k_match_ply (match_kernels.hip), then BOTH engines re-root with the move and reset the trees of
 // the games that ended.  Same conventions as the self-play driver (selfplay_driver.hip): everything between calls
-// lives in the object.
+// lives in the object.  A player may bring a team of trees per game (root-parallel play, the symmetry ensemble;
+// player.py:248-329): engine e then holds B * T[e] trees, tree j of game g is its tree g * T[e] + j.
 #include "engine_internal.h"
 
 struct az_match {
     az_mcts *e[2] = {nullptr, nullptr};     // [0] the trees of player +1, [1] of player -1
     az_match_config c;
-    int B = 0;
+    int B = 0;                              // games
+    int T[2] = {1, 1};                      // trees per game of each player
+    int ens[2] = {0, 0};                    // that player's trees are the game's symmetry ensemble
     DevBuf<uint64_t> bb0, bb1;
-    DevBuf<int32_t> turn, aux, length, actions, winner, counts, moves;
-    DevBuf<uint8_t> done, dead;
-    DevBuf<uint8_t> ones;                   // a reset mask that names every tree (fresh-tree players)
+    DevBuf<int32_t> turn, aux, length, winner, counts, moves;
+    DevBuf<int32_t> actions[2];             // per engine and tree: the move in the tree's frame
+    DevBuf<uint8_t> done[2], dead;          // done: per engine and tree
+    DevBuf<uint8_t> ones;                   // a reset mask that names every tree of either engine (fresh-tree players)
     DevBuf<unsigned long long> totals;      // won by +1, won by -1, drawn, finished
     unsigned long long *fin_host = nullptr; // pinned: `finished` as of the newest ply that has completed
     int64_t ply = 0;                        // plies finished: the sampler's call counter and the move record's row
@@ -34,7 +38,9 @@ struct az_match {
         drv.require("az_match");
         az_mcts *m = mover_engine();
         HIP_OK(hipSetDevice(m->device));
-        az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
+        const int side = mover > 0 ? 0 : 1;
+        if (T[side] == 1 && !ens[side]) az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
+        else az::launch_match_team_roots(m->game, bb0.p, bb1.p, turn.p, T[side], ens[side], m->roots(), B, s);
         ply_open = true;
         return true;
     }
@@ -59,20 +65,22 @@ struct az_match {
         ply_open = false;
         az::launch_counts(m->game, m->arena(), counts.p, s);
         az::MatchPly p{};
-        p.counts = counts.p;
+        const int side = mover > 0 ? 0 : 1;
+        p.counts = counts.p; p.trees = T[side]; p.ensemble = ens[side];
         p.tape = drv.row(B);
         p.bb0 = bb0.p; p.bb1 = bb1.p; p.turn = turn.p; p.aux = aux.p; p.length = length.p; p.dead = dead.p;
-        p.actions = actions.p; p.done = done.p; p.winner = winner.p;
+        for (int i = 0; i < 2; ++i) p.team[i] = az::MatchTeam{actions[i].p, done[i].p, T[i], ens[i]};
+        p.winner = winner.p;
         p.moves = c.record_moves ? moves.p : nullptr;
         p.totals = totals.p; p.temperature = c.temperature;
         p.seed = e[0]->dev_seed; p.ply = static_cast<uint64_t>(ply); p.n = B;
         az::launch_match_ply(m->game, p, s);
         drv.advance();
-        for (az_mcts *x : e) {
-            x->prune_on(actions.p, nullptr, true, x->replay_noise, s);
-            az::launch_bump_call(x->call_ctr.p, s);
+        for (int i = 0; i < 2; ++i) {
+            e[i]->prune_on(actions[i].p, nullptr, true, e[i]->replay_noise, s);
+            az::launch_bump_call(e[i]->call_ctr.p, s);
         }
-        for (az_mcts *x : e) az::launch_reset_masked(x->arena(), done.p, s);
+        for (int i = 0; i < 2; ++i) az::launch_reset_masked(e[i]->arena(), done[i].p, s);
         HIP_OK(hipMemcpyAsync(fin_host, totals.p + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         ++ply;
         mover = -mover;
@@ -120,38 +128,63 @@ struct az_match {
     }
 };
 
+static void create_match(const char *who, az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, const az_match_teams *t,
+                         az_match **out)
+{
+    const std::string w = std::string(who) + ": ";
+    require(engine_p1 != nullptr && engine_p2 != nullptr && c != nullptr && t != nullptr && out != nullptr, w + "null argument");
+    require(engine_p1 != engine_p2, w + "the two players need an engine each");
+    require(engine_p1->game == engine_p2->game, w + "the engines play different games");
+    require(engine_p1->device == engine_p2->device, w + "the engines are on different devices");
+    require(t->trees_p1 >= 1 && t->trees_p2 >= 1, w + "a player needs at least one tree per game");
+    require(engine_p1->B % t->trees_p1 == 0 && engine_p2->B % t->trees_p2 == 0, w + "an engine's n_envs is no multiple of its trees per game");
+    require(engine_p1->B / t->trees_p1 == engine_p2->B / t->trees_p2, w + "the engines differ in n_envs (games)");
+    const int n_sym = az::replay_num_augment(engine_p1->game);
+    require((t->ensemble_p1 == 0 || t->trees_p1 == n_sym) && (t->ensemble_p2 == 0 || t->trees_p2 == n_sym),
+            w + "a symmetry ensemble has one tree per symmetry of the game (az_game_num_augment)");
+    HIP_OK(hipSetDevice(engine_p1->device));
+    auto mt = std::make_unique<az_match>();
+    mt->e[0] = engine_p1; mt->e[1] = engine_p2; mt->c = *c;
+    mt->T[0] = t->trees_p1; mt->T[1] = t->trees_p2;
+    mt->ens[0] = t->ensemble_p1 != 0; mt->ens[1] = t->ensemble_p2 != 0;
+    mt->B = engine_p1->B / t->trees_p1;
+    const size_t B = static_cast<size_t>(mt->B);
+    const size_t trees = static_cast<size_t>(std::max(engine_p1->B, engine_p2->B));
+    mt->bb0.ensure(B); mt->bb1.ensure(B); mt->turn.ensure(B); mt->aux.ensure(B); mt->length.ensure(B);
+    mt->winner.ensure(B); mt->dead.ensure(B);
+    for (int i = 0; i < 2; ++i) {
+        mt->actions[i].ensure(static_cast<size_t>(mt->e[i]->B), true);
+        mt->done[i].ensure(static_cast<size_t>(mt->e[i]->B), true);
+    }
+    mt->counts.ensure(trees * engine_p1->geo.actions, true);
+    mt->ones.ensure(trees);
+    HIP_OK(hipMemset(mt->ones.p, 1, trees));
+    mt->totals.ensure(4);
+    if (c->record_moves) {
+        mt->moves.ensure(B * engine_p1->geo.max_plies);
+        HIP_OK(hipMemset(mt->moves.p, 0xFF, B * engine_p1->geo.max_plies * sizeof(int32_t)));      // -1: nothing played
+    }
+    HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&mt->fin_host), sizeof(unsigned long long), hipHostMallocDefault));
+    mt->drv.create_events();
+    const az::GameState st = start_state(engine_p1->game);
+    const std::vector<uint64_t> h0(B, st.bb0), h1(B, st.bb1);
+    mt->load(h0.data(), h1.data(), 1);
+    *out = mt.release();
+}
+
 extern "C" {
 
 int az_match_create(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, az_match **out)
 {
     return guarded([&] {
-        require(engine_p1 != nullptr && engine_p2 != nullptr && c != nullptr && out != nullptr, "az_match_create: null argument");
-        require(engine_p1 != engine_p2, "az_match_create: the two players need an engine each");
-        require(engine_p1->game == engine_p2->game, "az_match_create: the engines play different games");
-        require(engine_p1->B == engine_p2->B, "az_match_create: the engines differ in n_envs");
-        require(engine_p1->device == engine_p2->device, "az_match_create: the engines are on different devices");
-        HIP_OK(hipSetDevice(engine_p1->device));
-        auto mt = std::make_unique<az_match>();
-        mt->e[0] = engine_p1; mt->e[1] = engine_p2; mt->c = *c;
-        mt->B = engine_p1->B;
-        const size_t B = static_cast<size_t>(mt->B);
-        mt->bb0.ensure(B); mt->bb1.ensure(B); mt->turn.ensure(B); mt->aux.ensure(B); mt->length.ensure(B);
-        mt->actions.ensure(B, true); mt->winner.ensure(B); mt->done.ensure(B, true); mt->dead.ensure(B);
-        mt->counts.ensure(B * engine_p1->geo.actions, true);
-        mt->ones.ensure(B);
-        HIP_OK(hipMemset(mt->ones.p, 1, B));
-        mt->totals.ensure(4);
-        if (c->record_moves) {
-            mt->moves.ensure(B * engine_p1->geo.max_plies);
-            HIP_OK(hipMemset(mt->moves.p, 0xFF, B * engine_p1->geo.max_plies * sizeof(int32_t)));      // -1: nothing played
-        }
-        HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&mt->fin_host), sizeof(unsigned long long), hipHostMallocDefault));
-        mt->drv.create_events();
-        const az::GameState st = start_state(engine_p1->game);
-        const std::vector<uint64_t> h0(B, st.bb0), h1(B, st.bb1);
-        mt->load(h0.data(), h1.data(), 1);
-        *out = mt.release();
+        const az_match_teams single{1, 1, 0, 0};
+        create_match("az_match_create", engine_p1, engine_p2, c, &single, out);
     });
+}
+
+int az_match_create_teams(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, const az_match_teams *t, az_match **out)
+{
+    return guarded([&] { create_match("az_match_create_teams", engine_p1, engine_p2, c, t, out); });
 }
 
 void az_match_destroy(az_match *mt)
@@ -283,6 +316,35 @@ int az_match_sample(int game, const int32_t *counts, float temperature, uint64_t
         require(known_game(game), "az_match_sample: unknown game");
         require(counts != nullptr && actions != nullptr && n >= 0, "az_match_sample: bad argument");
         az::launch_match_sample(game, counts, temperature, seed, ply, actions, n, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_match_team_roots(int game, const uint64_t *bb_p1, const uint64_t *bb_p2, const int32_t *turns, int trees, int ensemble,
+                        uint64_t *out_bb_p1, uint64_t *out_bb_p2, int32_t *out_turns, int64_t n, void *stream)
+{
+    return guarded([&] {
+        require(known_game(game), "az_match_team_roots: unknown game");
+        require(bb_p1 != nullptr && bb_p2 != nullptr && turns != nullptr && out_bb_p1 != nullptr && out_bb_p2 != nullptr &&
+                out_turns != nullptr && n >= 0 && trees >= 1, "az_match_team_roots: bad argument");
+        require(ensemble == 0 || trees == az::replay_num_augment(game), "az_match_team_roots: an ensemble has one tree per symmetry");
+        az::RootState rs{out_bb_p1, out_bb_p2, out_turns, nullptr};
+        az::launch_match_team_roots(game, bb_p1, bb_p2, turns, trees, ensemble != 0, rs, n, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_match_team_sample(int game, const int32_t *counts, int trees, int ensemble, float temperature, uint64_t seed, uint64_t ply,
+                         int32_t *summed, int32_t *actions, int out_trees, int out_ensemble, int32_t *tree_actions, int64_t n,
+                         void *stream)
+{
+    return guarded([&] {
+        require(known_game(game), "az_match_team_sample: unknown game");
+        require(counts != nullptr && actions != nullptr && n >= 0 && trees >= 1, "az_match_team_sample: bad argument");
+        const int n_sym = az::replay_num_augment(game);
+        require(ensemble == 0 || trees == n_sym, "az_match_team_sample: an ensemble has one tree per symmetry");
+        require(tree_actions == nullptr || (out_trees >= 1 && (out_ensemble == 0 || out_trees == n_sym)),
+                "az_match_team_sample: bad output team");
+        az::launch_match_team_sample(game, counts, trees, ensemble != 0, temperature, seed, ply, summed, actions, out_trees,
+                                     out_ensemble != 0, tree_actions, n, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -12,11 +12,18 @@
 //                 wavefront): lane e owns action e of the count row, Othello's pass rides with lane 0.  Every lane of
 //                 a group steps its game's position in registers (the pick leaves the move in all of them), lane 0 of
 //                 the group stores.  No LDS, no barrier.
-//   k_match_sample  the pick alone, for tests (az_match_sample).
+//                 Teams (player.py:248-329): the mover's `trees` count rows of a game are one row in registers before
+//                 the pick - lane e adds up its action's count over the rows, in an ensemble through each tree's
+//                 symmetry (board_sym.h; plain loads, no cross-lane traffic) - and after the step the group's lanes
+//                 write the move, in each tree's own frame, and `done` for every tree of BOTH engines' teams.
+//   k_match_sample  the pick alone, for tests (az_match_sample); k_match_team_sample its team form.
+//   k_match_team_roots  the games' positions -> the roots of the mover's team, one thread per tree (an ensemble's tree
+//                 j sees the position under symmetry j).  A match of single trees uses k_set_roots as before.
 //
 // Totals: one ballot per figure and wavefront, one atomic per figure per wavefront that has something to add.
 #include "kernels.h"
 
+#include "board_sym.h"
 #include "dev_rng.h"
 #include "games.h"
 #include "sp_pick.h"
@@ -25,6 +32,30 @@ namespace az {
 namespace {
 
 constexpr int WAVE = 64;
+
+// What lane `sub` of game g's group holds of the team's summed count row: c0 = sum over the trees of action sub's
+// count, c1 (Othello, lane 0) of the pass's; tree j's row is read at the action's index in that tree's frame.
+template <class G>
+__device__ __forceinline__ void team_counts(const int32_t *counts, int64_t g, int trees, int ensemble, bool live, int sub,
+                                            int &c0, int &c1)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    const bool has0 = live && sub < A, has1 = A > L && live && sub + L < A;
+    const int32_t *row = counts + g * trees * A;
+    c0 = 0; c1 = 0;
+    for (int j = 0; j < trees; ++j, row += A) {
+        if (has0) c0 += row[ensemble ? ensemble_action<G>(sub, j) : sub];
+        if (has1) c1 += row[ensemble ? ensemble_action<G>(sub + L, j) : sub + L];
+    }
+}
+
+// the move (game frame, -1: none) in the frames of a team's trees: lanes of the group share the trees
+template <class G>
+__device__ __forceinline__ void store_team_actions(int32_t *actions, int64_t g, int trees, int ensemble, int sub, int action)
+{
+    for (int j = sub; j < trees; j += G::LANES)
+        actions[g * trees + j] = (action >= 0 && ensemble) ? ensemble_action<G>(action, j) : action;
+}
 
 template <class G>
 __global__ void __launch_bounds__(WAVE) k_match_ply(MatchPly a)
@@ -36,8 +67,10 @@ __global__ void __launch_bounds__(WAVE) k_match_ply(MatchPly a)
     const int64_t g = live ? game : 0;                 // idle groups read game 0 and store nothing
     const bool dead = a.dead[g] != 0;
 
+    int c0, c1;
+    team_counts<G>(a.counts, g, a.trees, a.ensemble, live, sub, c0, c1);
     PickLane pl;
-    int action = pick_move<G, MATCH_STREAM>(a.counts + g * A, live, lane, a.temperature, a.tape, a.seed, a.ply, g, pl);
+    int action = pick_move_counts<G, MATCH_STREAM>(c0, c1, live, lane, a.temperature, a.tape, a.seed, a.ply, g, pl);
     if (dead || action < 0 || action >= A) action = -1;    // a tape's -1: the game does not move
 
     GameState s;
@@ -49,9 +82,15 @@ __global__ void __launch_bounds__(WAVE) k_match_ply(MatchPly a)
     }
     const bool fin = live && res >= 0;
     const int win = res == 1 ? 1 : (res == 2 ? -1 : 0);
+    if (live) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const MatchTeam &t = a.team[e];
+            store_team_actions<G>(t.actions, g, t.trees, t.ensemble, sub, action);
+            for (int j = sub; j < t.trees; j += L) t.done[g * t.trees + j] = fin ? 1 : 0;
+        }
+    }
     if (live && sub == 0) {
-        a.actions[g] = action;
-        a.done[g] = fin ? 1 : 0;
         if (a.moves != nullptr) a.moves[a.ply * static_cast<uint64_t>(a.n) + g] = action;
         if (action >= 0) {
             a.bb0[g] = s.bb0; a.bb1[g] = s.bb1; a.turn[g] = s.turn; a.aux[g] = s.aux;
@@ -84,6 +123,43 @@ __global__ void __launch_bounds__(WAVE) k_match_sample(const int32_t *counts, fl
     if (live && lane % L == 0) actions[g] = action;
 }
 
+template <class G>
+__global__ void __launch_bounds__(WAVE) k_match_team_sample(const int32_t *counts, int trees, int ensemble, float temperature,
+                                                            uint64_t seed, uint64_t ply, int32_t *summed, int32_t *actions,
+                                                            int out_trees, int out_ensemble, int32_t *tree_actions, int64_t n)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    const int lane = threadIdx.x, sub = lane % L;
+    const int64_t game = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
+    const bool live = game < n;
+    const int64_t g = live ? game : 0;
+    int c0, c1;
+    team_counts<G>(counts, g, trees, ensemble, live, sub, c0, c1);
+    PickLane pl;
+    const int action = pick_move_counts<G, MATCH_STREAM>(c0, c1, live, lane, temperature, nullptr, seed, ply, g, pl);
+    if (!live) return;
+    if (summed != nullptr) {
+        if (pl.has0) summed[g * A + sub] = c0;
+        if (pl.has1) summed[g * A + sub + L] = c1;
+    }
+    if (sub == 0) actions[g] = action;
+    if (tree_actions != nullptr) store_team_actions<G>(tree_actions, g, out_trees, out_ensemble, sub, action);
+}
+
+template <class G>
+__global__ void __launch_bounds__(256) k_match_team_roots(const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns,
+                                                          int trees, int ensemble, RootState rs, int64_t n_trees)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= n_trees) return;
+    const int64_t g = t / trees;
+    const int j = static_cast<int>(t - g * trees);
+    uint64_t a = bb0[g], b = bb1[g];
+    if (ensemble) { a = ensemble_board<G>(a, j); b = ensemble_board<G>(b, j); }     // the side to move stays (player.py:291-292)
+    rs.bb0[t] = a; rs.bb1[t] = b; rs.turn[t] = turns[g];
+    if (rs.aux != nullptr) rs.aux[t] = G::root_aux(a, b);
+}
+
 }  // namespace
 
 #define AZ_MATCH_DISPATCH(game, ...)                                               \
@@ -109,6 +185,27 @@ void launch_match_sample(int game, const int32_t *counts, float temperature, uin
         const unsigned grid = static_cast<unsigned>((n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
         hipLaunchKernelGGL(k_match_sample<G>, dim3(grid), dim3(WAVE), 0, s, counts, temperature, seed, ply, actions, n);
     });
+}
+
+void launch_match_team_sample(int game, const int32_t *counts, int trees, int ensemble, float temperature, uint64_t seed,
+                              uint64_t ply, int32_t *summed, int32_t *actions, int out_trees, int out_ensemble,
+                              int32_t *tree_actions, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return;
+    AZ_MATCH_DISPATCH(game, {
+        const unsigned grid = static_cast<unsigned>((n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
+        hipLaunchKernelGGL(k_match_team_sample<G>, dim3(grid), dim3(WAVE), 0, s, counts, trees, ensemble, temperature, seed, ply,
+                           summed, actions, out_trees, out_ensemble, tree_actions, n);
+    });
+}
+
+void launch_match_team_roots(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, int trees, int ensemble,
+                             RootState rs, int64_t n, hipStream_t s)
+{
+    const int64_t n_trees = n * trees;
+    if (n_trees <= 0) return;
+    AZ_MATCH_DISPATCH(game, hipLaunchKernelGGL(k_match_team_roots<G>, dim3(static_cast<unsigned>((n_trees + 255) / 256)), dim3(256), 0,
+                                               s, bb0, bb1, turns, trees, ensemble, rs, n_trees));
 }
 
 }  // namespace az

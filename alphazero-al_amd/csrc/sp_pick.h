@@ -55,18 +55,19 @@ struct PickLane {
     long long total;        // the row's sum, the same in every lane of the group
 };
 
-// The move of game g, the same value in every lane of its group.  cnt: the game's count row; tape: this ply's
-// recorded actions [n] or nullptr; draws come from the generator stream (seed, call, g, STREAM).
+// The move of game g, the same value in every lane of its group.  c0, c1: what this lane holds of the game's count
+// row - action sub and (Othello, lane 0) action sub + L - read where has0 / has1 of the result say so; tape: this
+// ply's recorded actions [n] or nullptr; draws come from the generator stream (seed, call, g, STREAM).
 template <class G, uint64_t STREAM>
-__device__ __forceinline__ int pick_move(const int32_t *cnt, bool live, int lane, float temp, const int32_t *tape,
-                                         uint64_t seed, uint64_t call, int64_t g, PickLane &pl)
+__device__ __forceinline__ int pick_move_counts(int c0, int c1, bool live, int lane, float temp, const int32_t *tape,
+                                                uint64_t seed, uint64_t call, int64_t g, PickLane &pl)
 {
     constexpr int L = G::LANES, A = G::ACTIONS;
     constexpr bool TWO = A > L;                       // a second action per lane (Othello: lane 0, the pass)
     const int sub = lane % L;
     const bool has0 = live && sub < A, has1 = TWO && live && sub + L < A;
-    const int n0 = has0 ? max(cnt[sub], 0) : 0;
-    const int n1 = has1 ? max(cnt[sub + L], 0) : 0;
+    const int n0 = has0 ? max(c0, 0) : 0;
+    const int n1 = has1 ? max(c1, 0) : 0;
     const long long total = group_sum<L>(static_cast<long long>(n0) + n1);
     pl.n0 = n0; pl.n1 = n1; pl.has0 = has0; pl.has1 = has1; pl.total = total;
     int action;
@@ -107,6 +108,18 @@ __device__ __forceinline__ int pick_move(const int32_t *cnt, bool live, int lane
         else action = 63 - __clzll(static_cast<long long>(v0));
     }
     return action;
+}
+
+// pick_move_counts on a count row in memory (cnt: the game's row)
+template <class G, uint64_t STREAM>
+__device__ __forceinline__ int pick_move(const int32_t *cnt, bool live, int lane, float temp, const int32_t *tape,
+                                         uint64_t seed, uint64_t call, int64_t g, PickLane &pl)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS;
+    const int sub = lane % L;
+    const int c0 = (live && sub < A) ? cnt[sub] : 0;
+    const int c1 = (A > L && live && sub + L < A) ? cnt[sub + L] : 0;
+    return pick_move_counts<G, STREAM>(c0, c1, live, lane, temp, tape, seed, call, g, pl);
 }
 
 }  // namespace az

@@ -46,6 +46,12 @@ class MatchConfig(C.Structure):
     _fields_ = [("temperature", C.c_float), ("record_moves", C.c_int32)]
 
 
+class MatchTeams(C.Structure):
+    """az_match_teams (include/az_mcts.h): trees per game and the ensemble flag of player +1 / -1.  Passed by address to a
+    c_void_p parameter (C.byref), so it is no entry of `MIRRORS`; tests/test_team_cpu.py holds its layout to the header."""
+    _fields_ = [(n, C.c_int32) for n in ("trees_p1", "trees_p2", "ensemble_p1", "ensemble_p2")]
+
+
 class ReplayBatchC(C.Structure):
     """az_replay_batch (include/az_mcts.h): device pointers of one augmented batch's tensors."""
     _fields_ = [(n, C.c_void_p) for n in ("state", "prob", "winner", "steps_to_end", "aux_target", "root_wdl",
@@ -182,6 +188,7 @@ PROTOTYPES = (
     ("az_replay_dev_store", i32, [i32, P(SelfPlayGames), vp, vp, i64, P(ReplayTensorsC), i64, i32, vp]),
     ("az_selfplay_sample", i32, [i32, vp, vp, P(SelfPlayConfig), u64, u64, vp, i64, vp]),
     ("az_match_create", i32, [vp, vp, P(MatchConfig), P(vp)]),
+    ("az_match_create_teams", i32, [vp, vp, P(MatchConfig), vp, P(vp)]),
     ("az_match_destroy", None, [vp]),
     ("az_match_set_positions", i32, [vp, vp, vp, vp]),
     ("az_match_step", i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -194,6 +201,8 @@ PROTOTYPES = (
     ("az_match_moves", i32, [vp, vp]),
     ("az_match_max_plies", i32, [vp]),
     ("az_match_sample", i32, [i32, vp, f32, u64, u64, vp, i64, vp]),
+    ("az_match_team_roots", i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp, i64, vp]),
+    ("az_match_team_sample", i32, [i32, vp, i32, i32, f32, u64, u64, vp, vp, i32, i32, vp, i64, vp]),
     ("az_game_num_augment", i32, [i32]),
     ("az_replay_dev_batch", i32, [i32, P(ReplayTensorsC), vp, vp, i64, i64, P(ReplayBatchC), vp]),
     ("az_replay_dev_sample_indices", i32, [u64, u64, i64, vp, i64, vp]),

@@ -27,6 +27,13 @@ pure-MCTS rollout player (`MCTSPlayer`, player.py:73-103; searched by k_rollout_
 `fresh_trees` makes a side start every search from empty trees as `Game.play` does (game.py:41), and
 `rating_games(net, ...)` plays the two colour-swapped matches; src/elo.py turns their results into ratings.  Logging
 and the best-network bookkeeping stay with the caller.
+
+Teams: the reference's strongest play modes search several trees of one root and choose the move from the summed visit
+counts - root-parallel play (`AlphaZeroPlayer(n_trees=K)`, `MCTSPlayer(n_trees=K)`, player.py:73-103, 248-283) and the
+symmetry ensemble (`AlphaZeroPlayer(sym_ensemble=True)`, player.py:285-329: one tree per board symmetry, each shown
+the position under its symmetry).  `EvaluationMatch(..., n_trees=, sym_ensemble=)` and `RolloutPlayer(n_trees=)` give a
+side that many trees per game in its engine; the match driver (az_match_create_teams) spreads the roots, sums the
+count rows per game inside the ply's one tail kernel and re-roots every tree with the move in its own frame.
 """
 import ctypes as C
 
@@ -34,7 +41,7 @@ import numpy as np
 import torch
 
 from src import fused as F
-from src.abi import MatchConfig, lib as match_lib      # noqa: F401  (match_lib: the name callers written before src/abi.py use)
+from src.abi import MatchConfig, MatchTeams, lib as match_lib      # noqa: F401  (match_lib: the name callers written before src/abi.py use)
 from src.MCTS_cpp import BatchedMCTS
 from src.selfplay import _reserve_arenas, _setup_search
 
@@ -58,19 +65,21 @@ def gate_decision(results_first, results_second, n_games, threshold):
 class RolloutPlayer:
     """Marker for `EvaluationMatch`: this side is the reference's pure-MCTS player (`MCTSPlayer`, player.py:73-103) -
     uniform priors, the value of a leaf is the result of a random playout.  Defaults: MCTSPlayer's n_playout and the
-    c_puct that `update_elo` passes (pipeline.py:233)."""
+    c_puct that `update_elo` passes (pipeline.py:233).  n_trees: root-parallel search (player.py:83,94-101), that many
+    independent trees per game, the move from their summed visit counts."""
 
-    def __init__(self, n_playout=1000, c_puct=1.0):
-        self.n_playout, self.c_puct = int(n_playout), float(c_puct)
+    def __init__(self, n_playout=1000, c_puct=1.0, n_trees=1):
+        self.n_playout, self.c_puct, self.n_trees = int(n_playout), float(c_puct), max(1, int(n_trees))
 
 
 class _Side:
     """One player's engine and evaluator binding (what selfplay._setup_search builds)."""
 
 
-def _setup_rollout(self, player, n_games, seed, game, device):
-    """A rollout player's side: an engine only, configured as MCTSPlayer configures it (player.py:84-88)."""
-    self.B, self.n_playout, self.vl_batch = int(n_games), player.n_playout, 1
+def _setup_rollout(self, player, n_trees, seed, game, device):
+    """A rollout player's side: an engine only (n_trees trees in all), configured as MCTSPlayer configures it
+    (player.py:84-88)."""
+    self.B, self.n_playout, self.vl_batch = int(n_trees), player.n_playout, 1
     self.game, self.game_id = game, 0 if game == "Connect4" else 1
     self.MAX_PLIES = 42 if game == "Connect4" else 126
     with torch.cuda.device(device):
@@ -95,23 +104,34 @@ class EvaluationMatch:
     (int32, +1 / -1 / 0) like the reference; `step(n)`, `remaining()`, `results()`, `moves()` are the pieces.
     Either side may be a `RolloutPlayer` (its own n_playout and c_puct; the other arguments configure network sides).
     fresh_trees (a flag or a pair): that side starts every one of its searches from empty trees instead of the
-    subtree its re-rooting kept (game.py:41)."""
+    subtree its re-rooting kept (game.py:41).
+    n_trees, sym_ensemble (each a value or a pair): a network side searches n_trees trees per game (root-parallel,
+    player.py:248-283) or, as an ensemble, one tree per board symmetry of the game (2 / 4; player.py:285-329) with the
+    engine's own random symmetry off (player.py:177-180); a RolloutPlayer brings its own n_trees and is never an
+    ensemble.  The side's engine holds n_games * trees trees.  eval_noise_eps may be a pair as well: root-parallel
+    trees of a deterministic evaluator differ only through their root noise (player.py:112-117)."""
 
     def __init__(self, net_p1, net_p2, n_games, n_playout=200, vl_batch=1, c_init=1.25, c_base=500, alpha=0.3,
                  eval_noise_eps=0.05, eval_temp=0.2, use_symmetry=True, mlh_slope=0.0, mlh_cap=0.2,
                  score_utility_factor=0.0, score_scale=8.0, value_decay=1.0, fpu_reduction=0.4, seed=0, game="Connect4",
-                 table_log2=0, positions=None, record_moves=False, reserve_slots=None, fresh_trees=False):
+                 table_log2=0, positions=None, record_moves=False, reserve_slots=None, fresh_trees=False, n_trees=1,
+                 sym_ensemble=False):
         self._mt = None
         self.B, self.n_playout, self.vl_batch = int(n_games), int(n_playout), int(vl_batch)
         self.game = game
         self.fresh_trees = sum((1 << i) for i, f in enumerate(_pair(fresh_trees)) if f)
         self.sides = [None, None]
         nets = (net_p1, net_p2)
-        for i, (net, ci) in enumerate(zip(nets, _pair(c_init))):
+        n_sym = 2 if game == "Connect4" else 4                # az_game_num_augment
+        self.ensemble = tuple(bool(f) and not isinstance(net, RolloutPlayer) for f, net in zip(_pair(sym_ensemble), nets))
+        self.trees = tuple(net.n_trees if isinstance(net, RolloutPlayer) else n_sym if ens else max(1, int(k))
+                           for net, ens, k in zip(nets, self.ensemble, _pair(n_trees)))
+        for i, (net, ci, eps) in enumerate(zip(nets, _pair(c_init), _pair(eval_noise_eps))):
             if isinstance(net, RolloutPlayer):
                 continue
             s = _Side()
-            _setup_search(s, net, n_games, n_playout, vl_batch, ci, c_base, alpha, eval_noise_eps, fpu_reduction, use_symmetry,
+            _setup_search(s, net, self.B * self.trees[i], n_playout, vl_batch, ci, c_base, alpha, eps, fpu_reduction,
+                          use_symmetry and not self.ensemble[i],
                           mlh_slope, mlh_cap, value_decay, eval_temp, 0, eval_temp, int(seed) + i, table_log2, game,
                           score_utility_factor, score_scale)
             self.sides[i] = s
@@ -119,19 +139,21 @@ class EvaluationMatch:
         for i, net in enumerate(nets):                        # rollout players go where the network side is
             if self.sides[i] is None:
                 self.sides[i] = _Side()
-                _setup_rollout(self.sides[i], net, n_games, int(seed) + i, game, dev)
+                _setup_rollout(self.sides[i], net, self.B * self.trees[i], int(seed) + i, game, dev)
         for s in self.sides:
             _reserve_arenas(s, reserve_slots)
         self.device = self.sides[0].device
         self.MAX_PLIES = self.sides[0].MAX_PLIES
         self.A = self.sides[0].search.action_size
-        self._ones = None                                     # reset mask of the begin / search / finish route
+        self._ones = [None, None]                             # reset masks of the begin / search / finish route
         self.L = F.lib()
         self.config = MatchConfig(float(eval_temp), int(bool(record_moves)))
         self.record_moves = bool(record_moves)
+        self.teams = MatchTeams(self.trees[0], self.trees[1], int(self.ensemble[0]), int(self.ensemble[1]))
         mt = C.c_void_p()
         with torch.cuda.device(self.device):
-            F.check(self.L.az_match_create(self.sides[0].h, self.sides[1].h, C.byref(self.config), C.byref(mt)))
+            F.check(self.L.az_match_create_teams(self.sides[0].h, self.sides[1].h, C.byref(self.config), C.byref(self.teams),
+                                                 C.byref(mt)))
         self._mt = mt
         self._tape = None
         self.poll_every = 4
@@ -204,9 +226,9 @@ class EvaluationMatch:
                 i = 0 if mover.value > 0 else 1
                 side = self.sides[i]
                 if (self.fresh_trees >> i) & 1:
-                    if self._ones is None:
-                        self._ones = torch.ones(self.B, dtype=torch.uint8, device=self.device)
-                    F.check(self.L.az_mcts_dev_reset_masked(side.h, self._ones.data_ptr(), s))
+                    if self._ones[i] is None:
+                        self._ones[i] = torch.ones(side.B, dtype=torch.uint8, device=self.device)
+                    F.check(self.L.az_mcts_dev_reset_masked(side.h, self._ones[i].data_ptr(), s))
                 if side.fused is None:
                     F.check(self.L.az_mcts_dev_rollout_search(side.h, side.n_playout, 0, s))
                 else:
@@ -248,18 +270,24 @@ class EvaluationMatch:
         return tuple(F.counters(s.h) for s in self.sides)
 
 
-def rating_games(net, n_games, n_playout, pure_mcts_n_playout, **kw):
+def rating_games(net, n_games, n_playout, pure_mcts_n_playout, n_trees=1, sym_ensemble=False, rollout_trees=1, **kw):
     """The games of one rating round (`TrainPipeline.update_elo`, pipeline.py:219-239): `n_games` with `net` as +1
     against the rollout player, then `n_games` with the colours swapped, both sides starting every search from empty
     trees.  Returns (winners with net as +1, winners with net as -1), int32 +1 / -1 / 0 each.  The network side
     searches as `update_elo` configures it - no root noise, the most visited move, c_base 500; other keyword
     arguments go to EvaluationMatch (the second match uses seed + 2).  n_games = 1 is the reference's round; with
-    more, the rollout player's randomness makes the games differ.  src/elo.py's `rate` turns the pair into ratings."""
+    more, the rollout player's randomness makes the games differ.  src/elo.py's `rate` turns the pair into ratings.
+    n_trees / sym_ensemble: the network side plays root-parallel or as the symmetry ensemble; rollout_trees: the rollout
+    player's trees per game.  Without an eval_noise_eps of the caller's the network side takes what
+    `AlphaZeroPlayer.eval()` sets (player.py:221-232): 0.05 when root-parallel, 0 for an ensemble or a single tree."""
     seed = int(kw.pop("seed", 0))
-    kw = dict(dict(eval_noise_eps=0.0, eval_temp=0.0, c_base=500, fresh_trees=True), **kw)
-    rollout = RolloutPlayer(pure_mcts_n_playout, 1.0)
-    first = EvaluationMatch(net, rollout, n_games, n_playout=n_playout, seed=seed, **kw).play()
-    second = EvaluationMatch(rollout, net, n_games, n_playout=n_playout, seed=seed + 2, **kw).play()
+    eps = 0.05 if int(n_trees) > 1 and not sym_ensemble else 0.0
+    kw = dict(dict(eval_noise_eps=eps, eval_temp=0.0, c_base=500, fresh_trees=True), **kw)
+    rollout = RolloutPlayer(pure_mcts_n_playout, 1.0, rollout_trees)
+    first = EvaluationMatch(net, rollout, n_games, n_playout=n_playout, seed=seed, n_trees=n_trees, sym_ensemble=sym_ensemble,
+                            **kw).play()
+    second = EvaluationMatch(rollout, net, n_games, n_playout=n_playout, seed=seed + 2, n_trees=n_trees,
+                             sym_ensemble=sym_ensemble, **kw).play()
     return first, second
 
 

@@ -435,7 +435,28 @@ int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, cons
  * generator on a stream of its own (MATCH_STREAM in dev_rng.h, not the self-play driver's), keyed by (the seed of
  * engine_p1, the match's ply counter, the game): az_selfplay_sample does NOT reproduce them, az_match_sample does.
  * The reference's two objects draw noise and symmetry ids from ONE thread-local mt19937 (MCTS.h:13-17); here each
- * engine has its own device generator stream. */
+ * engine has its own device generator stream.
+ *
+ * Teams.  The reference's strongest players search SEVERAL trees of one root and choose the move from the summed
+ * visit counts: root-parallel play (AlphaZeroPlayer / MCTSPlayer with n_trees = K, src/player.py:73-103, 248-283) and
+ * the symmetry ensemble (sym_ensemble, player.py:285-329 with src/symmetry.py: one tree per board symmetry of the
+ * game).  az_match_create_teams gives each player `trees` trees per game: tree j of game g is tree g * trees + j of
+ * that player's engine, so n_games = n_envs(engine) / trees and the two engines may differ in n_envs.  In an ensemble
+ * team (trees = az_game_num_augment(game)) tree j works in the frame of the game's j-th symmetry - Connect4:
+ * identity, column mirror; Othello: the reference's ids 0, 2, 6, 7; the order of az_replay_dev_batch - and the
+ * engine's own random symmetry should be off (player.py:177-180: use_symmetry = 0 in its az_search_config).  A ply:
+ *   roots    every tree of the mover's team gets the game's position, ensemble tree j under symmetry j (both
+ *            bitboards transformed, the side to move as it is);
+ *   move     the team's count rows become one row per game, summed[a] = sum over j of counts[tree j][perm_j(a)]
+ *            (perm_j the identity without an ensemble; the pass stays; every perm is an involution), and the pick
+ *            above runs on that row, its draws keyed by (seed of engine_p1, ply, GAME).  The move record, winner,
+ *            length and totals are per game and in the game's frame;
+ *   re-root  BOTH engines, every tree with the move mapped into its own frame (player.py:321-324); every tree of a
+ *            finished or dead game gets action -1 and is reset, as a single tree is.
+ * Trees of one game diverge through what the engine's generator gives each TREE (root noise, symmetry ids, random
+ * playouts) or, in an ensemble, through the frames.  All per-game arrays of the calls below (set_positions, results,
+ * moves, remaining, the action tape) have n_games entries; fresh_trees and the begin / finish route cover all trees
+ * of the side (the caller of begin_ply searches the mover's engine over all its trees). */
 typedef struct az_match_config {
     float   temperature;
     int32_t record_moves;
@@ -447,13 +468,31 @@ static_assert(sizeof(az_match_config) == AZ_MATCH_CONFIG_BYTES, "az_match_config
 _Static_assert(sizeof(az_match_config) == AZ_MATCH_CONFIG_BYTES, "az_match_config layout");
 #endif
 
+typedef struct az_match_teams {
+    int32_t trees_p1, trees_p2;          /* trees per game of player +1 / -1, >= 1 */
+    int32_t ensemble_p1, ensemble_p2;    /* != 0: that player's trees are the game's symmetry ensemble */
+} az_match_teams;
+#define AZ_MATCH_TEAMS_BYTES 16
+#ifdef __cplusplus
+static_assert(sizeof(az_match_teams) == AZ_MATCH_TEAMS_BYTES, "az_match_teams layout");
+#else
+_Static_assert(sizeof(az_match_teams) == AZ_MATCH_TEAMS_BYTES, "az_match_teams layout");
+#endif
+
 typedef struct az_match az_match;
 
 /* Every game at its initial position with player +1 to move, ply 0, every tree of both engines reset
- * (synchronises).  AZ_ERR_ARG: the engines differ in game, n_envs or device, or are one and the same. */
+ * (synchronises).  AZ_ERR_ARG: the engines differ in game, n_envs or device, or are one and the same.
+ * az_match_create_teams with {1, 1, 0, 0}. */
 int  az_match_create(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, az_match **out);
+/* The same with a team of trees per player and game (see above): n_games = n_envs(engine_p1) / trees_p1 =
+ * n_envs(engine_p2) / trees_p2.  AZ_ERR_ARG besides az_match_create's: a null argument, a tree count below 1, an
+ * n_envs that is no multiple of its tree count, unequal game counts, an ensemble whose tree count is not
+ * az_game_num_augment(game). */
+int  az_match_create_teams(az_mcts *engine_p1, az_mcts *engine_p2, const az_match_config *c, const az_match_teams *t,
+                           az_match **out);
 void az_match_destroy(az_match *mt);
-/* Start positions from HOST arrays of n_envs entries (an opening suite; deterministic tests); before the first ply
+/* Start positions from HOST arrays of n_games entries (an opening suite; deterministic tests); before the first ply
  * only (AZ_ERR_ARG after it).  Every game must have the same side to move (AZ_ERR_ARG otherwise).  Both engines'
  * trees of every game are reset; a position that is already over counts as finished at ply 0 with its winner and
  * length 0.  Connect4's last mover and Othello's pass count are derived as an import derives them.  Synchronises. */
@@ -500,6 +539,20 @@ int az_match_max_plies(const az_match *mt);
  * match's draws. */
 int az_match_sample(int game, const int32_t *counts, float temperature, uint64_t seed, uint64_t ply, int32_t *actions,
                     int64_t n, void *stream);
+/* The team forms, for tests; both only enqueue, every pointer is DEVICE memory.
+ * az_match_team_roots: positions [n] -> a team's roots [n * trees], tree j of game g at g * trees + j, symmetrised
+ * for an ensemble - what a team match puts into the mover's engine.
+ * az_match_team_sample: counts [n * trees][A] -> summed [n][A] (may be NULL), actions [n] in the game's frame (the
+ * pick of az_match_sample on the summed row, draws keyed by (seed, ply, game)) and tree_actions [n * out_trees], the
+ * move in the frames of a team of out_trees trees (out_ensemble as above; may be NULL).  With trees = 1 and
+ * ensemble = 0 the actions are az_match_sample's.  AZ_ERR_ARG: an unknown game, a null pointer that may not be, a tree
+ * count below 1, an ensemble whose tree count is not az_game_num_augment(game). */
+int az_match_team_roots(int game, const uint64_t *bb_p1, const uint64_t *bb_p2, const int32_t *turns, int trees,
+                        int ensemble, uint64_t *out_bb_p1, uint64_t *out_bb_p2, int32_t *out_turns, int64_t n,
+                        void *stream);
+int az_match_team_sample(int game, const int32_t *counts, int trees, int ensemble, float temperature, uint64_t seed,
+                         uint64_t ply, int32_t *summed, int32_t *actions, int out_trees, int out_ensemble,
+                         int32_t *tree_actions, int64_t n, void *stream);
 
 /* ---- augmented training batches out of the replay tensors, on the device (k_replay_batch) ----------------
  * The reference's learner draws a sample on the host (src/ReplayBuffer.py:130-145: np.random.randint, `get`, a

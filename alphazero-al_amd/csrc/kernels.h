@@ -186,6 +186,15 @@ struct SpPick {
     int     temp_decay_moves;
     uint64_t seed, call;     // generator key: the engine's seed and the driver's ply counter
     int64_t n;
+    // The team form (k_sp_pick's TEAM instantiation; MatchPly's conventions): game_actions != nullptr selects it.  n is
+    // then the number of GAMES, counts [n * trees][A] and stats [n * trees][STATS] hold a game's trees side by side, the
+    // rows are summed per game (through the symmetries of an ensemble) before the pick, whose draws are keyed by the game.
+    int      trees, ensemble;
+    int32_t *game_actions;   // [n] out: the move in the game's frame (what the game step reads); `actions` is then
+                             // [n * trees] or nullptr: the move in each tree's own frame (what the re-rooting reads)
+    uint8_t *tree_done;      // [n * trees] or nullptr, out: 1 iff the tree's game ends with this move (the trees' reset
+                             // reads it; needs bb0 / bb1 / turn / aux: the kernel steps the position in registers)
+    int32_t *summed;         // [n][A] or nullptr, out: the summed row
 };
 
 struct SpAdvance {
@@ -203,7 +212,8 @@ struct SpAdvance {
     unsigned long long *n_alloc, *n_rows;    // games asked for (may pass `capacity`: those were dropped), rows handed out
     int64_t  capacity;                       // games the finished store holds
     int64_t  driver_ply;
-    float   *eps;                            // per-game noise epsilon of the next ply, or nullptr
+    int      trees;                          // trees per game (0 counts as 1)
+    float   *eps;                            // [n * trees] noise epsilon of the next ply, the game's value for each of its trees, or nullptr
     int      noise_steps;
     double   noise_eps_init, noise_eps_min;
     unsigned long long *totals;              // positions, games, p1 wins, p2 wins, draws
@@ -211,6 +221,9 @@ struct SpAdvance {
 
 void launch_sp_pick(int game, SpPick a, bool record, hipStream_t s);
 void launch_sp_advance(int game, SpAdvance a, hipStream_t s);
+// Merged root statistics of a team (k_team_root_stats; symmetry.py:140-186 `inverse_sym_stats`): stats [n * trees][6 + 8A]
+// as launch_root_stats writes them -> merged [n][6 + 8A] in the game's frame
+void launch_team_root_stats(int game, const float *stats, int trees, int ensemble, float *merged, int64_t n, hipStream_t s);
 
 // Packed games -> replay-buffer rows in a ring (k_sp_export; az_replay_tensors in az_mcts.h).  Game g: rows
 // src_row0[g] .. src_row0[g] + len[g] of `fin`, written to the ring slots (ptr + dst_row0[g] + t) % capacity.

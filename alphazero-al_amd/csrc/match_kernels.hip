@@ -14,7 +14,7 @@
 //                 the group stores.  No LDS, no barrier.
 //                 Teams (player.py:248-329): the mover's `trees` count rows of a game are one row in registers before
 //                 the pick - lane e adds up its action's count over the rows, in an ensemble through each tree's
-//                 symmetry (board_sym.h; plain loads, no cross-lane traffic) - and after the step the group's lanes
+//                 symmetry (team.h, shared with k_sp_pick's team form; plain loads, no cross-lane traffic) - and after the step the group's lanes
 //                 write the move, in each tree's own frame, and `done` for every tree of BOTH engines' teams.
 //   k_match_sample  the pick alone, for tests (az_match_sample); k_match_team_sample its team form.
 //   k_match_team_roots  the games' positions -> the roots of the mover's team, one thread per tree (an ensemble's tree
@@ -27,35 +27,12 @@
 #include "dev_rng.h"
 #include "games.h"
 #include "sp_pick.h"
+#include "team.h"
 
 namespace az {
 namespace {
 
 constexpr int WAVE = 64;
-
-// What lane `sub` of game g's group holds of the team's summed count row: c0 = sum over the trees of action sub's
-// count, c1 (Othello, lane 0) of the pass's; tree j's row is read at the action's index in that tree's frame.
-template <class G>
-__device__ __forceinline__ void team_counts(const int32_t *counts, int64_t g, int trees, int ensemble, bool live, int sub,
-                                            int &c0, int &c1)
-{
-    constexpr int L = G::LANES, A = G::ACTIONS;
-    const bool has0 = live && sub < A, has1 = A > L && live && sub + L < A;
-    const int32_t *row = counts + g * trees * A;
-    c0 = 0; c1 = 0;
-    for (int j = 0; j < trees; ++j, row += A) {
-        if (has0) c0 += row[ensemble ? ensemble_action<G>(sub, j) : sub];
-        if (has1) c1 += row[ensemble ? ensemble_action<G>(sub + L, j) : sub + L];
-    }
-}
-
-// the move (game frame, -1: none) in the frames of a team's trees: lanes of the group share the trees
-template <class G>
-__device__ __forceinline__ void store_team_actions(int32_t *actions, int64_t g, int trees, int ensemble, int sub, int action)
-{
-    for (int j = sub; j < trees; j += G::LANES)
-        actions[g * trees + j] = (action >= 0 && ensemble) ? ensemble_action<G>(action, j) : action;
-}
 
 template <class G>
 __global__ void __launch_bounds__(WAVE) k_match_ply(MatchPly a)

@@ -47,11 +47,14 @@ az::SpExport export_args(const az_replay_tensors *dst, int64_t ptr, int td_steps
 struct az_selfplay {
     az_mcts *m = nullptr;
     az_selfplay_config c;
-    int B = 0, A = 0;
+    int B = 0, A = 0;              // B: games
+    int T = 1, ens = 0;            // trees per game (tree j of game g is the engine's tree g * T + j), symmetry ensemble
     DevBuf<uint64_t> bb0, bb1;
-    DevBuf<int32_t> turn, aux, ply, actions, winner, counts;
-    DevBuf<uint8_t> done, dead;
-    DevBuf<float> stats, eps;
+    DevBuf<int32_t> turn, aux, ply, actions, winner, counts;      // actions, counts: per TREE
+    DevBuf<int32_t> game_actions;  // teams: the move per game, in the game's frame (k_game_step reads it)
+    DevBuf<uint8_t> done, dead;    // per game
+    DevBuf<uint8_t> tree_done;     // teams: per tree (the trees' reset reads it)
+    DevBuf<float> stats, eps;      // per tree
     DevBuf<unsigned long long> totals, alloc;      // alloc: [0] games asked for, [1] rows handed out
     // trajectories of the games in progress and the packed store of finished games
     struct Rows {
@@ -79,7 +82,8 @@ struct az_selfplay {
     {
         drv.require("az_selfplay");
         HIP_OK(hipSetDevice(m->device));
-        az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
+        if (T == 1) az::launch_set_roots(m->game, bb0.p, bb1.p, turn.p, m->roots(), B, s);
+        else az::launch_match_team_roots(m->game, bb0.p, bb1.p, turn.p, T, ens, m->roots(), B, s);
     }
 
     void finish_ply(void *stream)
@@ -96,20 +100,22 @@ struct az_selfplay {
         p.rec = rec.view(); p.rows_per_game = m->geo.max_plies;
         p.temperature = c.temperature; p.temp_endgame = c.temp_endgame; p.temp_decay_moves = c.temp_decay_moves;
         p.seed = m->dev_seed; p.call = static_cast<uint64_t>(driver_ply); p.n = B;
+        const bool team = T > 1;
+        if (team) { p.trees = T; p.ensemble = ens; p.game_actions = game_actions.p; p.tree_done = tree_done.p; }
         az::launch_sp_pick(m->game, p, c.record != 0, s);
         drv.advance();
         m->prune_on(actions.p, nullptr, true, m->replay_noise, s);
         az::launch_bump_call(m->call_ctr.p, s);
         // the end state has to survive the step (it is the last row of a recorded game): k_sp_advance refills
-        az::launch_game_step(m->game, bb0.p, bb1.p, turn.p, aux.p, actions.p, done.p, winner.p, B, false, s);
-        az::launch_reset_masked(m->arena(), done.p, s);
+        az::launch_game_step(m->game, bb0.p, bb1.p, turn.p, aux.p, team ? game_actions.p : actions.p, done.p, winner.p, B, false, s);
+        az::launch_reset_masked(m->arena(), team ? tree_done.p : done.p, s);
         az::SpAdvance a{};
         a.bb0 = bb0.p; a.bb1 = bb1.p; a.turn = turn.p; a.aux = aux.p; a.ply = ply.p; a.dead = dead.p;
         a.done = done.p; a.winner = winner.p; a.n = B; a.refill = c.refill; a.record = c.record;
         a.rec = rec.view(); a.fin = fin.view(); a.rows_per_game = m->geo.max_plies;
         a.fin_slot = fin_slot.p; a.fin_len = fin_len.p; a.fin_winner = fin_winner.p; a.fin_ply = fin_ply.p; a.fin_row0 = fin_row0.p;
         a.n_alloc = alloc.p; a.n_rows = alloc.p + 1; a.capacity = capacity; a.driver_ply = driver_ply;
-        a.eps = c.noise_steps > 0 ? eps.p : nullptr;
+        a.trees = T; a.eps = c.noise_steps > 0 ? eps.p : nullptr;
         a.noise_steps = c.noise_steps; a.noise_eps_init = c.noise_eps_init; a.noise_eps_min = c.noise_eps_min;
         a.totals = totals.p;
         az::launch_sp_advance(m->game, a, s);
@@ -148,47 +154,64 @@ struct az_selfplay {
     }
 };
 
+static void create_selfplay(const char *who, az_mcts *m, const az_selfplay_config *c, const az_selfplay_teams *t, az_selfplay **out)
+{
+    const std::string w = std::string(who) + ": ";
+    require(m != nullptr && c != nullptr && t != nullptr && out != nullptr, w + "null argument");
+    require(t->trees >= 1, w + "a game needs at least one tree");
+    require(m->B % t->trees == 0, w + "the engine's n_envs is no multiple of the trees per game");
+    require(t->ensemble == 0 || t->trees == az::replay_num_augment(m->game),
+            w + "a symmetry ensemble has one tree per symmetry of the game (az_game_num_augment)");
+    HIP_OK(hipSetDevice(m->device));
+    auto sp = std::make_unique<az_selfplay>();
+    sp->m = m; sp->c = *c; sp->T = t->trees; sp->ens = t->ensemble != 0; sp->B = m->B / t->trees; sp->A = m->geo.actions;
+    const size_t B = static_cast<size_t>(sp->B), trees = static_cast<size_t>(m->B);
+    const az::GameState st = start_state(m->game);
+    sp->bb0.ensure(B); sp->bb1.ensure(B); sp->turn.ensure(B);
+    const std::vector<uint64_t> h0(B, st.bb0), h1(B, st.bb1);
+    const std::vector<int32_t> ht(B, 1);
+    HIP_OK(hipMemcpy(sp->bb0.p, h0.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(sp->bb1.p, h1.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(sp->turn.p, ht.data(), B * sizeof(int32_t), hipMemcpyHostToDevice));
+    sp->aux.ensure(B, true); sp->ply.ensure(B, true); sp->actions.ensure(trees, true); sp->winner.ensure(B, true);
+    sp->done.ensure(B, true); sp->dead.ensure(B, true);
+    if (sp->T > 1) { sp->game_actions.ensure(B, true); sp->tree_done.ensure(trees, true); }
+    sp->counts.ensure(trees * sp->A, true);
+    sp->totals.ensure(5, true); sp->alloc.ensure(2, true);
+    if (c->noise_steps > 0) {
+        const std::vector<float> he(trees, static_cast<float>(c->noise_eps_min + (c->noise_eps_init - c->noise_eps_min) * 1.0));
+        sp->eps.ensure(trees);
+        HIP_OK(hipMemcpy(sp->eps.p, he.data(), trees * sizeof(float), hipMemcpyHostToDevice));
+        m->noise_eps_tree = sp->eps.p;
+    }
+    if (c->record) {
+        sp->stats.ensure(trees * m->geo.stats, true);
+        sp->capacity = c->max_finished_games > 0 ? c->max_finished_games : std::max<int64_t>(4 * sp->B, 1024);
+        sp->rec.ensure(B * m->geo.max_plies, sp->A);
+        sp->fin.ensure(static_cast<size_t>(sp->capacity) * (m->geo.max_plies + 1), sp->A);
+        const size_t G = static_cast<size_t>(sp->capacity);
+        sp->fin_slot.ensure(G); sp->fin_len.ensure(G); sp->fin_winner.ensure(G); sp->fin_ply.ensure(G); sp->fin_row0.ensure(G);
+        sp->exp_len.ensure(G); sp->exp_winner.ensure(G); sp->exp_src.ensure(G); sp->exp_dst.ensure(G);
+    }
+    sp->drv.create_events();
+    // the games start over: so do the trees (flushed by the first search's az_mcts_dev_prepare)
+    m->reset_all_trees();
+    *out = sp.release();
+}
+
 extern "C" {
 
 int az_selfplay_create(az_mcts *m, const az_selfplay_config *c, az_selfplay **out)
 {
     return guarded([&] {
-        require(m != nullptr && c != nullptr && out != nullptr, "az_selfplay_create: null argument");
-        HIP_OK(hipSetDevice(m->device));
-        auto sp = std::make_unique<az_selfplay>();
-        sp->m = m; sp->c = *c; sp->B = m->B; sp->A = m->geo.actions;
-        const size_t B = static_cast<size_t>(m->B);
-        const az::GameState st = start_state(m->game);
-        sp->bb0.ensure(B); sp->bb1.ensure(B); sp->turn.ensure(B);
-        const std::vector<uint64_t> h0(B, st.bb0), h1(B, st.bb1);
-        const std::vector<int32_t> ht(B, 1);
-        HIP_OK(hipMemcpy(sp->bb0.p, h0.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(sp->bb1.p, h1.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(sp->turn.p, ht.data(), B * sizeof(int32_t), hipMemcpyHostToDevice));
-        sp->aux.ensure(B, true); sp->ply.ensure(B, true); sp->actions.ensure(B, true); sp->winner.ensure(B, true);
-        sp->done.ensure(B, true); sp->dead.ensure(B, true);
-        sp->counts.ensure(B * sp->A, true);
-        sp->totals.ensure(5, true); sp->alloc.ensure(2, true);
-        if (c->noise_steps > 0) {
-            const std::vector<float> he(B, static_cast<float>(c->noise_eps_min + (c->noise_eps_init - c->noise_eps_min) * 1.0));
-            sp->eps.ensure(B);
-            HIP_OK(hipMemcpy(sp->eps.p, he.data(), B * sizeof(float), hipMemcpyHostToDevice));
-            m->noise_eps_tree = sp->eps.p;
-        }
-        if (c->record) {
-            sp->stats.ensure(B * m->geo.stats, true);
-            sp->capacity = c->max_finished_games > 0 ? c->max_finished_games : std::max<int64_t>(4 * m->B, 1024);
-            sp->rec.ensure(B * m->geo.max_plies, sp->A);
-            sp->fin.ensure(static_cast<size_t>(sp->capacity) * (m->geo.max_plies + 1), sp->A);
-            const size_t G = static_cast<size_t>(sp->capacity);
-            sp->fin_slot.ensure(G); sp->fin_len.ensure(G); sp->fin_winner.ensure(G); sp->fin_ply.ensure(G); sp->fin_row0.ensure(G);
-            sp->exp_len.ensure(G); sp->exp_winner.ensure(G); sp->exp_src.ensure(G); sp->exp_dst.ensure(G);
-        }
-        sp->drv.create_events();
-        // the games start over: so do the trees (flushed by the first search's az_mcts_dev_prepare)
-        m->reset_all_trees();
-        *out = sp.release();
+        const az_selfplay_teams single{1, 0};
+        create_selfplay("az_selfplay_create", m, c, &single, out);
     });
+}
+
+int az_selfplay_create_teams(az_mcts *m, const az_selfplay_config *c, const az_selfplay_teams *t, az_selfplay **out)
+{
+    return guarded([&] { create_selfplay("az_selfplay_create_teams", m, c, t, out); });
 }
 
 void az_selfplay_destroy(az_selfplay *sp)
@@ -421,6 +444,33 @@ int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, cons
         p.temperature = c->temperature; p.temp_endgame = c->temp_endgame; p.temp_decay_moves = c->temp_decay_moves;
         p.seed = seed; p.call = call; p.n = n;
         az::launch_sp_pick(game, p, false, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_selfplay_team_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c, int trees, int ensemble,
+                            uint64_t seed, uint64_t call, int32_t *summed, int32_t *actions, int32_t *tree_actions, int64_t n, void *stream)
+{
+    return guarded([&] {
+        require(known_game(game), "az_selfplay_team_sample: unknown game");
+        require(counts != nullptr && ply != nullptr && c != nullptr && actions != nullptr && n >= 0 && trees >= 1,
+                "az_selfplay_team_sample: bad argument");
+        require(ensemble == 0 || trees == az::replay_num_augment(game), "az_selfplay_team_sample: an ensemble has one tree per symmetry");
+        az::SpPick p{};
+        p.counts = counts; p.ply = ply; p.actions = tree_actions; p.game_actions = actions; p.summed = summed;
+        p.trees = trees; p.ensemble = ensemble != 0;
+        p.temperature = c->temperature; p.temp_endgame = c->temp_endgame; p.temp_decay_moves = c->temp_decay_moves;
+        p.seed = seed; p.call = call; p.n = n;
+        az::launch_sp_pick(game, p, false, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_mcts_dev_team_root_stats(int game, const float *stats, int trees, int ensemble, float *merged, int64_t n, void *stream)
+{
+    return guarded([&] {
+        require(known_game(game), "az_mcts_dev_team_root_stats: unknown game");
+        require(stats != nullptr && merged != nullptr && n >= 0 && trees >= 1, "az_mcts_dev_team_root_stats: bad argument");
+        require(ensemble == 0 || trees == az::replay_num_augment(game), "az_mcts_dev_team_root_stats: an ensemble has one tree per symmetry");
+        az::launch_team_root_stats(game, stats, trees, ensemble != 0, merged, n, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -6,8 +6,12 @@
 //                 trajectory (game.py:97-108).  One lane group per game as in kernels.hip (Connect4: 8
 //                 lanes, 8 games per wavefront; Othello: a wavefront): lane e owns action e, Othello's
 //                 65th action (pass) rides with lane 0.  The pick itself is sp_pick.h, shared with k_match_ply.
+//                 Its team form (a team of trees per game, team.h) sums the team's count rows first, writes
+//                 the move per game and per tree, `done` per tree, and records the merged root_wdl.
+//   k_team_root_stats  a team's root statistics merged into the game's frame (symmetry.py:140-186).
 //   k_sp_advance  after the re-rooting and the game step: ply counters, finished games' rows into the
-//                 finished store, refill, next ply's noise epsilon (game.py:87-91), running totals.
+//                 finished store, refill, next ply's noise epsilon (game.py:87-91; per tree of the
+//                 game's team), running totals.
 //                 One lane per game for the bookkeeping; a wavefront then copies the rows of ITS
 //                 finished games together - bytes moved follow the games that ended, not slots x plies.
 //   k_sp_export   the packed store of finished games -> the learner's replay-buffer rows, written in place
@@ -24,13 +28,20 @@
 #include "dev_rng.h"
 #include "games.h"
 #include "sp_pick.h"
+#include "team.h"
 
 namespace az {
 namespace {
 
 constexpr int WAVE = 64;
 
-template <class G, bool RECORD>
+// TEAM (player.py:248-329 with is_selfplay = 1): the game's `trees` count rows are one row in registers before the pick -
+// lane e adds up its action's count over the rows, in an ensemble through each tree's symmetry (team.h; plain loads, no
+// cross-lane traffic) - the draws are keyed by the GAME, the move goes once to the game (the game's frame) and to every
+// tree in the tree's own frame, every lane of the group steps a copy of the position in registers as k_match_ply does
+// and the group's lanes write `done` per tree (k_game_step still owns the stored position), and the recorded root_wdl is
+// the team's merged one (team_head_mean, what k_team_root_stats gives).
+template <class G, bool RECORD, bool TEAM>
 __global__ void __launch_bounds__(WAVE) k_sp_pick(SpPick a)
 {
     constexpr int L = G::LANES, A = G::ACTIONS;
@@ -44,22 +55,58 @@ __global__ void __launch_bounds__(WAVE) k_sp_pick(SpPick a)
     // game.py:55-63
     const float temp = (a.temp_decay_moves <= 0 || ply < a.temp_decay_moves) ? a.temperature : a.temp_endgame;
     PickLane pl;
-    int action = pick_move<G, SP_STREAM>(a.counts + g * A, live, lane, temp, a.tape, a.seed, a.call, g, pl);
+    int action;
+    if (TEAM) {
+        int c0, c1;
+        team_counts<G>(a.counts, g, a.trees, a.ensemble, live, sub, c0, c1);
+        action = pick_move_counts<G, SP_STREAM>(c0, c1, live, lane, temp, a.tape, a.seed, a.call, g, pl);
+        if (action < 0 || action >= A) action = -1;        // a tape's -1: the game does not move
+    } else {
+        action = pick_move<G, SP_STREAM>(a.counts + g * A, live, lane, temp, a.tape, a.seed, a.call, g, pl);
+    }
     const int n0 = pl.n0, n1 = pl.n1;
     const bool has0 = pl.has0, has1 = pl.has1;
     const long long total = pl.total;
     if (dead) action = -1;
-    if (live && sub == 0) a.actions[g] = action;
+    GameState s;
+    if (TEAM) {
+        const bool stepped = a.tree_done != nullptr;
+        if (RECORD || stepped) { s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g]; }
+        if (live) {
+            if (sub == 0) a.game_actions[g] = action;
+            if (a.actions != nullptr) store_team_actions<G>(a.actions, g, a.trees, a.ensemble, sub, action);
+            if (a.summed != nullptr) {
+                if (has0) a.summed[g * A + sub] = n0;
+                if (has1) a.summed[g * A + sub + L] = n1;
+            }
+            if (stepped) {
+                // k_game_step's rule on a copy: it steps the stored position after the re-rooting
+                int res = -1;
+                if (action >= 0) {
+                    GameState t = s;
+                    G::step(t, action);
+                    res = G::result(t);
+                }
+                for (int j = sub; j < a.trees; j += L) a.tree_done[g * a.trees + j] = res >= 0 ? 1 : 0;
+            }
+        }
+    } else {
+        if (live && sub == 0) a.actions[g] = action;
+    }
 
     if (RECORD) {
         if (!live || dead || ply < 0 || ply >= a.rows_per_game) return;
         const size_t r = static_cast<size_t>(g) * a.rows_per_game + ply;
-        GameState s;
-        s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g];
+        if (!TEAM) { s.bb0 = a.bb0[g]; s.bb1 = a.bb1[g]; s.turn = a.turn[g]; s.aux = a.aux[g]; }
         if (sub == 0) {
             a.rec.bb0[r] = s.bb0; a.rec.bb1[r] = s.bb1; a.rec.turn[r] = static_cast<int8_t>(s.turn);
-            const float *st = a.stats + g * G::STATS;
-            a.rec.wdl[r * 3 + 0] = st[3]; a.rec.wdl[r * 3 + 1] = st[4]; a.rec.wdl[r * 3 + 2] = st[5];
+            if (TEAM) {
+#pragma unroll
+                for (int f = 0; f < 3; ++f) a.rec.wdl[r * 3 + f] = team_head_mean<G>(a.stats, g, a.trees, 3 + f);
+            } else {
+                const float *st = a.stats + g * G::STATS;
+                a.rec.wdl[r * 3 + 0] = st[3]; a.rec.wdl[r * 3 + 1] = st[4]; a.rec.wdl[r * 3 + 2] = st[5];
+            }
         }
         // player.py:356: int / int in double, rounded once to f32
         const double den = static_cast<double>(total);
@@ -151,7 +198,10 @@ __global__ void __launch_bounds__(WAVE) k_sp_advance(SpAdvance a)
         if (a.eps != nullptr) {
             // game.py:87-91 in double, then one rounding
             const double decay = fmax(0.0, 1.0 - static_cast<double>(ply) / static_cast<double>(a.noise_steps));
-            a.eps[g] = static_cast<float>(a.noise_eps_min + (a.noise_eps_init - a.noise_eps_min) * decay);
+            const float eps = static_cast<float>(a.noise_eps_min + (a.noise_eps_init - a.noise_eps_min) * decay);
+            // the engine reads one value per TREE: the game's, for each tree of its team
+            const int trees = a.trees > 1 ? a.trees : 1;
+            for (int j = 0; j < trees; ++j) a.eps[g * trees + j] = eps;
         }
     }
     if (lane == 0) {
@@ -165,6 +215,59 @@ __global__ void __launch_bounds__(WAVE) k_sp_advance(SpAdvance a)
         if (w1) atomicAdd(&a.totals[2], static_cast<unsigned long long>(__popcll(w1)));
         if (w2) atomicAdd(&a.totals[3], static_cast<unsigned long long>(__popcll(w2)));
         if (w0) atomicAdd(&a.totals[4], static_cast<unsigned long long>(__popcll(w0)));
+    }
+}
+
+// ---- k_team_root_stats --------------------------------------------------------------------------------
+// symmetry.py:140-186 (`inverse_sym_stats`) for trees j = 0 .. trees - 1 of every game: rows of launch_root_stats
+// (head root_N, root_Q, root_M, root_D, root_P1W, root_P2W; then per action N, Q, prior, noise, M, D, P1W, P2W) ->
+// one row per game in the game's frame.  Lane e of the game's group owns action e and reads tree j's eight values at the
+// action's index in that tree's frame (the perms are involutions, the pass stays; identity without an ensemble); lane 0
+// writes the head.  All float32, every product and sum rounded on its own (no fused multiply-add), every sum taken in
+// tree order starting from tree 0's term: numpy sums a column of fewer than 8 values in that order and pairwise from 8
+// on, so from 8 trees on the merged means may differ from numpy's in the last bit.
+//   head             sum / trees
+//   N                sum
+//   prior, noise     sum / trees
+//   Q, M, D, P1W, P2W  sum_j(x_j * N_j) / sum_j(N_j) where that denominator is > 0, else 0
+template <class G>
+__global__ void __launch_bounds__(WAVE) k_team_root_stats(const float *stats, int trees, int ensemble, float *merged, int64_t n)
+{
+    constexpr int L = G::LANES, A = G::ACTIONS, ST = G::STATS;
+    const int lane = threadIdx.x, sub = lane % L;
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * (WAVE / L) + lane / L;
+    if (g >= n) return;                                    // no cross-lane traffic below
+    const float *in = stats + g * trees * ST;
+    float *out = merged + g * ST;
+    if (sub == 0) {
+#pragma unroll
+        for (int f = 0; f < 6; ++f) out[f] = team_head_mean<G>(stats, g, trees, f);
+    }
+    const float k = static_cast<float>(trees);
+    for (int act = sub; act < A; act += L) {
+        float sum_n = 0.0f, prior = 0.0f, noise = 0.0f, q = 0.0f, m = 0.0f, d = 0.0f, p1 = 0.0f, p2 = 0.0f;
+        for (int j = 0; j < trees; ++j) {
+            const float *r = in + static_cast<size_t>(j) * ST + 6 + 8 * (ensemble ? ensemble_action<G>(act, j) : act);
+            const float w = r[0];
+            const float tq = __fmul_rn(r[1], w), tm = __fmul_rn(r[4], w), td = __fmul_rn(r[5], w);
+            const float t1 = __fmul_rn(r[6], w), t2 = __fmul_rn(r[7], w);
+            if (j == 0) {
+                sum_n = w; prior = r[2]; noise = r[3]; q = tq; m = tm; d = td; p1 = t1; p2 = t2;
+            } else {
+                sum_n = __fadd_rn(sum_n, w); prior = __fadd_rn(prior, r[2]); noise = __fadd_rn(noise, r[3]);
+                q = __fadd_rn(q, tq); m = __fadd_rn(m, tm); d = __fadd_rn(d, td); p1 = __fadd_rn(p1, t1); p2 = __fadd_rn(p2, t2);
+            }
+        }
+        const bool any = sum_n > 0.0f;
+        float *o = out + 6 + 8 * act;
+        o[0] = sum_n;
+        o[1] = any ? __fdiv_rn(q, sum_n) : 0.0f;
+        o[2] = __fdiv_rn(prior, k);
+        o[3] = __fdiv_rn(noise, k);
+        o[4] = any ? __fdiv_rn(m, sum_n) : 0.0f;
+        o[5] = any ? __fdiv_rn(d, sum_n) : 0.0f;
+        o[6] = any ? __fdiv_rn(p1, sum_n) : 0.0f;
+        o[7] = any ? __fdiv_rn(p2, sum_n) : 0.0f;
     }
 }
 
@@ -282,8 +385,22 @@ void launch_sp_pick(int game, SpPick a, bool record, hipStream_t s)
     if (a.n <= 0) return;
     AZ_SP_DISPATCH(game, {
         const unsigned grid = static_cast<unsigned>((a.n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
-        if (record) hipLaunchKernelGGL((k_sp_pick<G, true>), dim3(grid), dim3(WAVE), 0, s, a);
-        else hipLaunchKernelGGL((k_sp_pick<G, false>), dim3(grid), dim3(WAVE), 0, s, a);
+        if (a.game_actions != nullptr) {
+            if (record) hipLaunchKernelGGL((k_sp_pick<G, true, true>), dim3(grid), dim3(WAVE), 0, s, a);
+            else hipLaunchKernelGGL((k_sp_pick<G, false, true>), dim3(grid), dim3(WAVE), 0, s, a);
+        } else {
+            if (record) hipLaunchKernelGGL((k_sp_pick<G, true, false>), dim3(grid), dim3(WAVE), 0, s, a);
+            else hipLaunchKernelGGL((k_sp_pick<G, false, false>), dim3(grid), dim3(WAVE), 0, s, a);
+        }
+    });
+}
+
+void launch_team_root_stats(int game, const float *stats, int trees, int ensemble, float *merged, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return;
+    AZ_SP_DISPATCH(game, {
+        const unsigned grid = static_cast<unsigned>((n + WAVE / G::LANES - 1) / (WAVE / G::LANES));
+        hipLaunchKernelGGL(k_team_root_stats<G>, dim3(grid), dim3(WAVE), 0, s, stats, trees, ensemble, merged, n);
     });
 }
 

@@ -52,6 +52,13 @@ class MatchTeams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("trees_p1", "trees_p2", "ensemble_p1", "ensemble_p2")]
 
 
+class SelfPlayTeams(C.Structure):
+    """az_selfplay_teams (include/az_mcts.h): trees per game and the ensemble flag of a self-play driver.  Passed by address
+    to a c_void_p parameter (C.byref) like MatchTeams, so it is no entry of `MIRRORS`; tests/test_team_selfplay_cpu.py holds
+    its layout to the header."""
+    _fields_ = [("trees", C.c_int32), ("ensemble", C.c_int32)]
+
+
 class ReplayBatchC(C.Structure):
     """az_replay_batch (include/az_mcts.h): device pointers of one augmented batch's tensors."""
     _fields_ = [(n, C.c_void_p) for n in ("state", "prob", "winner", "steps_to_end", "aux_target", "root_wdl",
@@ -187,6 +194,9 @@ PROTOTYPES = (
     ("az_selfplay_export", i32, [vp, P(ReplayTensorsC), i64, i32, i64, i64, P(SelfPlayExportInfo), P(i64), vp]),
     ("az_replay_dev_store", i32, [i32, P(SelfPlayGames), vp, vp, i64, P(ReplayTensorsC), i64, i32, vp]),
     ("az_selfplay_sample", i32, [i32, vp, vp, P(SelfPlayConfig), u64, u64, vp, i64, vp]),
+    ("az_selfplay_create_teams", i32, [vp, P(SelfPlayConfig), vp, P(vp)]),
+    ("az_selfplay_team_sample", i32, [i32, vp, vp, P(SelfPlayConfig), i32, i32, u64, u64, vp, vp, vp, i64, vp]),
+    ("az_mcts_dev_team_root_stats", i32, [i32, vp, i32, i32, vp, i64, vp]),
     ("az_match_create", i32, [vp, vp, P(MatchConfig), P(vp)]),
     ("az_match_create_teams", i32, [vp, vp, P(MatchConfig), vp, P(vp)]),
     ("az_match_destroy", None, [vp]),

@@ -34,6 +34,12 @@ symmetry ensemble (`AlphaZeroPlayer(sym_ensemble=True)`, player.py:285-329: one 
 the position under its symmetry).  `EvaluationMatch(..., n_trees=, sym_ensemble=)` and `RolloutPlayer(n_trees=)` give a
 side that many trees per game in its engine; the match driver (az_match_create_teams) spreads the roots, sums the
 count rows per game inside the ply's one tail kernel and re-roots every tree with the move in its own frame.
+
+A team's root statistics: `team_root_stats(stats, game, trees, ensemble)` merges the rows of az_mcts_dev_root_stats of every
+game's trees into the game's frame as the reference's `inverse_sym_stats` does (src/symmetry.py:140-186, what its GUI shows of
+an ensemble search; k_team_root_stats on a GPU tensor, the same arithmetic in torch elsewhere), `root_stats_dict` gives the
+reference's dict.  The self-play driver's teams (`NativeSelfPlay(n_trees=, sym_ensemble=)`, src/selfplay.py) record elements
+3..5 of it as a ply's root_wdl.
 """
 import ctypes as C
 
@@ -268,6 +274,90 @@ class EvaluationMatch:
 
     def engine_counters(self):
         return tuple(F.counters(s.h) for s in self.sides)
+
+
+STAT_HEAD = ("root_N", "root_Q", "root_M", "root_D", "root_P1W", "root_P2W")          # a root-statistics row: the head ...
+STAT_FIELDS = ("N", "Q", "prior", "noise", "M", "D", "P1W", "P2W")                      # ... then these per action
+
+
+def team_action_perms(game, trees, ensemble=False):
+    """perm[j][a]: action a of the game's frame in the frame of tree j of a team (csrc/board_sym.h `ensemble_action`;
+    involutions, Othello's pass stays); the identity for every tree of a root-parallel team."""
+    A = 7 if game == "Connect4" else 65
+    perms = np.tile(np.arange(A, dtype=np.int64), (int(trees), 1))
+    if ensemble:
+        assert int(trees) == (2 if game == "Connect4" else 4), "an ensemble has one tree per symmetry of the game"
+        if game == "Connect4":
+            perms[1] = 6 - perms[1]
+        else:
+            r, c = np.arange(64) // 8, np.arange(64) % 8
+            perms[1, :64], perms[2, :64], perms[3, :64] = 63 - np.arange(64), c * 8 + r, (7 - c) * 8 + (7 - r)
+    return perms
+
+
+def _team_root_stats_torch(stats, game, trees, ensemble):
+    """k_team_root_stats in torch: float32 throughout, every product and sum an operation of its own, sums in tree order."""
+    A = 7 if game == "Connect4" else 65
+    x = stats.reshape(-1, trees, 6 + 8 * A).to(torch.float32)
+    k = torch.tensor(float(trees), dtype=torch.float32, device=x.device)
+
+    def seq_sum(t):                                           # [n, trees, ...] -> [n, ...], tree 0 first
+        acc = t[:, 0].clone()
+        for j in range(1, trees):
+            acc = acc + t[:, j]
+        return acc
+    perms = torch.as_tensor(team_action_perms(game, trees, ensemble), device=x.device)
+    # tree j's row of action a sits at a's index in that tree's frame
+    per = x[:, :, 6:].reshape(-1, trees, A, 8)
+    per = torch.gather(per, 2, perms[None, :, :, None].expand(per.shape[0], trees, A, 8))
+    w = per[..., 0]
+    n_sum = seq_sum(w)
+    out = torch.zeros((x.shape[0], A, 8), dtype=torch.float32, device=x.device)
+    out[..., 0] = n_sum
+    for q in (2, 3):
+        out[..., q] = seq_sum(per[..., q]) / k
+    for q in (1, 4, 5, 6, 7):
+        num = seq_sum(per[..., q] * w)
+        out[..., q] = torch.where(n_sum > 0, num / n_sum, torch.zeros_like(num))
+    return torch.cat([seq_sum(x[:, :, :6]) / k, out.reshape(-1, 8 * A)], dim=1)
+
+
+def team_root_stats(stats, game, trees, ensemble=False, route=None):
+    """The root statistics of teams of trees merged into each game's frame - the reference's `inverse_sym_stats`
+    (src/symmetry.py:140-186) for trees j = 0 .. trees - 1 of every game, with the game's ensemble symmetries
+    (`ensemble`) or the identity for every tree (a root-parallel team).  stats: float32 tensor [n * trees, 6 + 8A] laid
+    out as az_mcts_dev_root_stats writes it (tree j of game g in row g * trees + j); returns [n, 6 + 8A] on the same
+    device.  route: "kernel" (az_mcts_dev_team_root_stats, a GPU tensor) or "torch" (the same arithmetic in torch ops);
+    None takes the kernel for a GPU tensor and torch for a CPU tensor - the only route there."""
+    trees = int(trees)
+    A = 7 if game == "Connect4" else 65
+    assert game in ("Connect4", "Othello") and trees >= 1
+    assert stats.dim() == 2 and stats.shape[1] == 6 + 8 * A and stats.shape[0] % trees == 0 and stats.dtype == torch.float32
+    assert not ensemble or trees == (2 if game == "Connect4" else 4), "an ensemble has one tree per symmetry of the game"
+    if route is None:
+        route = "kernel" if stats.is_cuda else "torch"
+    assert route in ("kernel", "torch")
+    if route == "torch":
+        return _team_root_stats_torch(stats, game, trees, bool(ensemble))
+    assert stats.is_cuda, "team_root_stats: the kernel route needs a GPU tensor"
+    stats = stats.contiguous()
+    n = stats.shape[0] // trees
+    merged = torch.empty((n, 6 + 8 * A), dtype=torch.float32, device=stats.device)
+    with torch.cuda.device(stats.device):
+        F.check(F.lib().az_mcts_dev_team_root_stats(0 if game == "Connect4" else 1, stats.data_ptr(), trees, int(bool(ensemble)),
+                                                    merged.data_ptr(), n, F._stream()))
+    return merged
+
+
+def root_stats_dict(merged, A):
+    """Rows [n, 6 + 8A] of root statistics as the reference's `get_root_stats` / `inverse_sym_stats` dict: root_N ..
+    root_P2W arrays of shape (n,), N .. P2W of shape (n, A); float32 numpy."""
+    m = merged.detach().cpu().numpy() if isinstance(merged, torch.Tensor) else np.asarray(merged, np.float32)
+    assert m.ndim == 2 and m.shape[1] == 6 + 8 * int(A)
+    out = {k: m[:, i].copy() for i, k in enumerate(STAT_HEAD)}
+    per = m[:, 6:].reshape(m.shape[0], int(A), 8)
+    out.update({k: per[:, :, i].copy() for i, k in enumerate(STAT_FIELDS)})
+    return out
 
 
 def rating_games(net, n_games, n_playout, pure_mcts_n_playout, n_trees=1, sym_ensemble=False, rollout_trees=1, **kw):

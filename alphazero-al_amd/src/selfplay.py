@@ -39,7 +39,7 @@ import torch
 
 from src import fused as F
 # beside what this module uses: the Replay*C mirrors, `selfplay_lib` (= abi.lib) and src/replay.py's public names, where earlier callers look for them
-from src.abi import ReplayBatchC, ReplayTensorsC, SelfPlayConfig, SelfPlayExportInfo, SelfPlayGames, lib as selfplay_lib      # noqa: F401
+from src.abi import ReplayBatchC, ReplayTensorsC, SelfPlayConfig, SelfPlayExportInfo, SelfPlayGames, SelfPlayTeams, lib as selfplay_lib      # noqa: F401
 from src.MCTS_cpp import BatchedMCTS
 from src.replay import ReplayBatches, ReplayTensors, SampledReplayTensors, augmented, replay_tensors_c, sample_size      # noqa: F401
 
@@ -329,30 +329,46 @@ class NativeSelfPlay:
     and their order are DeviceSelfPlay's, so the engine's generator hands both drivers the same noise and
     symmetry ids; the moves come from the driver's own stream of the device generator (k_sp_pick), not
     from torch's.  `sampler="tape"` with `set_action_tape()` plays recorded moves (parity tests; takes
-    the place of `sampler="reference"`)."""
+    the place of `sampler="reference"`).
+
+    Teams (az_selfplay_create_teams; the reference's `AlphaZeroPlayer(n_trees=K)` / `(sym_ensemble=True)` with
+    is_selfplay=1, player.py:248-329): `n_trees` trees search every game's root - as `sym_ensemble` one tree per board
+    symmetry of the game (2 / 4), each in its own frame, with the engine's random symmetry off (player.py:177-180) - the
+    move and the recorded policy target come from the summed visit counts, the recorded root_wdl from the merged root
+    statistics, and every tree keeps its subtree.  The engine then has n_games * trees trees (`self.search`,
+    `self.fused`); `self.B` stays the number of games, and the tape, `positions()`, `drain()` and `export()` are per
+    game."""
 
     def __init__(self, net, n_games, n_playout=200, vl_batch=4, c_init=1.4, c_base=None, alpha=0.3,
                  noise_epsilon=0.25, fpu_reduction=0.2, use_symmetry=True, mlh_slope=0.1, mlh_cap=0.2,
                  value_decay=1.0, temperature=1.0, temp_decay_moves=20, temp_endgame=0.0, seed=0,
                  reserve_slots=None, record=False, td_steps=0, refill=True, sampler="device",
                  max_finished_games=None, table_log2=0, game="Connect4", score_utility_factor=0.0, score_scale=8.0,
-                 noise_steps=0, noise_eps_min=0.1):
+                 noise_steps=0, noise_eps_min=0.1, n_trees=1, sym_ensemble=False):
         self._sp = None
-        _setup_search(self, net, n_games, n_playout, vl_batch, c_init, c_base, alpha, noise_epsilon, fpu_reduction,
-                      use_symmetry, mlh_slope, mlh_cap, value_decay, temperature, temp_decay_moves, temp_endgame, seed,
-                      table_log2, game, score_utility_factor, score_scale)
+        self.ensemble = bool(sym_ensemble)
+        self.trees = (2 if game == "Connect4" else 4) if self.ensemble else max(1, int(n_trees))      # az_game_num_augment
+        _setup_search(self, net, int(n_games) * self.trees, n_playout, vl_batch, c_init, c_base, alpha, noise_epsilon, fpu_reduction,
+                      use_symmetry and not self.ensemble, mlh_slope, mlh_cap, value_decay, temperature, temp_decay_moves,
+                      temp_endgame, seed, table_log2, game, score_utility_factor, score_scale)
+        self.n_envs = self.B                                      # trees in the engine
         assert sampler in ("device", "tape")
         self.sampler, self.refill, self.record, self.td_steps = sampler, bool(refill), bool(record), int(td_steps)
         _reserve_arenas(self, reserve_slots)
+        self.B = int(n_games)
         self.L = F.lib()
         self.config = SelfPlayConfig(float(temperature), float(temp_endgame), int(temp_decay_moves), int(self.refill),
                                      int(self.record), int(noise_steps), int(max_finished_games or 0),
                                      float(noise_epsilon), float(noise_eps_min))
         sp = C.c_void_p()
         with torch.cuda.device(self.device):
-            F.check(self.L.az_selfplay_create(self.h, C.byref(self.config), C.byref(sp)))
+            if self.trees == 1:
+                F.check(self.L.az_selfplay_create(self.h, C.byref(self.config), C.byref(sp)))
+            else:
+                self.teams = SelfPlayTeams(self.trees, int(self.ensemble))
+                F.check(self.L.az_selfplay_create_teams(self.h, C.byref(self.config), C.byref(self.teams), C.byref(sp)))
         self._sp = sp
-        self._tape = None
+        self._tape, self._tape_over = None, False
 
     def __del__(self):
         try:
@@ -363,10 +379,11 @@ class NativeSelfPlay:
             pass
 
     def set_action_tape(self, actions):
-        """actions: (n_plies, n_games) integers, -1 where a game is over; None ends the tape."""
+        """actions: (n_plies, n_games) integers, -1 where a game is over; None ends the tape: from then on the moves come
+        from the sampler (openings from a tape, then play)."""
         assert self.sampler == "tape"
         if actions is None:
-            self._tape = None
+            self._tape, self._tape_over = None, True
             F.check(self.L.az_selfplay_set_action_tape(self._sp, None, 0))
             return
         t = torch.as_tensor(np.ascontiguousarray(actions, dtype=np.int32)).to(self.device).contiguous()
@@ -377,7 +394,7 @@ class NativeSelfPlay:
 
     def step(self, n=1):
         """n plies in every game."""
-        assert self.sampler != "tape" or self._tape is not None, "sampler='tape' needs set_action_tape()"
+        assert self.sampler != "tape" or self._tape is not None or self._tape_over, "sampler='tape' needs set_action_tape()"
         self.fused._sync_fast_net()
         model = self.fused._native_model()
         s = F._stream()

@@ -411,6 +411,63 @@ int az_replay_dev_store(int game, const az_selfplay_games *games_dev, const int6
 int az_selfplay_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c,
                        uint64_t seed, uint64_t call, int32_t *actions, int64_t n, void *stream);
 
+/* ---- teams in the self-play driver ----------------------------------------------------------------------------
+ * The reference's self-play player may search SEVERAL trees of one root (AlphaZeroPlayer.get_action /
+ * _get_action_sym_ensemble with is_selfplay = 1, src/player.py:248-329): root-parallel play (n_trees = K) and the
+ * symmetry ensemble (one tree per board symmetry of the game).  Every tree of the team searches the same root, the
+ * move and the recorded policy target come from the summed visit counts, and every tree is re-rooted with the move
+ * mapped into its own frame, so each keeps its subtree.  az_selfplay_create_teams gives every game `trees` trees:
+ * tree j of game g is the engine's tree g * trees + j (the match driver's rule, see az_match_create_teams below), so
+ * n_games = n_envs / trees.  In an ensemble (trees = az_game_num_augment(game)) tree j works in the frame of the
+ * game's j-th symmetry - Connect4: identity, column mirror; Othello: the reference's ids 0, 2, 6, 7 - and the
+ * engine's own random symmetry should be off (player.py:177-180: use_symmetry = 0 in its az_search_config).  A ply:
+ *   roots    every tree of a game gets the game's position, ensemble tree j under symmetry j;
+ *   move     summed[a] = sum over j of counts[tree j][perm_j(a)] (perm_j the identity without an ensemble; the
+ *            pass stays; every perm is an involution); k_sp_pick's rule runs on that row, its draws keyed by (the
+ *            engine's seed, the driver's ply counter, the GAME) - with one tree they are az_selfplay_create's;
+ *   record   the position (the game's frame), prob = summed / its total, the legal mask of the game's position, and
+ *            the team's merged root [draw, p1, p2]: elements 3..5 of az_mcts_dev_team_root_stats, bit for bit;
+ *   re-root  every tree with the move in its own frame; a dead slot or a tape entry of -1 gives -1 to every tree;
+ *   reset    every tree of a game that ended; with noise_steps > 0 every tree of a game gets the game's epsilon.
+ * The tail has as many launches as a single-tree ply's, none of which grows with `trees`.  Trees of one game
+ * diverge only through what the engine's generator gives each TREE (root noise, symmetry ids) or, in an ensemble,
+ * through the frames.  Every per-game quantity of the calls above has n_games entries: az_selfplay_positions, the
+ * rows of the action tape, `slot` of finished games; totals[0] counts n_games positions per ply; the default store
+ * holds max(4 n_games, 1024) games.  The begin / finish route covers all trees: the caller of az_selfplay_begin_ply
+ * searches the whole engine.  az_selfplay_create is az_selfplay_create_teams with {1, 0}. */
+typedef struct az_selfplay_teams {
+    int32_t trees;       /* trees per game, >= 1 */
+    int32_t ensemble;    /* != 0: a game's trees are its symmetry ensemble */
+} az_selfplay_teams;
+#define AZ_SELFPLAY_TEAMS_BYTES 8
+#ifdef __cplusplus
+static_assert(sizeof(az_selfplay_teams) == AZ_SELFPLAY_TEAMS_BYTES, "az_selfplay_teams layout");
+#else
+_Static_assert(sizeof(az_selfplay_teams) == AZ_SELFPLAY_TEAMS_BYTES, "az_selfplay_teams layout");
+#endif
+/* AZ_ERR_ARG: a null argument, trees < 1, an n_envs that is no multiple of trees, an ensemble whose tree count is
+ * not az_game_num_augment(game). */
+int az_selfplay_create_teams(az_mcts *m, const az_selfplay_config *c, const az_selfplay_teams *t, az_selfplay **out);
+/* The team pick on caller-supplied counts, for tests - az_selfplay_sample's contract with the team in front: counts
+ * int32 [n * trees][A] and ply int32 [n] in DEVICE memory -> summed int32 [n][A] (may be NULL), actions int32 [n] in
+ * the game's frame, tree_actions int32 [n * trees] in each tree's frame (may be NULL); draws are keyed by (seed, call,
+ * game).  With trees = 1 and ensemble = 0 the actions are az_selfplay_sample's.  Only enqueues.  AZ_ERR_ARG: an
+ * unknown game, a null pointer that may not be, trees < 1, an ensemble whose tree count is not az_game_num_augment. */
+int az_selfplay_team_sample(int game, const int32_t *counts, const int32_t *ply, const az_selfplay_config *c, int trees,
+                            int ensemble, uint64_t seed, uint64_t call, int32_t *summed, int32_t *actions,
+                            int32_t *tree_actions, int64_t n, void *stream);
+/* A team's root statistics merged into the game's frame (k_team_root_stats): what the reference's inverse_sym_stats
+ * (src/symmetry.py:140-186) returns for trees j = 0 .. trees - 1, with the game's ensemble symmetries for an ensemble
+ * and the identity for a root-parallel team.  stats float32 [n * trees][6 + 8A] as az_mcts_dev_root_stats writes them
+ * (head root_N, root_Q, root_M, root_D, root_P1W, root_P2W, then per action N, Q, prior, noise, M, D, P1W, P2W) ->
+ * merged float32 [n][6 + 8A], both in DEVICE memory.  All arithmetic is float32, every product and sum rounded on its
+ * own, every sum in tree order from tree 0: head and prior / noise are sum / trees, N is the sum, Q, M, D, P1W and P2W
+ * are sum_j(x_j N_j) / sum_j(N_j) where the denominator is > 0, else 0.  numpy sums fewer than 8 float32 values in
+ * that order and pairwise from 8 on: from 8 trees on the merged means may differ from numpy's in the last bit.
+ * Only enqueues.  AZ_ERR_ARG as az_selfplay_team_sample. */
+int az_mcts_dev_team_root_stats(int game, const float *stats, int trees, int ensemble, float *merged, int64_t n,
+                                void *stream);
+
 /* ---- evaluation matches between two networks (alphazero-al_amd/csrc/match_kernels.hip) ---------------------
  * The reference's gate plays n games between two players in lock step (src/pipeline.py:264-335,
  * `_batched_eval_games`): two BatchedMCTS objects over the same games (pipeline.py:280-293), the side to move

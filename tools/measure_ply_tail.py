@@ -14,6 +14,13 @@ config 3 (Othello, 4096 games, n_playout 400, score utility 0.15, OthelloNet) - 
 One JSON line on stdout (kept under profiles/); progress on stderr.  `--record` turns recording on in both.
 
     python tools/measure_ply_tail.py [--othello] [--record] [--games N] [--n-playout N] [--plies N] [--reps N]
+                                     [--trees K | --ensemble]
+
+`--trees K [--ensemble]` compares two NATIVE drivers instead: "team" - `NativeSelfPlay(n_trees=K)` (or the game's symmetry
+ensemble, K trees) on `--games` games (default: the config's games // K) - against "single", the same driver with one tree
+per game and K times the games, i.e. the same number of trees in the engine.  Both search the same number of trees per ply
+and the team plays a K-th of the positions, so the expectation to confirm or refute is: the tail's launch count is the same,
+and the time per ply follows the number of trees searched (ply_ms about equal, positions/s about 1/K).
 
 `--trace-only DRIVER` plays `--plies` plies with one driver and exits: the program to put behind
 `rocprofv3 --kernel-trace --stats --` for the tail's device time per ply (k_sp_* against the torch kernels).
@@ -56,6 +63,10 @@ def make_driver(kind, net, args):
     kw = dict(n_playout=args.n_playout, vl_batch=4, seed=0, record=args.record)
     if args.othello:
         kw.update(game="Othello", score_utility_factor=0.15, score_scale=8.0)
+    if kind == "team":
+        return SP.NativeSelfPlay(net, args.games, n_trees=args.trees, sym_ensemble=args.ensemble, **kw)
+    if kind == "single":
+        return SP.NativeSelfPlay(net, args.games * args.trees, **kw)
     cls = SP.NativeSelfPlay if kind == "native" else SP.DeviceSelfPlay
     return cls(net, args.games, **kw)
 
@@ -99,8 +110,14 @@ def main():
     ap.add_argument("--enqueue-samples", type=int, default=4)
     ap.add_argument("--no-launch-count", action="store_true")
     ap.add_argument("--trace-only", choices=["device", "native"], default=None)
+    ap.add_argument("--trees", type=int, default=1, help="compare a team of K trees per game with single trees (see above)")
+    ap.add_argument("--ensemble", action="store_true", help="the team is the game's symmetry ensemble (K = 2 / 4)")
     args = ap.parse_args()
-    args.games = args.games or (4096 if args.othello else 8192)
+    if args.ensemble:
+        args.trees = 4 if args.othello else 2
+    teams = args.trees > 1
+    assert not (teams and args.trace_only), "--trace-only takes no team"
+    args.games = args.games or (4096 if args.othello else 8192) // args.trees
     args.n_playout = args.n_playout or (400 if args.othello else 200)
     args.plies = args.plies or (3 if args.othello else 20)
     args.lead_in = (2 if args.othello else 12) if args.lead_in is None else args.lead_in
@@ -116,13 +133,14 @@ def main():
         print(json.dumps({"driver": args.trace_only, "plies": args.lead_in + args.plies, "totals": sp.read_totals()}), flush=True)
         return
 
-    drivers = {k: make_driver(k, net, args) for k in ("device", "native")}
+    kinds = ("team", "single") if teams else ("device", "native")
+    drivers = {k: make_driver(k, net, args) for k in kinds}
     for k, sp in drivers.items():
         t = time.perf_counter()
         step(sp, args.lead_in)
         torch.cuda.synchronize()
         log("%s: lead-in of %d plies in %.2f s" % (k, args.lead_in, time.perf_counter() - t))
-    res = {k: dict(positions_per_s=[], host_enqueue_ms=[]) for k in drivers}
+    res = {k: dict(positions_per_s=[], ply_ms=[], host_enqueue_ms=[]) for k in drivers}
     for rep in range(args.reps):
         for k, sp in drivers.items():
             torch.cuda.synchronize()
@@ -130,7 +148,8 @@ def main():
             step(sp, args.plies)
             torch.cuda.synchronize()
             el = time.perf_counter() - t0
-            res[k]["positions_per_s"].append(args.games * args.plies / el)
+            res[k]["positions_per_s"].append(sp.B * args.plies / el)
+            res[k]["ply_ms"].append(el / args.plies * 1e3)
             enq = []
             for _ in range(args.enqueue_samples):
                 torch.cuda.synchronize()
@@ -143,7 +162,9 @@ def main():
     out = {"tool": "measure_ply_tail", "game": "Othello" if args.othello else "Connect4", "games": args.games,
            "n_playout": args.n_playout, "vl_batch": 4, "evaluator": args.evaluator, "record": args.record,
            "plies_per_repetition": args.plies, "repetitions": args.reps, "lead_in_plies": args.lead_in,
-           "native_model": drivers["native"].fused._native_model() is not None}
+           "native_model": drivers[kinds[1]].fused._native_model() is not None}
+    if teams:
+        out.update(trees=args.trees, ensemble=args.ensemble, trees_in_engine=args.games * args.trees)
     for k, r in res.items():
         d = {}
         for name, v in r.items():
@@ -159,9 +180,14 @@ def main():
                 d["tail_launches_per_ply"] = None
                 d["tail_launches_error"] = repr(e)
         out[k] = d
-    pd, pn = out["device"]["positions_per_s"], out["native"]["positions_per_s"]
-    out["native_over_device"] = round(pn["median"] / pd["median"], 4)
-    out["device_spread"] = round((pd["max"] - pd["min"]) / pd["median"], 4)
+    if teams:
+        pt, ps = out["team"]["ply_ms"], out["single"]["ply_ms"]
+        out["team_ply_ms_over_single"] = round(pt["median"] / ps["median"], 4)
+        out["single_spread"] = round((ps["max"] - ps["min"]) / ps["median"], 4)
+    else:
+        pd, pn = out["device"]["positions_per_s"], out["native"]["positions_per_s"]
+        out["native_over_device"] = round(pn["median"] / pd["median"], 4)
+        out["device_spread"] = round((pd["max"] - pd["min"]) / pd["median"], 4)
     print(json.dumps(out), flush=True)
 
 

@@ -1,7 +1,8 @@
 // engine_internal.h - what the host-side translation units of libaz_mcts.so share: the error type, the device
 // buffers, the engine object and the small helpers of the C ABI's entry points.  Nothing here is exported as a
 // C symbol; the shared pieces live in az::host, as the launchers of kernels.h live in az.  Included by engine.hip,
-// engine_host.hip, engine_dev.hip, selfplay_driver.hip and match_driver.hip.
+// engine_host.hip, engine_dev.hip, selfplay_driver.hip and match_driver.hip, and for the error type and the entry points'
+// helpers by train_kernels.hip and optim_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -165,6 +166,9 @@ inline void require(bool ok, const std::string &msg)
     if (!ok) throw AzError(AZ_ERR_ARG, msg);
 }
 
+// a device address an entry point may hand a kernel: not null, and a multiple of `to` bytes
+inline bool aligned(const void *p, uintptr_t to) { return p != nullptr && reinterpret_cast<uintptr_t>(p) % to == 0; }
+
 // the status of a C ABI call made from inside another one: its failure, text included, becomes the caller's
 inline void check_rc(int rc)
 {
@@ -205,7 +209,7 @@ struct PlyDriver {
 };
 
 }  // namespace az::host
-// this header serves the five host translation units only, and all of them are written in these names
+// this header serves the host translation units only, and all of them are written in these names
 using namespace az::host;
 
 struct az_mcts {

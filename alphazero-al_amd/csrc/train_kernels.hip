@@ -371,8 +371,6 @@ using namespace az::host;
 
 namespace {
 
-bool aligned(const void *p, uintptr_t to) { return p != nullptr && reinterpret_cast<uintptr_t>(p) % to == 0; }
-
 // every check of az_train.h, before anything is enqueued
 az::TrainArgs train_args(const std::string &w, int game, const az_replay_batch *b, const az_train_heads *h, int64_t N,
                          const az_train_loss_config *c, const az_train_loss_out *o, bool need_workspace)

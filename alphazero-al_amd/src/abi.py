@@ -269,6 +269,10 @@ PROTOTYPES = (
     ("az_train_dev_loss", i32, [i32, P(ReplayBatchC), P(TrainHeadsC), i64, P(TrainLossConfigC), P(TrainLossOutC), vp]),
     ("az_train_dev_loss_grad", i32, [i32, P(ReplayBatchC), P(TrainHeadsC), i64, P(TrainLossConfigC), P(TrainLossOutC), vp,
                                      P(TrainGradsC), vp]),
+    ("az_opt_create", i32, [i64, vp, vp, i32, P(vp)]),
+    ("az_opt_destroy", None, [vp]),
+    ("az_opt_bind", i32, [vp, vp, vp, vp]),
+    ("az_opt_dev_step", i32, [vp, vp, vp, vp, f32, vp, vp]),
 )
 
 _LIB = None

@@ -11,8 +11,9 @@ autograd run their mirror image and reads the value head's predictions back for 
                     on a GPU.
     macro_f1        sklearn's macro F1 as a function of the nine confusion counts.
     train_step      the reference's `train_step` with the net as first argument: `net.train_step(loader, augment,
-                    ...)` becomes `train_step(net, loader, augment, ...)`.  Optimiser, scheduler and gradient
-                    clipping stay torch's; the device is read once, at the end.
+                    ...)` becomes `train_step(net, loader, augment, ...)`.  Scheduler, optimiser and gradient
+                    clipping stay torch's unless `net.opt` is a `ClipAdamW` (src/optim.py: `adopt(net.opt)`), which
+                    clips and steps in three launches; the device is read once, at the end.
 
 The terms are stated in include/az_train.h.  Everything here is written from that statement."""
 import ctypes as C
@@ -22,6 +23,7 @@ import torch
 
 from src.abi import ReplayBatchC, TrainGradsC, TrainHeadsC, TrainLossConfigC, TrainLossOutC, _stream, check, lib
 from src.abi import lib as train_lib      # noqa: F401  (train_lib: the name callers written before src/abi.py use)
+from src.optim import ClipAdamW
 
 GAME_OF_ACTIONS = {7: 0, 65: 1}             # the width of log_p names the game: Connect4, Othello
 
@@ -268,7 +270,8 @@ def train_step(net, dataloader, augment, ddp_model=None, n_epochs=10, distill_al
                psw_beta=0.0, entropy_lambda=0.0, td_alpha=0.0, td_steps=5, route=None):
     """The reference's `Base.train_step` with the losses from `training_loss`: `n_epochs` passes over `dataloader`
     (every batch through `augment`; `augmented` for `ReplayBatches`, which augment already), one optimiser step per
-    batch with the gradient norm clipped at 5, one scheduler step at the end.  Uses net.opt, net.scheduler and
+    batch with the gradient norm clipped at 5 (`net.opt.clip_step(5)` when net.opt is a `ClipAdamW`, else
+    `clip_grad_norm_` and `net.opt.step()`), one scheduler step at the end.  Uses net.opt, net.scheduler and
     net.aux_target_offset.  Returns (policy loss, value loss, aux loss: means over the batches; policy entropy of the
     last batch; its gradient norm; macro F1 of a no-grad forward of the last batch after the last step).  The
     device is read once, at the end."""
@@ -287,8 +290,11 @@ def train_step(net, dataloader, augment, ddp_model=None, n_epochs=10, distill_al
             log_p, value, steps = model(last[0], action_mask=last[6])
             loss = training_loss(log_p, value, steps, last, net.aux_target_offset, config, route)
             loss.total.backward()
-            grad_norm = torch.nn.utils.clip_grad_norm_(net.parameters(), 5)
-            net.opt.step()
+            if isinstance(net.opt, ClipAdamW):
+                grad_norm = net.opt.clip_step(5)
+            else:
+                grad_norm = torch.nn.utils.clip_grad_norm_(net.parameters(), 5)
+                net.opt.step()
             sums += torch.stack([loss.policy.detach(), loss.value.detach(), loss.aux.detach()])
             entropy = loss.entropy
             n_batches += 1

@@ -1,4 +1,6 @@
-/* az_train.h - the training losses of a batch and their gradients, on the device (alphazero-al_amd/csrc/train_kernels.hip).
+/* az_train.h - the learner's device side: the training losses of a batch and their gradients
+ * (alphazero-al_amd/csrc/train_kernels.hip), and below them the clipping of the gradient norm with the AdamW step
+ * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -103,6 +105,52 @@ int az_train_dev_loss(int game, const az_replay_batch *batch, const az_train_hea
 int az_train_dev_loss_grad(int game, const az_replay_batch *batch, const az_train_heads *heads, int64_t N,
                            const az_train_loss_config *config, const az_train_loss_out *out, const float *upstream,
                            const az_train_grads *grads, void *stream);
+
+/* ---- Gradient-norm clipping and the AdamW step over every tensor of an optimiser: three launches
+ * (`torch.nn.utils.clip_grad_norm_` followed by `torch.optim.AdamW.step`, as the reference's `_optimize_batch` calls them).
+ *
+ *   total_norm = sqrt(sum over every tensor with a gradient of grad^2);  coef = min(1, max_norm / (total_norm + 1e-6))
+ * and per element, in float32, in this order (t: the tensor's own step number; lr, beta1, beta2, eps, wd: its group's):
+ *   g  = grad * coef                                   (only when clipping: max_norm > 0)
+ *   p  = p * decay                                     decay = 1 - lr * wd
+ *   m  = m + (g - m) * (1 - beta1)
+ *   v  = v * beta2 + ((1 - beta2) * g) * g
+ *   p  = p - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+ *                                                      step_size = lr / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t)
+ * decay, 1 - beta1, 1 - beta2, step_size and inv_sqrt_bc2 are formed in double on the host and rounded once; division and
+ * square root are IEEE.  Non-finite values follow from the formulas (torch's error_if_nonfinite=False).
+ * The GRADIENTS ARE READ AND NEVER WRITTEN: after a step `.grad` still holds the unclipped gradient, where
+ * clip_grad_norm_ leaves the clipped one - the reference reads no gradient after the step.  A tensor whose gradient is
+ * null is skipped whole: no decay, no change of its moments, no part in the norm.
+ * The sum of squares is one partial per chunk of a tensor, added in a fixed order; no atomics: two calls on the same
+ * inputs give the same bytes.  A handle's steps belong on one stream at a time (its workspace holds the partials and
+ * coef between the launches). */
+#define AZ_OPT_MAX_GROUPS 16
+#define AZ_OPT_GROUP_HP 5                 /* lr, beta1, beta2, eps, weight_decay - doubles, per group */
+typedef struct az_opt az_opt;             /* opaque */
+
+/* A handle for n_tensors contiguous float32 tensors of numel[i] elements, tensor i in parameter group group[i]; the
+ * table that maps a workgroup to a tensor and a chunk of it is built here.  `numel` and `group` are HOST arrays.  Touches
+ * no device.  AZ_ERR_ARG: a null array or `out`; n_tensors <= 0; a numel <= 0; a group index outside [0, n_groups);
+ * n_groups outside [1, AZ_OPT_MAX_GROUPS]. */
+int  az_opt_create(int64_t n_tensors, const int64_t *numel, const int32_t *group, int32_t n_groups, az_opt **out);
+void az_opt_destroy(az_opt *o);
+/* The DEVICE addresses of every tensor's parameter and two moments (HOST arrays of n_tensors addresses each; 4-byte
+ * aligned, 16 bytes are not needed), copied to the current device.  To be called before the first step and again
+ * whenever one of the addresses has changed; may wait for the device.  AZ_ERR_ARG, with nothing changed: a null handle
+ * or array, a null or misaligned address. */
+int  az_opt_bind(az_opt *o, void *const *param, void *const *exp_avg, void *const *exp_avg_sq);
+/* One step on `stream`: k_opt_sqsum, k_opt_norm, k_opt_clip_adamw (the first and the third once per 96 tensors); nothing
+ * waits for the device, nothing is allocated or copied: the gradients' addresses travel as kernel arguments.
+ * grad[i]: DEVICE address of tensor i's gradient (4-byte aligned) or null; step[i]: the step tensor i takes now, >= 1, or
+ * 0 with a null grad[i]; group_hp[g * AZ_OPT_GROUP_HP ...]: lr, beta1, beta2, eps, weight_decay of group g (all HOST
+ * arrays).  max_norm > 0: total_norm is written to `grad_norm` (one float32 in DEVICE memory); max_norm <= 0: no
+ * clipping, the first two launches are skipped and grad_norm may be null.
+ * AZ_ERR_ARG, with nothing enqueued: a null handle or array; a step before az_opt_bind; lr < 0, a beta outside [0, 1),
+ * eps < 0 or weight_decay < 0; step[i] < 0; step[i] > 0 with a null grad[i], or step[i] == 0 with one; a misaligned
+ * gradient; max_norm > 0 with a null or misaligned grad_norm; a max_norm that is not a number. */
+int  az_opt_dev_step(az_opt *o, const void *const *grad, const int64_t *step, const double *group_hp,
+                     float max_norm, float *grad_norm, void *stream);
 
 #ifdef __cplusplus
 }

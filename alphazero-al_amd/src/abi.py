@@ -127,6 +127,23 @@ class TrainGradsC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("d_log_p", "d_value", "d_steps")]
 
 
+class TrainBlockParamsC(C.Structure):
+    """az_train_block_params (include/az_train.h).  Passed by address to a c_void_p parameter (C.byref) like MatchTeams, as
+    are the two below, so none is an entry of `MIRRORS`; tests/test_train_block_cpu.py holds their layouts to the header."""
+    _fields_ = [(n, C.c_void_p) for n in ("norm_weight", "norm_bias", "conv_weight", "conv_bias")]
+
+
+class TrainBlockSavedC(C.Structure):
+    """az_train_block_saved (include/az_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("z", "stats")]
+
+
+class TrainBlockGradsC(C.Structure):
+    """az_train_block_grads (include/az_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dx", "d_norm_weight", "d_norm_bias", "d_conv_weight", "d_conv_bias", "workspace")] + \
+               [("workspace_bytes", C.c_int64)]
+
+
 MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfig, "az_selfplay_games": SelfPlayGames,
            "az_replay_tensors": ReplayTensorsC, "az_selfplay_export_info": SelfPlayExportInfo, "az_match_config": MatchConfig,
            "az_replay_batch": ReplayBatchC, "az_nn_positions": Positions, "az_nn_heads_weights": HeadsWeights,
@@ -136,6 +153,9 @@ MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfi
 
 P, vp, cstr, i32, i64, u32, u64, f32 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
+# The three az_train_block_* struct parameters below are bound as plain c_void_p (their mirrors are no entries of `MIRRORS`,
+# see TrainBlockParamsC), so tests/test_abi_cpu.py does NOT check their pointer types: tests/test_train_block_cpu.py holds
+# the layouts instead.  A new struct belongs in `MIRRORS` with a POINTER(<mirror>) parameter, not here.
 PROTOTYPES = (
     # include/az_mcts.h
     ("az_last_error", cstr, []),
@@ -273,6 +293,9 @@ PROTOTYPES = (
     ("az_opt_destroy", None, [vp]),
     ("az_opt_bind", i32, [vp, vp, vp, vp]),
     ("az_opt_dev_step", i32, [vp, vp, vp, vp, f32, vp, vp]),
+    ("az_train_block_workspace_bytes", i64, [i64, i32]),
+    ("az_train_dev_block_fwd", i32, [vp, vp, vp, i64, f32, vp, vp, vp]),
+    ("az_train_dev_block_bwd", i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
 )
 
 _LIB = None

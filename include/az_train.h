@@ -1,6 +1,7 @@
 /* az_train.h - the learner's device side: the training losses of a batch and their gradients
- * (alphazero-al_amd/csrc/train_kernels.hip), and below them the clipping of the gradient norm with the AdamW step
- * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip).
+ * (alphazero-al_amd/csrc/train_kernels.hip), below them the clipping of the gradient norm with the AdamW step
+ * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), and last the Connect4 residual block's training forward and
+ * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -151,6 +152,80 @@ int  az_opt_bind(az_opt *o, void *const *param, void *const *exp_avg, void *cons
  * gradient; max_norm > 0 with a null or misaligned grad_norm; a max_norm that is not a number. */
 int  az_opt_dev_step(az_opt *o, const void *const *grad, const int64_t *step, const double *group_hp,
                      float max_norm, float *grad_norm, void *stream);
+
+/* ---- The Connect4 residual block's training forward and backward (alphazero-al_amd/csrc/train_block_kernels.hip):
+ * y = x + keep * silu(conv3x3(GroupNorm(1, 64)(x))), the reference's `ResidualBlock(64, 64)` with its Dropout2d factor
+ * handed in.  Everything float32, contiguous, in DEVICE memory; x, y, dy, dx are [N][64][6][7] (NCHW as torch holds
+ * them), conv_weight [64][64][3][3] (OIHW), keep [N][64] (0 or 1 / (1 - p) per sample and channel) or null for all ones.
+ *
+ * Forward, one launch, per sample n (2688 values):
+ *   mean = sum x / 2688;  rstd = 1 / sqrt(sum (x - mean)^2 / 2688 + eps)           (the biased variance, as group_norm)
+ *   xn   = (x - mean) * rstd * norm_weight[c] + norm_bias[c]
+ *   z    = conv3x3(xn, conv_weight) + conv_bias[o]     zero padding: a tap outside the board contributes nothing
+ *   y    = x + keep[n][o] * (z * sigmoid(z))
+ * Saved for the backward when asked: z [N][64][6][7] and stats [N][2] = (mean, rstd).  Nothing else is kept: the backward
+ * reads x again and forms xn as the forward did.
+ * Backward, two launches (s = sigmoid(z), xhat = (x - mean) * rstd):
+ *   dz      = dy * keep * (s + z * s * (1 - s))
+ *   d_conv_bias[o]           = sum over n, cell of dz
+ *   d_conv_weight[o][c][tap] = sum over n, cell of dz[n][o][cell] * xn[n][c][cell + tap]
+ *   dxn     = conv_transpose(dz, conv_weight)
+ *   d_norm_bias[c] = sum dxn;   d_norm_weight[c] = sum dxn * xhat
+ *   g = dxn * norm_weight[c];   dx = dy + rstd * (g - mean_n(g) - xhat * mean_n(g * xhat))       mean_n: over the sample
+ * The four parameter gradients are sums over the batch: every workgroup of the first launch walks a contiguous run of
+ * samples and leaves ONE partial row (37056 floats: d_conv_weight, d_conv_bias, d_norm_weight, d_norm_bias) in the
+ * caller's workspace; the second launch adds the rows in row order.  No atomics, nothing cleared beforehand: two calls
+ * on the same inputs give the same bytes.  `max_workgroups` caps the workgroups that walk the batch (and with them the
+ * rows): 0 is the unit's default, 256; values above 1024 count as 1024; N below the cap gives N rows.
+ * The matrix products run on the f32-input MFMA (a k-ordered chain of float32 fused multiply-adds): exact float32,
+ * nothing narrower anywhere.  Different caps add in different orders: their results agree to rounding, not in bytes. */
+typedef struct az_train_block_params {
+    const float *norm_weight;   /* [64]  4-byte aligned */
+    const float *norm_bias;     /* [64]  4-byte aligned */
+    const float *conv_weight;   /* [64][64][3][3]  16-byte aligned */
+    const float *conv_bias;     /* [64]  4-byte aligned */
+} az_train_block_params;
+#define AZ_TRAIN_BLOCK_PARAMS_BYTES 32
+typedef struct az_train_block_saved {
+    float *z;                   /* [N][64][6][7]  16-byte aligned */
+    float *stats;               /* [N][2] mean, rstd  4-byte aligned */
+} az_train_block_saved;
+#define AZ_TRAIN_BLOCK_SAVED_BYTES 16
+typedef struct az_train_block_grads {
+    float  *dx;                 /* [N][64][6][7]  16-byte aligned */
+    float  *d_norm_weight;      /* [64]  4-byte aligned */
+    float  *d_norm_bias;        /* [64]  4-byte aligned */
+    float  *d_conv_weight;      /* [64][64][3][3]  16-byte aligned */
+    float  *d_conv_bias;        /* [64]  4-byte aligned */
+    void   *workspace;          /* 16-byte aligned; its contents need not be kept */
+    int64_t workspace_bytes;    /* at least az_train_block_workspace_bytes(N, max_workgroups) */
+} az_train_block_grads;
+#define AZ_TRAIN_BLOCK_GRADS_BYTES 56
+#ifdef __cplusplus
+static_assert(sizeof(az_train_block_params) == AZ_TRAIN_BLOCK_PARAMS_BYTES && sizeof(az_train_block_saved) == AZ_TRAIN_BLOCK_SAVED_BYTES &&
+              sizeof(az_train_block_grads) == AZ_TRAIN_BLOCK_GRADS_BYTES, "az_train_block pointer structs");
+#else
+_Static_assert(sizeof(az_train_block_params) == AZ_TRAIN_BLOCK_PARAMS_BYTES && sizeof(az_train_block_saved) == AZ_TRAIN_BLOCK_SAVED_BYTES &&
+               sizeof(az_train_block_grads) == AZ_TRAIN_BLOCK_GRADS_BYTES, "az_train_block pointer structs");
+#endif
+
+/* Bytes of workspace a backward over N samples needs under this cap; -1 for N <= 0, N beyond 2^30 or a negative cap. */
+int64_t az_train_block_workspace_bytes(int64_t N, int max_workgroups);
+/* The forward: one launch on `stream`, nothing waits for the device, nothing is allocated.  `saved` null, or both of its
+ * pointers null: eval or no-grad, nothing is saved.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: N <= 0 or beyond 2^30; a null `params`, x, y or parameter;
+ * x, y, conv_weight, keep (when given) or saved z not 16-byte aligned (the three 64-vectors and stats: 4-byte);
+ * eps not positive or not finite; exactly one of the two save pointers null. */
+int az_train_dev_block_fwd(const az_train_block_params *params, const float *x, const float *keep, int64_t N, float eps,
+                           float *y, const az_train_block_saved *saved, void *stream);
+/* The backward: two launches on `stream`, nothing waits for the device, nothing is allocated.  x, keep and `params` as
+ * the forward had them, `saved` what it left.  Inputs are read, never written.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: as above, plus a null struct, dy, saved pointer, gradient or
+ * workspace; dy, dx, d_conv_weight or the workspace not 16-byte aligned (the three 64-vectors: 4-byte);
+ * max_workgroups < 0; workspace_bytes below what az_train_block_workspace_bytes(N, max_workgroups) says. */
+int az_train_dev_block_bwd(const az_train_block_params *params, const float *x, const float *keep, const float *dy,
+                           const az_train_block_saved *saved, int64_t N, int max_workgroups,
+                           const az_train_block_grads *grads, void *stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,19 @@ class TrainBlockGradsC(C.Structure):
                [("workspace_bytes", C.c_int64)]
 
 
+class TrainAttnParamsC(C.Structure):
+    """az_train_attn_params (include/az_train.h).  Bound like TrainBlockParamsC, as is the one below: passed by address to a
+    c_void_p parameter (tests/test_abi_cpu.py fixes the number of `MIRRORS` entries); tests/test_train_attn_cpu.py holds their
+    layouts to the header."""
+    _fields_ = [(n, C.c_void_p) for n in ("prenorm_weight", "qkv_weight", "gate_weight", "o_weight", "q_norm_weight", "k_norm_weight")]
+
+
+class TrainAttnGradsC(C.Structure):
+    """az_train_attn_grads (include/az_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dx", "d_prenorm_weight", "d_qkv_weight", "d_gate_weight", "d_o_weight", "d_q_norm_weight",
+                                          "d_k_norm_weight", "workspace")] + [("workspace_bytes", C.c_int64)]
+
+
 MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfig, "az_selfplay_games": SelfPlayGames,
            "az_replay_tensors": ReplayTensorsC, "az_selfplay_export_info": SelfPlayExportInfo, "az_match_config": MatchConfig,
            "az_replay_batch": ReplayBatchC, "az_nn_positions": Positions, "az_nn_heads_weights": HeadsWeights,
@@ -153,9 +166,9 @@ MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfi
 
 P, vp, cstr, i32, i64, u32, u64, f32 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
-# The three az_train_block_* struct parameters below are bound as plain c_void_p (their mirrors are no entries of `MIRRORS`,
-# see TrainBlockParamsC), so tests/test_abi_cpu.py does NOT check their pointer types: tests/test_train_block_cpu.py holds
-# the layouts instead.  A new struct belongs in `MIRRORS` with a POINTER(<mirror>) parameter, not here.
+# The three az_train_block_* and the two az_train_attn_* struct parameters below are bound as plain c_void_p (their mirrors are no entries of `MIRRORS`,
+# see TrainBlockParamsC), so tests/test_abi_cpu.py does NOT check their pointer types: tests/test_train_block_cpu.py and
+# tests/test_train_attn_cpu.py hold the layouts instead.  A new struct belongs in `MIRRORS` with a POINTER(<mirror>) parameter, not here.
 PROTOTYPES = (
     # include/az_mcts.h
     ("az_last_error", cstr, []),
@@ -296,6 +309,9 @@ PROTOTYPES = (
     ("az_train_block_workspace_bytes", i64, [i64, i32]),
     ("az_train_dev_block_fwd", i32, [vp, vp, vp, i64, f32, vp, vp, vp]),
     ("az_train_dev_block_bwd", i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    ("az_train_attn_workspace_bytes", i64, [i64, i32]),
+    ("az_train_dev_attn_fwd", i32, [vp, vp, i32, vp, f32, i64, f32, vp, vp]),
+    ("az_train_dev_attn_bwd", i32, [vp, vp, i32, vp, f32, vp, i64, f32, i32, vp, vp]),
 )
 
 _LIB = None

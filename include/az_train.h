@@ -1,7 +1,8 @@
 /* az_train.h - the learner's device side: the training losses of a batch and their gradients
  * (alphazero-al_amd/csrc/train_kernels.hip), below them the clipping of the gradient norm with the AdamW step
- * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), and last the Connect4 residual block's training forward and
- * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip).
+ * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), the Connect4 residual block's training forward and
+ * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip), and last the Connect4 gated attention
+ * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -226,6 +227,91 @@ int az_train_dev_block_fwd(const az_train_block_params *params, const float *x, 
 int az_train_dev_block_bwd(const az_train_block_params *params, const float *x, const float *keep, const float *dy,
                            const az_train_block_saved *saved, int64_t N, int max_workgroups,
                            const az_train_block_grads *grads, void *stream);
+
+/* ---- The Connect4 gated attention block's training forward and backward (alphazero-al_amd/csrc/train_attn_kernels.hip):
+ * the reference's `AttentionBlock(64, 4, dropout)` round `GatedAttention`, the last layer of `hidden`, with its dropout
+ * mask handed in.  Everything float32, contiguous, in DEVICE memory.  x and dx are [N][64][6][7] (x_token_major 0: NCHW,
+ * cell t = 7 * row + col is token t) or [N][42][64] (x_token_major 1: the memory of a channels-last NCHW tensor); y and dy
+ * are [N][42][64], token-major, as the heads take it.  dx leaves in the layout x came in.
+ *
+ * Forward, one launch, per sample, with rms(v, w) = v * (1 / sqrt(mean(v^2) + eps)) * w:
+ *   tok[t][c] = x[c][t]
+ *   h[t]      = rms(tok[t], prenorm_weight)                                 over the 64 channels
+ *   qkv[t]    = qkv_weight @ h[t]        q, k, v of head a: elements 16 a .. 16 a + 15 of thirds 0, 1, 2
+ *   g[t][a]   = gate_weight[a] . h[t]
+ *   qh, kh    = rms(q[t][a], q_norm_weight), rms(k[t][a], k_norm_weight)    over the 16 of a head, the same eps
+ *   P[a][i][:] = softmax_j(0.25 * qh[i][a] . kh[j][a])                      over the 42 keys, the row maximum taken out
+ *   P'        = P * keep(a, i, j) * keep_scale
+ *   O[i][a]   = sum_j P'[a][i][j] * v[j][a];   o[i][a] = sigmoid(g[i][a]) * O[i][a]
+ *   y[i]      = o_weight @ concat_a o[i][a] + tok[i]
+ * keep_bits is [N][4][42] uint64: bit j of word (n, a, i) says that probability (a, i, j) is kept; bits 42 .. 63 are
+ * ignored.  Null: all kept, and keep_scale must be 1.  The mask is an input so that a float64 restatement can use the
+ * same one and two calls are reproducible.
+ * Backward, two launches.  NOTHING is saved between the passes: the backward reads x and keep_bits again and runs the
+ * forward up to O once more (s = sigmoid(g), hn = tok * rinv, qn = q * rq: the normalised values before their weight):
+ *   d_o_weight[c][c'] = sum over n, i of dy[i][c] * o[i][c'];        do = dy @ o_weight
+ *   dO = do * s;   dg = (sum_d do * O) * s * (1 - s);   delta[i] = sum_d dO[i] * O[i]     (= sum_j P' dP')
+ *   dP'[i][j] = dO[i] . v[j];   dv[j] = sum_i P'[i][j] * dO[i]
+ *   dS[i][j]  = 0.25 * P[i][j] * (keep * keep_scale * dP'[i][j] - delta[i])
+ *   dqh[i] = sum_j dS[i][j] * kh[j];   dkh[j] = sum_i dS[i][j] * qh[i]
+ *   d_q_norm_weight[d] = sum dqh * qn;   u = dqh * q_norm_weight;   dq = rq * (u - qn * mean_d(u * qn))      (k alike)
+ *   d_qkv_weight[o][c] = sum over n, t of dqkv[t][o] * h[t][c];      d_gate_weight[a][c] = sum dg[t][a] * h[t][c]
+ *   dh = dqkv @ qkv_weight + dg @ gate_weight
+ *   d_prenorm_weight[c] = sum dh * hn;   u = dh * prenorm_weight;   dx's token = dy + rinv * (u - hn * mean_c(u * hn))
+ * The six parameter gradients are sums over the batch: every workgroup of the first launch walks a contiguous run of
+ * samples and leaves ONE partial row (16736 floats: d_qkv_weight, d_o_weight, d_gate_weight, d_prenorm_weight,
+ * d_q_norm_weight, d_k_norm_weight) in the caller's workspace; the second launch adds the rows in row order.  No atomics,
+ * nothing cleared beforehand: two calls on the same inputs give the same bytes.  `max_workgroups` caps the workgroups
+ * that walk the batch (and with them the rows): 0 is the unit's default, 256; values above 1024 count as 1024; N below
+ * the cap gives N rows.  The matrix products run on the f32-input MFMA: exact float32, nothing narrower anywhere.
+ * Different caps add in different orders: their results agree to rounding, not in bytes. */
+typedef struct az_train_attn_params {
+    const float *prenorm_weight;    /* [64]  4-byte aligned */
+    const float *qkv_weight;        /* [192][64]  16-byte aligned */
+    const float *gate_weight;       /* [4][64]  4-byte aligned */
+    const float *o_weight;          /* [64][64]  16-byte aligned */
+    const float *q_norm_weight;     /* [16]  4-byte aligned */
+    const float *k_norm_weight;     /* [16]  4-byte aligned */
+} az_train_attn_params;
+#define AZ_TRAIN_ATTN_PARAMS_BYTES 48
+typedef struct az_train_attn_grads {
+    float  *dx;                     /* x's shape and layout  16-byte aligned */
+    float  *d_prenorm_weight;       /* [64]  4-byte aligned */
+    float  *d_qkv_weight;           /* [192][64]  16-byte aligned */
+    float  *d_gate_weight;          /* [4][64]  4-byte aligned */
+    float  *d_o_weight;             /* [64][64]  16-byte aligned */
+    float  *d_q_norm_weight;        /* [16]  4-byte aligned */
+    float  *d_k_norm_weight;        /* [16]  4-byte aligned */
+    void   *workspace;              /* 16-byte aligned; its contents need not be kept */
+    int64_t workspace_bytes;        /* at least az_train_attn_workspace_bytes(N, max_workgroups) */
+} az_train_attn_grads;
+#define AZ_TRAIN_ATTN_GRADS_BYTES 72
+#ifdef __cplusplus
+static_assert(sizeof(az_train_attn_params) == AZ_TRAIN_ATTN_PARAMS_BYTES && sizeof(az_train_attn_grads) == AZ_TRAIN_ATTN_GRADS_BYTES,
+              "az_train_attn pointer structs");
+#else
+_Static_assert(sizeof(az_train_attn_params) == AZ_TRAIN_ATTN_PARAMS_BYTES && sizeof(az_train_attn_grads) == AZ_TRAIN_ATTN_GRADS_BYTES,
+               "az_train_attn pointer structs");
+#endif
+
+/* Bytes of workspace a backward over N samples needs under this cap; -1 for N <= 0, N beyond 2^30 or a negative cap. */
+int64_t az_train_attn_workspace_bytes(int64_t N, int max_workgroups);
+/* The forward: one launch on `stream`, nothing waits for the device, nothing is allocated.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: N <= 0 or beyond 2^30; a null `params`, x, y or parameter;
+ * x, y, qkv_weight or o_weight not 16-byte aligned (keep_bits, when given: 8-byte; the four small parameters: 4-byte);
+ * eps not positive or not finite; keep_scale not finite or below 1, or not 1 with null keep_bits; x_token_major other
+ * than 0 or 1. */
+int az_train_dev_attn_fwd(const az_train_attn_params *params, const float *x, int x_token_major,
+                          const uint64_t *keep_bits, float keep_scale, int64_t N, float eps, float *y, void *stream);
+/* The backward: two launches on `stream`, nothing waits for the device, nothing is allocated.  x, x_token_major,
+ * keep_bits, keep_scale, eps and `params` as the forward had them (the forward is run again, so its eps is needed here
+ * too).  Inputs are read, never written.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: as above, plus a null struct, dy, gradient or workspace; dy, dx,
+ * d_qkv_weight, d_o_weight or the workspace not 16-byte aligned (the four small gradients: 4-byte); max_workgroups < 0;
+ * workspace_bytes below what az_train_attn_workspace_bytes(N, max_workgroups) says. */
+int az_train_dev_attn_bwd(const az_train_attn_params *params, const float *x, int x_token_major,
+                          const uint64_t *keep_bits, float keep_scale, const float *dy, int64_t N, float eps,
+                          int max_workgroups, const az_train_attn_grads *grads, void *stream);
 
 #ifdef __cplusplus
 }

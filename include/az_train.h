@@ -1,8 +1,9 @@
 /* az_train.h - the learner's device side: the training losses of a batch and their gradients
  * (alphazero-al_amd/csrc/train_kernels.hip), below them the clipping of the gradient norm with the AdamW step
  * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), the Connect4 residual block's training forward and
- * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip), and last the Connect4 gated attention
- * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip).
+ * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip), the Connect4 gated attention
+ * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip), and last the Connect4 stem's
+ * (az_train_*stem*, alphazero-al_amd/csrc/train_stem_kernels.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -312,6 +313,89 @@ int az_train_dev_attn_fwd(const az_train_attn_params *params, const float *x, in
 int az_train_dev_attn_bwd(const az_train_attn_params *params, const float *x, int x_token_major,
                           const uint64_t *keep_bits, float keep_scale, const float *dy, int64_t N, float eps,
                           int max_workgroups, const az_train_attn_grads *grads, void *stream);
+
+/* ---- The Connect4 stem's training forward and backward (alphazero-al_amd/csrc/train_stem_kernels.hip): the reference's
+ * `_embed_state`, `hidden[0]` (Conv2d(32, 64, 3, padding 1)) and `hidden[1]` (SiLU) as one function.  Everything float32,
+ * contiguous, in DEVICE memory: state [N][3][6][7] (planes 0 and 1 are MULTIPLIERS - own, opponent - of any value, plane
+ * 2 is never read), piece_emb [2][32], pos_emb [24][32], conv_weight [64][32][3][3] (OIHW), conv_bias [64]; y and dy are
+ * [N][64][6][7] (NCHW, contiguous: what the first residual block takes without a copy).
+ *   orbit(cell) = 4 * (cell / 7) + min(cell % 7, 6 - cell % 7)                     a constant of the game, compiled in
+ *   t[n][c][cell] = (state[n][0][cell] * piece_emb[0][c] + state[n][1][cell] * piece_emb[1][c]) + pos_emb[orbit(cell)][c]
+ *   z = conv3x3(t, conv_weight) + conv_bias[o]        zero padding: a tap outside the board contributes an exact zero
+ *   y = z * sigmoid(z)
+ * Backward (s = sigmoid(z)):
+ *   dz = dy * (s + z * s * (1 - s))
+ *   d_conv_bias[o]           = sum over n, cell of dz
+ *   d_conv_weight[o][c][tap] = sum over n, cell of dz[n][o][cell] * t[n][c][cell + tap]
+ *   dt = conv_transpose(dz, conv_weight)
+ *   d_piece_emb[j][c] = sum over n, cell of state[n][j][cell] * dt[n][c][cell]
+ *   d_pos_emb[k][c]   = sum over n and the cells of orbit k of dt[n][c][cell]
+ * state gets no gradient.
+ * HOW it is computed.  The convolution is linear and t is linear in 26 features per cell, S[n][f][cell]: the two planes
+ * (f = 0, 1) and the one-hot of the cell's orbit (f = 2 .. 25); with Emb = [piece_emb; pos_emb] ([26][32]), t = Emb^T S.
+ * Forward, two launches: the first folds the parameters into a table of 3840 floats,
+ *   T[o][f][tap] = sum_c conv_weight[o][c][tap] * piece_emb[f][c]   (f < 2)      Pz = conv3x3(pos_emb[orbit(.)]) + conv_bias
+ * at the head of `workspace`; the second forms z[o][cell] = Pz[o][cell] + sum over f < 2, tap of state_f[cell + tap] *
+ * T[o][f][tap] per sample: 18 terms where the direct form has 288.
+ * Backward, three launches.  NOTHING per sample is saved: z is formed again from state and the table.  Everything follows
+ * from G[o][f][tap] = sum over n, cell of dz[n][o][cell] * S[n][f][cell + tap]:
+ *   d_conv_weight[o][c][tap] = sum_f G[o][f][tap] * Emb[f][c];       dEmb[f][c] = sum over o, tap of G[o][f][tap] * conv_weight[o][c][tap]
+ * G's piece part (f < 2) is a [64][18] sum over the samples; its position part needs only D[o][cell] = sum_n dz[n][o][cell],
+ * because the one-hot does not depend on n; d_conv_bias[o] = sum_cell D[o][cell].  Every workgroup of the first launch
+ * walks a contiguous run of samples and leaves ONE partial row (3840 floats: D, G's piece part) in the caller's
+ * workspace; the second adds the rows in row order; the third unfolds the sum into the four gradients.  No atomics,
+ * nothing cleared beforehand: two calls on the same inputs give the same bytes.  `max_workgroups` caps the workgroups
+ * that walk the batch (and with them the rows): 0 is the unit's default, 256; values above 1024 count as 1024; N below
+ * the cap gives N rows.  Every sum is a chain of float32 fused multiply-adds; nothing narrower anywhere.  Different caps
+ * add in different orders: their results agree to rounding, not in bytes.
+ * `table`, although the backward is a function of state, the parameters and dy alone: the backward
+ * takes the forward's table instead of folding the parameters a second time, which would cost a fourth launch or, inside
+ * the sample walk, more than the walk itself at a thousand samples.  It is a function of the parameters alone: any
+ * forward on the same parameters leaves the one the backward needs. */
+typedef struct az_train_stem_params {
+    const float *piece_emb;     /* [2][32]  4-byte aligned */
+    const float *pos_emb;       /* [24][32]  4-byte aligned */
+    const float *conv_weight;   /* [64][32][3][3]  4-byte aligned */
+    const float *conv_bias;     /* [64]  4-byte aligned */
+} az_train_stem_params;
+#define AZ_TRAIN_STEM_PARAMS_BYTES 32
+typedef struct az_train_stem_grads {
+    float  *d_piece_emb;        /* [2][32]  4-byte aligned */
+    float  *d_pos_emb;          /* [24][32]  4-byte aligned */
+    float  *d_conv_weight;      /* [64][32][3][3]  4-byte aligned */
+    float  *d_conv_bias;        /* [64]  4-byte aligned */
+    void   *workspace;          /* 16-byte aligned; its contents need not be kept */
+    int64_t workspace_bytes;    /* at least az_train_stem_workspace_bytes(N, max_workgroups) */
+} az_train_stem_grads;
+#define AZ_TRAIN_STEM_GRADS_BYTES 48
+#define AZ_TRAIN_STEM_TABLE_BYTES 15360
+#ifdef __cplusplus
+static_assert(sizeof(az_train_stem_params) == AZ_TRAIN_STEM_PARAMS_BYTES && sizeof(az_train_stem_grads) == AZ_TRAIN_STEM_GRADS_BYTES,
+              "az_train_stem pointer structs");
+#else
+_Static_assert(sizeof(az_train_stem_params) == AZ_TRAIN_STEM_PARAMS_BYTES && sizeof(az_train_stem_grads) == AZ_TRAIN_STEM_GRADS_BYTES,
+               "az_train_stem pointer structs");
+#endif
+
+/* Bytes of a workspace that serves both passes over N samples under this cap: the forward's table
+ * (AZ_TRAIN_STEM_TABLE_BYTES, at its head, which the backward never writes), the added row and the partial rows;
+ * -1 for N <= 0, N beyond 2^30 or a negative cap. */
+int64_t az_train_stem_workspace_bytes(int64_t N, int max_workgroups);
+/* The forward: two launches on `stream`, nothing waits for the device, nothing is allocated.  It needs the first
+ * AZ_TRAIN_STEM_TABLE_BYTES of `workspace` only and leaves the table there.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: N <= 0 or beyond 2^30; a null `params`, state, y, parameter or
+ * workspace; y or the workspace not 16-byte aligned (state and the parameters: 4-byte); workspace_bytes below
+ * AZ_TRAIN_STEM_TABLE_BYTES. */
+int az_train_dev_stem_fwd(const az_train_stem_params *params, const float *state, int64_t N, float *y,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+/* The backward: three launches on `stream`, nothing waits for the device, nothing is allocated.  state and `params` as
+ * the forward had them; `table`: the AZ_TRAIN_STEM_TABLE_BYTES a forward on these parameters left at the head of its
+ * workspace (it may be the head of `grads->workspace` itself).  Inputs, the table included, are read, never written.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: as above, plus a null struct, table, dy, gradient or workspace;
+ * table, dy or the workspace not 16-byte aligned (the four gradients: 4-byte); max_workgroups < 0; workspace_bytes below
+ * what az_train_stem_workspace_bytes(N, max_workgroups) says. */
+int az_train_dev_stem_bwd(const az_train_stem_params *params, const float *state, const float *table, const float *dy,
+                          int64_t N, int max_workgroups, const az_train_stem_grads *grads, void *stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,21 @@ class TrainStemGradsC(C.Structure):
                [("workspace_bytes", C.c_int64)]
 
 
+class TrainHeadsParamsC(C.Structure):
+    """az_train_heads_params (include/az_train.h).  Bound like TrainBlockParamsC, as is the one below: passed by address to a
+    c_void_p parameter; tests/test_train_heads_cpu.py holds their layouts to the header."""
+    _NAMES = ("policy_norm_weight", "row_gate_weight", "row_gate_bias", "policy_fc_weight", "policy_fc_bias", "policy_out_weight",
+              "policy_out_bias", "pool_norm_weight", "pool_fc_weight", "pool_fc_bias", "norm_weight", "fc_weight", "fc_bias",
+              "out_norm_weight", "value_out_weight", "value_out_bias", "aux_out_weight", "aux_out_bias")
+    _fields_ = [(n, C.c_void_p) for n in _NAMES]
+
+
+class TrainHeadsGradsC(C.Structure):
+    """az_train_heads_grads (include/az_train.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_tokens",) + tuple("d_" + n for n in TrainHeadsParamsC._NAMES) + ("workspace",)] + \
+               [("workspace_bytes", C.c_int64)]
+
+
 MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfig, "az_selfplay_games": SelfPlayGames,
            "az_replay_tensors": ReplayTensorsC, "az_selfplay_export_info": SelfPlayExportInfo, "az_match_config": MatchConfig,
            "az_replay_batch": ReplayBatchC, "az_nn_positions": Positions, "az_nn_heads_weights": HeadsWeights,
@@ -178,9 +193,9 @@ MIRRORS = {"az_search_config": SearchConfig, "az_selfplay_config": SelfPlayConfi
 
 P, vp, cstr, i32, i64, u32, u64, f32 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
-# The three az_train_block_*, the two az_train_attn_* and the two az_train_stem_* struct parameters below are bound as plain c_void_p (their mirrors are no entries of `MIRRORS`,
+# The three az_train_block_*, the two az_train_attn_*, the two az_train_stem_* and the two az_train_heads_* struct parameters below are bound as plain c_void_p (their mirrors are no entries of `MIRRORS`,
 # see TrainBlockParamsC), so tests/test_abi_cpu.py does NOT check their pointer types: tests/test_train_block_cpu.py,
-# tests/test_train_attn_cpu.py and tests/test_train_stem_cpu.py hold the layouts instead.  A new struct belongs in `MIRRORS` with a POINTER(<mirror>) parameter, not here.
+# tests/test_train_attn_cpu.py, tests/test_train_stem_cpu.py and tests/test_train_heads_cpu.py hold the layouts instead.  A new struct belongs in `MIRRORS` with a POINTER(<mirror>) parameter, not here.
 PROTOTYPES = (
     # include/az_mcts.h
     ("az_last_error", cstr, []),
@@ -327,6 +342,9 @@ PROTOTYPES = (
     ("az_train_stem_workspace_bytes", i64, [i64, i32]),
     ("az_train_dev_stem_fwd", i32, [vp, vp, i64, vp, vp, i64, vp]),
     ("az_train_dev_stem_bwd", i32, [vp, vp, vp, vp, i64, i32, vp, vp]),
+    ("az_train_heads_workspace_bytes", i64, [i64, i32]),
+    ("az_train_dev_heads_fwd", i32, [vp, vp, vp, vp, vp, i64, f32, vp, vp, vp, vp]),
+    ("az_train_dev_heads_bwd", i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i32, vp, vp]),
 )
 
 _LIB = None

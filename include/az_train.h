@@ -2,8 +2,9 @@
  * (alphazero-al_amd/csrc/train_kernels.hip), below them the clipping of the gradient norm with the AdamW step
  * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), the Connect4 residual block's training forward and
  * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip), the Connect4 gated attention
- * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip), and last the Connect4 stem's
- * (az_train_*stem*, alphazero-al_amd/csrc/train_stem_kernels.hip).
+ * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip), the Connect4 stem's
+ * (az_train_*stem*, alphazero-al_amd/csrc/train_stem_kernels.hip), and last the Connect4 heads'
+ * (az_train_*heads*, alphazero-al_amd/csrc/train_heads_kernels.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -396,6 +397,122 @@ int az_train_dev_stem_fwd(const az_train_stem_params *params, const float *state
  * what az_train_stem_workspace_bytes(N, max_workgroups) says. */
 int az_train_dev_stem_bwd(const az_train_stem_params *params, const float *state, const float *table, const float *dy,
                           int64_t N, int max_workgroups, const az_train_stem_grads *grads, void *stream);
+
+/* ---- The Connect4 heads' training forward and backward (alphazero-al_amd/csrc/train_heads_kernels.hip): the reference's
+ * `ColumnPolicyHead(64, dropout)` and `DualHead(64, 3, dropout)` as one function of the tokens, with their two dropout
+ * factors handed in.  Everything float32, contiguous, in DEVICE memory.  tokens and d_tokens are [N][42][64], what
+ * az_train_dev_attn_fwd writes and az_train_dev_attn_bwd takes as dy; token t = 7 * row + col.  legal is [N][7] bytes (a
+ * bool tensor's memory; non-zero = legal) or null for all legal.  keep_policy is [N][7][64] and keep_pool [N][64]: 0 or
+ * 1 / (1 - p) per element, or null for all ones.  log_p is [N][7], value [N][3], steps [N]: what az_train_dev_loss reads.
+ *
+ * Forward, one launch, per sample, with rms(v, w) = v * (1 / sqrt(mean(v^2) + eps)) * w over the 64 channels and ONE eps
+ * for all four norms:
+ *   policy:  xn[t]    = rms(tok[t], policy_norm_weight)
+ *            s[t]     = row_gate_weight . xn[t] + row_gate_bias
+ *            w[r][c]  = softmax over the 6 rows r of s[7 r + c], the column's maximum taken out
+ *            colf[c]  = sum_r w[r][c] * xn[7 r + c]
+ *            u[c]     = policy_fc_weight @ colf[c] + policy_fc_bias;     a[c] = u * sigmoid(u) * keep_policy[n][c]
+ *            logit[c] = legal ? policy_out_weight . a[c] + policy_out_bias : -1e9
+ *            log_p    = logit - max - log(sum exp(logit - max))       (all seven illegal: every entry is -log 7)
+ *   value:   m        = (sum_t tok[t]) / 42
+ *            z1       = pool_fc_weight @ rms(m, pool_norm_weight) + pool_fc_bias;   x1 = m + keep_pool[n] * z1 * sigmoid(z1)
+ *            z2       = fc_weight @ rms(x1, norm_weight) + fc_bias;                 h  = rms(z2 * sigmoid(z2), out_norm_weight)
+ *            value    = log_softmax(value_out_weight @ h + value_out_bias);         steps = sigmoid(aux_out_weight . h + aux_out_bias)
+ * Backward, two launches.  NOTHING is saved between the passes: the backward reads tokens, legal and the keeps again and
+ * runs the forward once more (a sample is 10.5 KB; forming it again is cheaper than writing intermediates), which is why
+ * eps is its argument too.  With silu'(z) = s + z s (1 - s), s = sigmoid(z), and for y = rms(v, w), vn = v * r:
+ * dv = r * (g * w - vn * mean(g * w * vn)), dw = sum g * vn:
+ *   d_logit[c] = legal ? d_log_p[c] - exp(log_p[c]) * sum over ALL seven k of d_log_p[k] : 0
+ *   d_policy_out_bias = sum d_logit;  d_policy_out_weight = sum d_logit[c] * a[c];  du[c] = d_logit[c] * policy_out_weight * keep_policy * silu'(u[c])
+ *   d_policy_fc_bias = sum du;  d_policy_fc_weight[o][i] = sum du[c][o] * colf[c][i];  dcolf[c] = policy_fc_weight^T du[c]
+ *   dw[r][c] = dcolf[c] . xn[7 r + c];  ds[r][c] = w[r][c] * (dw[r][c] - sum_r' w[r'][c] dw[r'][c])
+ *   d_row_gate_bias = sum ds;  d_row_gate_weight = sum ds[t] * xn[t];  dxn[t] = w[t] * dcolf[col(t)] + ds[t] * row_gate_weight
+ *   d_policy_norm_weight and the policy part of d_tokens through rms
+ *   dzv = d_value - exp(value) * sum d_value;  dza = d_steps * steps * (1 - steps);  d_value_out_*, d_aux_out_* from them and h
+ *   dh = value_out_weight^T dzv + dza * aux_out_weight -> rms(out_norm) -> * silu'(z2) -> d_fc_*, fc_weight^T -> rms(norm) -> dx1
+ *   dz1 = dx1 * keep_pool * silu'(z1) -> d_pool_fc_*, pool_fc_weight^T -> rms(pool_norm) -> dm';   dm = dx1 + dm'
+ *   d_tokens[t] = policy part[t] + dm / 42
+ * d_row_gate_bias is zero in exact arithmetic (a softmax ignores a shift) and d_policy_out_bias is zero for an all-legal
+ * row; both are the plain sums above, so what they hold is rounding.
+ * The 18 parameter gradients are sums over the batch: every workgroup of the first launch walks a contiguous run of
+ * samples, keeps its share of the sums in registers, and leaves ONE partial row (13126 floats, padded to 13128: the
+ * gradients in the order of az_train_heads_params) in the caller's workspace; the second launch adds the rows in row
+ * order.  No atomics, nothing cleared beforehand: two calls on the same inputs give the same bytes.  `max_workgroups` caps
+ * the workgroups that walk the batch (and with them the rows): 0 is the unit's default, 256; values above 1024 count as
+ * 1024; N below the cap gives N rows.  Every sum is a chain of float32 fused multiply-adds; nothing narrower anywhere.
+ * Different caps add in different orders: their results agree to rounding, not in bytes. */
+typedef struct az_train_heads_params {
+    const float *policy_norm_weight;    /* [64]  policy_head.norm.weight  4-byte aligned */
+    const float *row_gate_weight;       /* [1][64]  policy_head.row_gate.weight  4-byte aligned */
+    const float *row_gate_bias;         /* [1]  4-byte aligned */
+    const float *policy_fc_weight;      /* [64][64]  policy_head.fc.weight  16-byte aligned */
+    const float *policy_fc_bias;        /* [64]  4-byte aligned */
+    const float *policy_out_weight;     /* [1][64]  policy_head.out.weight  4-byte aligned */
+    const float *policy_out_bias;       /* [1]  4-byte aligned */
+    const float *pool_norm_weight;      /* [64]  dual_head.pool_norm.weight  4-byte aligned */
+    const float *pool_fc_weight;        /* [64][64]  dual_head.pool_fc.weight  16-byte aligned */
+    const float *pool_fc_bias;          /* [64]  4-byte aligned */
+    const float *norm_weight;           /* [64]  dual_head.norm.weight  4-byte aligned */
+    const float *fc_weight;             /* [64][64]  dual_head.fc.weight  16-byte aligned */
+    const float *fc_bias;               /* [64]  4-byte aligned */
+    const float *out_norm_weight;       /* [64]  dual_head.out_norm.weight  4-byte aligned */
+    const float *value_out_weight;      /* [3][64]  dual_head.value_out.weight  4-byte aligned */
+    const float *value_out_bias;        /* [3]  4-byte aligned */
+    const float *aux_out_weight;        /* [1][64]  dual_head.aux_out.weight  4-byte aligned */
+    const float *aux_out_bias;          /* [1]  4-byte aligned */
+} az_train_heads_params;
+#define AZ_TRAIN_HEADS_PARAMS_BYTES 144
+typedef struct az_train_heads_grads {
+    float  *d_tokens;                   /* [N][42][64]  16-byte aligned */
+    float  *d_policy_norm_weight;       /* the parameters' shapes and alignments, in their order */
+    float  *d_row_gate_weight;
+    float  *d_row_gate_bias;
+    float  *d_policy_fc_weight;
+    float  *d_policy_fc_bias;
+    float  *d_policy_out_weight;
+    float  *d_policy_out_bias;
+    float  *d_pool_norm_weight;
+    float  *d_pool_fc_weight;
+    float  *d_pool_fc_bias;
+    float  *d_norm_weight;
+    float  *d_fc_weight;
+    float  *d_fc_bias;
+    float  *d_out_norm_weight;
+    float  *d_value_out_weight;
+    float  *d_value_out_bias;
+    float  *d_aux_out_weight;
+    float  *d_aux_out_bias;
+    void   *workspace;                  /* 16-byte aligned; its contents need not be kept */
+    int64_t workspace_bytes;            /* at least az_train_heads_workspace_bytes(N, max_workgroups) */
+} az_train_heads_grads;
+#define AZ_TRAIN_HEADS_GRADS_BYTES 168
+#ifdef __cplusplus
+static_assert(sizeof(az_train_heads_params) == AZ_TRAIN_HEADS_PARAMS_BYTES && sizeof(az_train_heads_grads) == AZ_TRAIN_HEADS_GRADS_BYTES,
+              "az_train_heads pointer structs");
+#else
+_Static_assert(sizeof(az_train_heads_params) == AZ_TRAIN_HEADS_PARAMS_BYTES && sizeof(az_train_heads_grads) == AZ_TRAIN_HEADS_GRADS_BYTES,
+               "az_train_heads pointer structs");
+#endif
+
+/* Bytes of workspace a backward over N samples needs under this cap; -1 for N <= 0, N beyond 2^30 or a negative cap. */
+int64_t az_train_heads_workspace_bytes(int64_t N, int max_workgroups);
+/* The forward: one launch on `stream`, nothing waits for the device, nothing is allocated.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: N <= 0 or beyond 2^30; a null `params`, tokens, output or
+ * parameter; tokens, the three 64 x 64 weights or a keep (when given) not 16-byte aligned (everything else: 4-byte;
+ * legal: any); eps not positive or not finite. */
+int az_train_dev_heads_fwd(const az_train_heads_params *params, const float *tokens, const uint8_t *legal,
+                           const float *keep_policy, const float *keep_pool, int64_t N, float eps,
+                           float *log_p, float *value, float *steps, void *stream);
+/* The backward: two launches on `stream`, nothing waits for the device, nothing is allocated.  tokens, legal, the keeps,
+ * eps and `params` as the forward had them; d_log_p [N][7], d_value [N][3], d_steps [N] are the gradients with respect to
+ * the three outputs (what az_train_dev_loss_grad writes).  Inputs are read, never written.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: as above, plus a null struct, upstream gradient, gradient or
+ * workspace; d_tokens, the three 64 x 64 gradients or the workspace not 16-byte aligned (everything else: 4-byte);
+ * max_workgroups < 0; workspace_bytes below what az_train_heads_workspace_bytes(N, max_workgroups) says. */
+int az_train_dev_heads_bwd(const az_train_heads_params *params, const float *tokens, const uint8_t *legal,
+                           const float *keep_policy, const float *keep_pool,
+                           const float *d_log_p, const float *d_value, const float *d_steps,
+                           int64_t N, float eps, int max_workgroups, const az_train_heads_grads *grads, void *stream);
 
 #ifdef __cplusplus
 }

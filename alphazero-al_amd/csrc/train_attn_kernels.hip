@@ -31,6 +31,7 @@
 
 #include "az_train.h"
 #include "nn_common.h"
+#include "train_common.h"
 
 namespace az {
 namespace {
@@ -45,14 +46,11 @@ constexpr int PER_LANE = (ACT + BLOCK - 1) / BLOCK;
 constexpr int RS = CH + 1, HS = HD + 1, PS = TP + 1;     // row strides in LDS: [48][65], [48][17], [48][49]
 constexpr int QKV_NUMEL = 3 * CH * CH, O_NUMEL = CH * CH, G_NUMEL = HEADS * CH;
 constexpr int ROW_FLOATS = QKV_NUMEL + O_NUMEL + G_NUMEL + CH + 2 * HD;      // 16736: d_qkv, d_o, d_gate, d_prenorm, d_q_norm, d_k_norm
-constexpr int DEFAULT_ROWS = 256, MAX_ROWS = 1024;
 constexpr int FWD_GRID = 1024;
 constexpr float SCALE = 0.25f;                  // 1 / sqrt(16)
 static_assert(WAVES == HEADS && HEADS * HD == CH, "a wavefront owns a head and a 16-channel tile");
 static_assert(ROW_FLOATS % 4 == 0 && ROW_FLOATS == 16736, "rows of the workspace stay 16-byte aligned");
 static_assert(TOK_STEPS * 4 >= TOK && TOK_STEPS * 4 <= TP, "the token steps stay inside the padded rows");
-
-using f4 = float __attribute__((ext_vector_type(4)));
 
 struct AttnArgs {
     const float *x, *pre, *Wqkv, *Wg, *Wo, *qn, *kn, *dy;
@@ -84,9 +82,7 @@ struct BwdLds {
     float red[2][WAVES][HD];
 };
 
-__device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f4 zero4() { return f4{0.0f, 0.0f, 0.0f, 0.0f}; }
-__device__ __forceinline__ float sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 // element e of a sample in the caller's layout -> its place in a [48][65] token image
 __device__ __forceinline__ int token_pos(int e, int token_major)
@@ -604,15 +600,6 @@ __global__ void __launch_bounds__(BLOCK) k_attn_reduce(AttnArgs a)
     else a.d_kn[i - HD] = v;
 }
 
-// backward workgroups: every one walks `per` samples, the last one what is left
-void shape(int64_t N, int max_workgroups, AttnArgs &a)
-{
-    const int64_t cap = max_workgroups == 0 ? DEFAULT_ROWS : max_workgroups < MAX_ROWS ? max_workgroups : MAX_ROWS;
-    const int64_t groups = N < cap ? N : cap;
-    a.per = (N + groups - 1) / groups;
-    a.rows = static_cast<int>((N + a.per - 1) / a.per);
-}
-
 }  // namespace
 }  // namespace az
 
@@ -620,12 +607,10 @@ using namespace az::host;
 
 namespace {
 
-bool attn_n_ok(int64_t N) { return N > 0 && N <= (int64_t(1) << 30); }
-
 void attn_inputs(const std::string &w, const az_train_attn_params *p, const float *x, int x_token_major,
                  const uint64_t *keep_bits, float keep_scale, int64_t N, az::AttnArgs &a)
 {
-    require(attn_n_ok(N), w + ": N must be positive (and at most 2^30)");
+    require(n_ok(N), w + ": N must be positive (and at most 2^30)");
     require(p != nullptr, w + ": null argument");
     require(aligned(x, 16) && aligned(p->qkv_weight, 16) && aligned(p->o_weight, 16),
             w + ": x, qkv_weight or o_weight null or not 16-byte aligned");
@@ -646,10 +631,8 @@ extern "C" {
 
 int64_t az_train_attn_workspace_bytes(int64_t N, int max_workgroups)
 {
-    if (!attn_n_ok(N) || max_workgroups < 0) return -1;
-    az::AttnArgs a{};
-    az::shape(N, max_workgroups, a);
-    return static_cast<int64_t>(a.rows) * az::ROW_FLOATS * static_cast<int64_t>(sizeof(float));
+    if (!n_ok(N) || max_workgroups < 0) return -1;
+    return rows_bytes(partition(N, max_workgroups).rows, az::ROW_FLOATS);
 }
 
 int az_train_dev_attn_fwd(const az_train_attn_params *params, const float *x, int x_token_major, const uint64_t *keep_bits,
@@ -662,8 +645,7 @@ int az_train_dev_attn_fwd(const az_train_attn_params *params, const float *x, in
         require(eps > 0.0f && std::isfinite(eps), w + ": eps must be positive");
         require(aligned(y, 16), w + ": a null y or one that is not 16-byte aligned");
         a.y = y; a.eps = eps;
-        const unsigned grid = static_cast<unsigned>(N < az::FWD_GRID ? N : az::FWD_GRID);
-        hipLaunchKernelGGL(az::k_attn_fwd, dim3(grid), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
+        hipLaunchKernelGGL(az::k_attn_fwd, dim3(fwd_grid(N, az::FWD_GRID)), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
         HIP_OK(hipGetLastError());
     });
 }
@@ -683,8 +665,9 @@ int az_train_dev_attn_bwd(const az_train_attn_params *params, const float *x, in
                 aligned(grads->workspace, 16), w + ": dy, dx, d_qkv_weight, d_o_weight or workspace null or not 16-byte aligned");
         require(aligned(grads->d_prenorm_weight, 4) && aligned(grads->d_gate_weight, 4) && aligned(grads->d_q_norm_weight, 4) &&
                 aligned(grads->d_k_norm_weight, 4), w + ": d_prenorm_weight, d_gate_weight, d_q_norm_weight or d_k_norm_weight null or misaligned");
-        az::shape(N, max_workgroups, a);
-        require(grads->workspace_bytes >= static_cast<int64_t>(a.rows) * az::ROW_FLOATS * static_cast<int64_t>(sizeof(float)),
+        const Runs runs = partition(N, max_workgroups);
+        a.per = runs.per; a.rows = runs.rows;
+        require(grads->workspace_bytes >= rows_bytes(a.rows, az::ROW_FLOATS),
                 w + ": a workspace smaller than az_train_attn_workspace_bytes says");
         a.dy = dy; a.eps = eps;
         a.dx = grads->dx; a.d_pre = grads->d_prenorm_weight; a.d_qkv = grads->d_qkv_weight; a.d_gate = grads->d_gate_weight;

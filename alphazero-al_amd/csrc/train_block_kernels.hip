@@ -29,29 +29,26 @@
 
 #include "az_train.h"
 #include "nn_common.h"
+#include "train_common.h"
 
 namespace az {
 namespace {
 
 constexpr int WAVE = 64;
 constexpr int BLOCK = 256, WAVES = BLOCK / WAVE;
-constexpr int CH = 64, ROWS = 6, COLS = 7, CELLS = ROWS * COLS, TAPS = 9;
+constexpr int CH = 64, CELLS = ROWS * COLS, TAPS = 9;
 constexpr int ACT = CH * CELLS;                 // 2688 values of a sample
 constexpr int KK = CH * TAPS;                   // 576: a filter's weights
-constexpr int PW = COLS + 2, PAD = (ROWS + 2) * PW;      // a channel's board with its ring of zeros: 8 x 9
 constexpr int PER_LANE = (ACT + BLOCK - 1) / BLOCK;      // 11 elements a lane owns (the last round is half full)
 constexpr int CELL_TILES = 3;                   // 48 cells in tiles of 16
 constexpr int CELL_STEPS = 11;                  // 44 cells in K steps of 4
 constexpr int SPLIT = 4;                        // independent accumulation chains of the 576-term products
 constexpr int W_NUMEL = CH * KK;                // 36864
 constexpr int ROW_FLOATS = W_NUMEL + 3 * CH;    // a partial row: dW, db, dgamma, dbeta
-constexpr int DEFAULT_ROWS = 256, MAX_ROWS = 1024;
 constexpr int FWD_GRID = 2048;
 static_assert(ROW_FLOATS % 4 == 0, "rows of the workspace stay 16-byte aligned");
 static_assert(SPLIT == 4 && (CH / 4) % SPLIT == 0, "the chains are added as (0 + 1) + (2 + 3)");
 static_assert(CELL_TILES * 16 >= CELLS && CELL_STEPS * 4 >= CELLS && CH % 16 == 0 && 16 * TAPS == 9 * 16, "tile shapes");
-
-using f4 = float __attribute__((ext_vector_type(4)));
 
 struct BlockArgs {
     const float *x, *gamma, *beta, *W, *b, *keep, *dy;
@@ -63,9 +60,9 @@ struct BlockArgs {
     float eps;
 };
 
-__device__ __forceinline__ int ring_pos(int cell) { return (cell / COLS + 1) * PW + cell % COLS + 1; }
-
-// two block sums at once, each the four wavefronts' sums in a fixed order; every lane gets both
+// two block sums at once, each the four wavefronts' sums in a fixed order; every lane gets both.  Local to this file:
+// the attention kernel's only sum across wavefronts (its d_q_norm, d_k_norm tail) adds 16-lane columns it staged itself,
+// not nn_common.h's wave_sum of a whole wavefront, so the two do not mean the same additions.
 __device__ __forceinline__ void block_sum2(float &a, float &b, float *red)
 {
     a = wave_sum(a);
@@ -130,7 +127,7 @@ __device__ __forceinline__ void conv_mfma(const float *__restrict__ Wg, const fl
                 const int off = FLIP ? (2 - ky) * PW + (2 - kx) : ky * PW + kx;
 #pragma unroll
                 for (int j = 0; j < CELL_TILES; ++j)
-                    part[u][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], s[corner[j] + off], part[u][j], 0, 0, 0);
+                    part[u][j] = mfma(a[t], s[corner[j] + off], part[u][j]);
             }
         }
     }
@@ -150,8 +147,6 @@ __device__ __forceinline__ void store_tiles(const f4 acc[CELL_TILES], float *dst
         for (int r = 0; r < 4; ++r) dst[(wave * 16 + 4 * (lane >> 4) + r) * CELLS + cell] = acc[j][r];
     }
 }
-
-__device__ __forceinline__ float sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 __global__ void __launch_bounds__(BLOCK) k_block_fwd(BlockArgs a)
 {
@@ -261,7 +256,7 @@ __global__ void __launch_bounds__(BLOCK) k_block_bwd(BlockArgs a)
             xnp[at] = xhat[j] * a.gamma[c] + a.beta[c];
             const float z = zs[e], s = sigmoid(z);
             const float k = a.keep != nullptr ? a.keep[n * CH + c] : 1.0f;
-            dzp[at] = dyv[j] * k * (s + z * s * (1.0f - s));
+            dzp[at] = dyv[j] * k * (s + z * s * (1.0f - s));        // dsilu(z) spelled out: the call gives this kernel other registers
         }
         __syncthreads();
         p_db += channel_sum(dzp, PAD, [](int cell) { return ring_pos(cell); });
@@ -282,7 +277,7 @@ __global__ void __launch_bounds__(BLOCK) k_block_bwd(BlockArgs a)
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int j = 0; j < TAPS; ++j)
-                    dw[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[j], dw[mt][j], 0, 0, 0);
+                    dw[mt][j] = mfma(av[mt], bv[j], dw[mt][j]);
         }
 
         f4 acc[CELL_TILES];
@@ -344,15 +339,6 @@ __global__ void __launch_bounds__(BLOCK) k_block_reduce(BlockArgs a)
     else a.dbeta[i - W_NUMEL - 2 * CH] = v;
 }
 
-// backward workgroups: every one walks `per` samples, the last one what is left
-void shape(int64_t N, int max_workgroups, BlockArgs &a)
-{
-    const int64_t cap = max_workgroups == 0 ? DEFAULT_ROWS : max_workgroups < MAX_ROWS ? max_workgroups : MAX_ROWS;
-    const int64_t groups = N < cap ? N : cap;
-    a.per = (N + groups - 1) / groups;
-    a.rows = static_cast<int>((N + a.per - 1) / a.per);
-}
-
 }  // namespace
 }  // namespace az
 
@@ -360,12 +346,10 @@ using namespace az::host;
 
 namespace {
 
-bool block_n_ok(int64_t N) { return N > 0 && N <= (int64_t(1) << 30); }
-
 void block_inputs(const std::string &w, const az_train_block_params *p, const float *x, const float *keep, int64_t N,
                   az::BlockArgs &a)
 {
-    require(block_n_ok(N), w + ": N must be positive (and at most 2^30)");
+    require(n_ok(N), w + ": N must be positive (and at most 2^30)");
     require(p != nullptr, w + ": null argument");
     require(aligned(x, 16) && aligned(p->conv_weight, 16), w + ": x or conv_weight null or not 16-byte aligned");
     require(keep == nullptr || aligned(keep, 16), w + ": a keep that is not 16-byte aligned");
@@ -381,10 +365,8 @@ extern "C" {
 
 int64_t az_train_block_workspace_bytes(int64_t N, int max_workgroups)
 {
-    if (!block_n_ok(N) || max_workgroups < 0) return -1;
-    az::BlockArgs a{};
-    az::shape(N, max_workgroups, a);
-    return static_cast<int64_t>(a.rows) * az::ROW_FLOATS * static_cast<int64_t>(sizeof(float));
+    if (!n_ok(N) || max_workgroups < 0) return -1;
+    return rows_bytes(partition(N, max_workgroups).rows, az::ROW_FLOATS);
 }
 
 int az_train_dev_block_fwd(const az_train_block_params *params, const float *x, const float *keep, int64_t N, float eps,
@@ -402,8 +384,7 @@ int az_train_dev_block_fwd(const az_train_block_params *params, const float *x, 
             a.z_out = saved->z; a.stats_out = saved->stats;
         }
         a.y = y; a.eps = eps;
-        const unsigned grid = static_cast<unsigned>(N < az::FWD_GRID ? N : az::FWD_GRID);
-        hipLaunchKernelGGL(az::k_block_fwd, dim3(grid), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
+        hipLaunchKernelGGL(az::k_block_fwd, dim3(fwd_grid(N, az::FWD_GRID)), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
         HIP_OK(hipGetLastError());
     });
 }
@@ -422,8 +403,9 @@ int az_train_dev_block_bwd(const az_train_block_params *params, const float *x, 
                 aligned(grads->workspace, 16), w + ": dy, saved z, dx, d_conv_weight or workspace null or not 16-byte aligned");
         require(aligned(saved->stats, 4) && aligned(grads->d_norm_weight, 4) && aligned(grads->d_norm_bias, 4) &&
                 aligned(grads->d_conv_bias, 4), w + ": saved stats, d_norm_weight, d_norm_bias or d_conv_bias null or misaligned");
-        az::shape(N, max_workgroups, a);
-        require(grads->workspace_bytes >= static_cast<int64_t>(a.rows) * az::ROW_FLOATS * static_cast<int64_t>(sizeof(float)),
+        const Runs runs = partition(N, max_workgroups);
+        a.per = runs.per; a.rows = runs.rows;
+        require(grads->workspace_bytes >= rows_bytes(a.rows, az::ROW_FLOATS),
                 w + ": a workspace smaller than az_train_block_workspace_bytes says");
         a.dy = dy; a.z_in = saved->z; a.stats_in = saved->stats;
         a.dx = grads->dx; a.dgamma = grads->d_norm_weight; a.dbeta = grads->d_norm_bias; a.dW = grads->d_conv_weight;

@@ -25,18 +25,18 @@
 #include "engine_internal.h"
 
 #include "az_train.h"
+#include "train_common.h"
 
 namespace az {
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int CH = 64, ROWS = 6, COLS = 7, TOK = ROWS * COLS;
+constexpr int CH = 64, TOK = ROWS * COLS;
 constexpr int SAMPLE = TOK * CH;                // 2688 values of a sample's tokens
 constexpr int TS = 68;                          // a token's row in LDS
 constexpr int WS = 65;                          // a weight's row in LDS
 constexpr int SQ = CH * CH;
 constexpr int NPARAM = 18;
-constexpr int DEFAULT_ROWS = 256, MAX_ROWS = 1024;
 constexpr int FWD_GRID = 512;
 
 // the parameters in the order of az_train_heads_params, and where each one's gradient sits in a partial row
@@ -84,11 +84,11 @@ struct Val {
     float m, mn, rp, z1, kp, x1, x1n, rn, z2, gn, ro, h, value[3], steps;
 };
 
-__device__ __forceinline__ float sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
-__device__ __forceinline__ float dsilu(float z) { const float s = sigmoid(z); return s + z * s * (1.0f - s); }
 __device__ __forceinline__ float rinv(float sum_sq, float eps) { return 1.0f / sqrtf(sum_sq * (1.0f / CH) + eps); }
 
-__device__ __forceinline__ float wave_sum(float v)
+// Over the wavefront as a __shfl_xor butterfly, every lane its own total.  NOT nn_common.h's wave_sum (a DPP chain read from
+// lane 63): that one adds in another order and gives other bits, so this file does not include it and the name differs.
+__device__ __forceinline__ float butterfly_sum(float v)
 {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
@@ -189,7 +189,7 @@ __device__ __forceinline__ void forward_sample(const HeadsArgs &a, Shared &S, in
         float sum = 0.0f;
         for (int k = 0; k < TOK; ++k) sum += S.tok[k * TS + tid];
         v.m = sum / static_cast<float>(TOK);
-        v.rp = rinv(wave_sum(v.m * v.m), a.eps);
+        v.rp = rinv(butterfly_sum(v.m * v.m), a.eps);
         v.mn = v.m * v.rp;
         S.pn[tid] = v.mn * S.vec[V_POOLNORM][tid];
     }
@@ -216,7 +216,7 @@ __device__ __forceinline__ void forward_sample(const HeadsArgs &a, Shared &S, in
         v.z1 = dot64(&S.W[1][tid * WS], 1, S.pn) + S.vec[V_POOLB][tid];
         v.kp = a.keep_pool != nullptr ? a.keep_pool[n * CH + tid] : 1.0f;
         v.x1 = v.m + v.kp * (v.z1 * sigmoid(v.z1));
-        v.rn = rinv(wave_sum(v.x1 * v.x1), a.eps);
+        v.rn = rinv(butterfly_sum(v.x1 * v.x1), a.eps);
         v.x1n = v.x1 * v.rn;
         S.hn[tid] = v.x1n * S.vec[V_NORM][tid];
     }
@@ -236,17 +236,17 @@ __device__ __forceinline__ void forward_sample(const HeadsArgs &a, Shared &S, in
     if (tid < CH) {
         v.z2 = dot64(&S.W[2][tid * WS], 1, S.hn) + S.vec[V_FCB][tid];
         const float g = v.z2 * sigmoid(v.z2);
-        v.ro = rinv(wave_sum(g * g), a.eps);
+        v.ro = rinv(butterfly_sum(g * g), a.eps);
         v.gn = g * v.ro;
         v.h = v.gn * S.vec[V_OUTNORM][tid];
         float zv[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) zv[j] = wave_sum(v.h * S.vec[V_VAL0 + j][tid]) + S.sc[SC_VAL_B + j];
+        for (int j = 0; j < 3; ++j) zv[j] = butterfly_sum(v.h * S.vec[V_VAL0 + j][tid]) + S.sc[SC_VAL_B + j];
         const float mx = fmaxf(fmaxf(zv[0], zv[1]), zv[2]);
         const float lse = logf((expf(zv[0] - mx) + expf(zv[1] - mx)) + expf(zv[2] - mx));
 #pragma unroll
         for (int j = 0; j < 3; ++j) v.value[j] = (zv[j] - mx) - lse;
-        v.steps = sigmoid(wave_sum(v.h * S.vec[V_AUX][tid]) + S.sc[SC_AUX_B]);
+        v.steps = sigmoid(butterfly_sum(v.h * S.vec[V_AUX][tid]) + S.sc[SC_AUX_B]);
     }
     __syncthreads();
 
@@ -258,7 +258,7 @@ __device__ __forceinline__ void forward_sample(const HeadsArgs &a, Shared &S, in
             const float act = (u * sigmoid(u)) * keep;
             S.u[c][o] = u;
             S.a[c][o] = act;
-            const float logit = wave_sum(act * S.vec[V_OUTW][o]) + S.sc[SC_OUT_B];
+            const float logit = butterfly_sum(act * S.vec[V_OUTW][o]) + S.sc[SC_OUT_B];
             if (o == 0) S.logit[c] = (a.legal == nullptr || a.legal[n * COLS + c] != 0) ? logit : -1e9f;
         }
     }
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(BLOCK) k_heads_bwd(HeadsArgs a)
             dh = fmaf(S.vec[V_AUX][tid], dza, dh);
             aOutNorm = fmaf(dh, v.gn, aOutNorm);
             const float gw = dh * S.vec[V_OUTNORM][tid];
-            const float mean = wave_sum(gw * v.gn) * (1.0f / CH);
+            const float mean = butterfly_sum(gw * v.gn) * (1.0f / CH);
             const float dz2 = (v.ro * (gw - v.gn * mean)) * dsilu(v.z2);
             aFcB += dz2;
             S.dz2[tid] = dz2;
@@ -389,7 +389,7 @@ __global__ void __launch_bounds__(BLOCK) k_heads_bwd(HeadsArgs a)
             const float dhn = dot64(&S.W[2][tid], WS, S.dz2);
             aNorm = fmaf(dhn, v.x1n, aNorm);
             const float gw = dhn * S.vec[V_NORM][tid];
-            const float mean = wave_sum(gw * v.x1n) * (1.0f / CH);
+            const float mean = butterfly_sum(gw * v.x1n) * (1.0f / CH);
             dx1 = v.rn * (gw - v.x1n * mean);
             const float dz1 = (dx1 * v.kp) * dsilu(v.z1);
             aPoolB += dz1;
@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(BLOCK) k_heads_bwd(HeadsArgs a)
             const float dpn = dot64(&S.W[1][tid], WS, S.dz1);
             aPoolNorm = fmaf(dpn, v.mn, aPoolNorm);
             const float gw = dpn * S.vec[V_POOLNORM][tid];
-            const float mean = wave_sum(gw * v.mn) * (1.0f / CH);
+            const float mean = butterfly_sum(gw * v.mn) * (1.0f / CH);
             const float dm = dx1 + v.rp * (gw - v.mn * mean);
             S.dmv[tid] = dm / static_cast<float>(TOK);
         }
@@ -522,20 +522,6 @@ __global__ void __launch_bounds__(BLOCK) k_heads_reduce(HeadsArgs a)
     a.g[k][i - at] = v;
 }
 
-// backward workgroups: every one walks `per` samples, the last one what is left
-void shape(int64_t N, int max_workgroups, HeadsArgs &a)
-{
-    const int64_t cap = max_workgroups == 0 ? DEFAULT_ROWS : max_workgroups < MAX_ROWS ? max_workgroups : MAX_ROWS;
-    const int64_t groups = N < cap ? N : cap;
-    a.per = (N + groups - 1) / groups;
-    a.rows = static_cast<int>((N + a.per - 1) / a.per);
-}
-
-int64_t workspace_bytes(const HeadsArgs &a)
-{
-    return static_cast<int64_t>(a.rows) * ROW_FLOATS * static_cast<int64_t>(sizeof(float));
-}
-
 }  // namespace
 }  // namespace az
 
@@ -543,15 +529,13 @@ using namespace az::host;
 
 namespace {
 
-bool heads_n_ok(int64_t N) { return N > 0 && N <= (int64_t(1) << 30); }
-
 // which of the eighteen tensors are the 64 x 64 ones: 16-byte aligned, the rest 4-byte
 bool heads_square(int k) { return k == az::P_FC_W || k == az::D_POOL_W || k == az::D_FC_W; }
 
 void heads_inputs(const std::string &w, const az_train_heads_params *p, const float *tokens, const float *keep_policy,
                   const float *keep_pool, int64_t N, float eps, az::HeadsArgs &a)
 {
-    require(heads_n_ok(N), w + ": N must be positive (and at most 2^30)");
+    require(n_ok(N), w + ": N must be positive (and at most 2^30)");
     require(p != nullptr, w + ": null argument");
     require(eps > 0.0f && std::isfinite(eps), w + ": eps must be positive and finite");
     require(aligned(tokens, 16), w + ": null tokens or tokens that are not 16-byte aligned");
@@ -571,10 +555,8 @@ extern "C" {
 
 int64_t az_train_heads_workspace_bytes(int64_t N, int max_workgroups)
 {
-    if (!heads_n_ok(N) || max_workgroups < 0) return -1;
-    az::HeadsArgs a{};
-    az::shape(N, max_workgroups, a);
-    return az::workspace_bytes(a);
+    if (!n_ok(N) || max_workgroups < 0) return -1;
+    return rows_bytes(partition(N, max_workgroups).rows, az::ROW_FLOATS);
 }
 
 int az_train_dev_heads_fwd(const az_train_heads_params *params, const float *tokens, const uint8_t *legal,
@@ -587,8 +569,7 @@ int az_train_dev_heads_fwd(const az_train_heads_params *params, const float *tok
         heads_inputs(w, params, tokens, keep_policy, keep_pool, N, eps, a);
         require(aligned(log_p, 4) && aligned(value, 4) && aligned(steps, 4), w + ": log_p, value or steps null or misaligned");
         a.legal = legal; a.log_p = log_p; a.value = value; a.steps = steps;
-        const unsigned grid = static_cast<unsigned>(N < az::FWD_GRID ? N : az::FWD_GRID);
-        hipLaunchKernelGGL(az::k_heads_fwd, dim3(grid), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
+        hipLaunchKernelGGL(az::k_heads_fwd, dim3(fwd_grid(N, az::FWD_GRID)), dim3(az::BLOCK), 0, static_cast<hipStream_t>(stream), a);
         HIP_OK(hipGetLastError());
     });
 }
@@ -611,8 +592,9 @@ int az_train_dev_heads_bwd(const az_train_heads_params *params, const float *tok
             require(aligned(ptr[k], heads_square(k) ? 16 : 4), w + ": a gradient null or misaligned (the 64 x 64 ones: 16 bytes, the rest: 4)");
             a.g[k] = ptr[k];
         }
-        az::shape(N, max_workgroups, a);
-        require(grads->workspace_bytes >= az::workspace_bytes(a), w + ": a workspace smaller than az_train_heads_workspace_bytes says");
+        const Runs runs = partition(N, max_workgroups);
+        a.per = runs.per; a.rows = runs.rows;
+        require(grads->workspace_bytes >= rows_bytes(a.rows, az::ROW_FLOATS), w + ": a workspace smaller than az_train_heads_workspace_bytes says");
         a.legal = legal; a.d_log_p = d_log_p; a.d_value = d_value; a.d_steps = d_steps;
         a.d_tokens = grads->d_tokens; a.ws = static_cast<float *>(grads->workspace);
         const hipStream_t s = static_cast<hipStream_t>(stream);

@@ -32,16 +32,15 @@
 #include "engine_internal.h"
 
 #include "az_train.h"
-#include "nn_common.h"
+#include "train_common.h"
 
 namespace az {
 namespace {
 
 constexpr int BLOCK = 192;                      // 64 channels x 3 row pairs
-constexpr int CIN = 32, CH = 64, ROWS = 6, COLS = 7, CELLS = ROWS * COLS, TAPS = 9;
+constexpr int CIN = 32, CH = 64, CELLS = ROWS * COLS, TAPS = 9;
 constexpr int ACT = CH * CELLS;                 // 2688 values of a sample's output
 constexpr int STATE = 3 * CELLS;                // 126 values of a sample's input; the third plane is not read
-constexpr int PW = COLS + 2, PAD = (ROWS + 2) * PW;      // a plane with its ring of zeros: 8 x 9
 constexpr int OWN = ACT / BLOCK;                // 14 elements a lane owns: two board rows of one channel
 constexpr int PIECE = 2 * TAPS;                 // 18: a channel's piece weights
 constexpr int ORBITS = 24, FEATS = 2 + ORBITS;
@@ -49,7 +48,6 @@ constexpr int T_NUMEL = CH * PIECE;             // 1152
 constexpr int TABLE_FLOATS = T_NUMEL + ACT;     // 3840: T, then Pz
 constexpr int ROW_FLOATS = ACT + T_NUMEL;       // 3840: D, then G's piece part
 constexpr int W_NUMEL = CH * CIN * TAPS;        // 18432
-constexpr int DEFAULT_ROWS = 256, MAX_ROWS = 1024;
 constexpr int FWD_GRID = 1024;
 constexpr int UNFOLD_BLOCK = 256;
 static_assert(OWN * BLOCK == ACT && OWN == 2 * COLS && BLOCK == 3 * CH, "a lane owns two board rows of one channel");
@@ -65,8 +63,6 @@ struct StemArgs {
 };
 
 __device__ __forceinline__ int orbit(int cell) { const int c = cell % COLS; return 4 * (cell / COLS) + (c < COLS - 1 - c ? c : COLS - 1 - c); }
-__device__ __forceinline__ int ring_pos(int cell) { return (cell / COLS + 1) * PW + cell % COLS + 1; }
-__device__ __forceinline__ float sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 __global__ void __launch_bounds__(64) k_stem_fold(StemArgs a)
 {
@@ -210,8 +206,7 @@ __global__ void __launch_bounds__(BLOCK) k_stem_bwd(StemArgs a)
         lane_z(l, s, z);
 #pragma unroll
         for (int i = 0; i < OWN; ++i) {
-            const float sg = sigmoid(z[i]);
-            dz[i] = dz[i] * (sg + z[i] * sg * (1.0f - sg));
+            dz[i] = dz[i] * dsilu(z[i]);
             D[i] += dz[i];
         }
 #pragma unroll
@@ -308,20 +303,8 @@ __global__ void __launch_bounds__(UNFOLD_BLOCK) k_stem_unfold(StemArgs a)
     }
 }
 
-// backward workgroups: every one walks `per` samples, the last one what is left
-void shape(int64_t N, int max_workgroups, StemArgs &a)
-{
-    const int64_t cap = max_workgroups == 0 ? DEFAULT_ROWS : max_workgroups < MAX_ROWS ? max_workgroups : MAX_ROWS;
-    const int64_t groups = N < cap ? N : cap;
-    a.per = (N + groups - 1) / groups;
-    a.rows = static_cast<int>((N + a.per - 1) / a.per);
-}
-
 // the workspace: the forward's table, the added row, the partial rows
-int64_t workspace_bytes(const StemArgs &a)
-{
-    return (static_cast<int64_t>(TABLE_FLOATS) + static_cast<int64_t>(1 + a.rows) * ROW_FLOATS) * static_cast<int64_t>(sizeof(float));
-}
+int64_t workspace_bytes(int rows) { return AZ_TRAIN_STEM_TABLE_BYTES + rows_bytes(1 + rows, ROW_FLOATS); }
 
 }  // namespace
 }  // namespace az
@@ -330,11 +313,9 @@ using namespace az::host;
 
 namespace {
 
-bool stem_n_ok(int64_t N) { return N > 0 && N <= (int64_t(1) << 30); }
-
 void stem_inputs(const std::string &w, const az_train_stem_params *p, const float *state, int64_t N, az::StemArgs &a)
 {
-    require(stem_n_ok(N), w + ": N must be positive (and at most 2^30)");
+    require(n_ok(N), w + ": N must be positive (and at most 2^30)");
     require(p != nullptr, w + ": null argument");
     require(aligned(state, 4) && aligned(p->piece_emb, 4) && aligned(p->pos_emb, 4) && aligned(p->conv_weight, 4) &&
             aligned(p->conv_bias, 4), w + ": state, piece_emb, pos_emb, conv_weight or conv_bias null or misaligned");
@@ -348,10 +329,8 @@ extern "C" {
 
 int64_t az_train_stem_workspace_bytes(int64_t N, int max_workgroups)
 {
-    if (!stem_n_ok(N) || max_workgroups < 0) return -1;
-    az::StemArgs a{};
-    az::shape(N, max_workgroups, a);
-    return az::workspace_bytes(a);
+    if (!n_ok(N) || max_workgroups < 0) return -1;
+    return az::workspace_bytes(partition(N, max_workgroups).rows);
 }
 
 int az_train_dev_stem_fwd(const az_train_stem_params *params, const float *state, int64_t N, float *y,
@@ -366,9 +345,8 @@ int az_train_dev_stem_fwd(const az_train_stem_params *params, const float *state
         require(workspace_bytes >= AZ_TRAIN_STEM_TABLE_BYTES, w + ": a workspace smaller than AZ_TRAIN_STEM_TABLE_BYTES");
         a.y = y; a.table_out = static_cast<float *>(workspace); a.table = a.table_out;
         const hipStream_t s = static_cast<hipStream_t>(stream);
-        const unsigned grid = static_cast<unsigned>(N < az::FWD_GRID ? N : az::FWD_GRID);
         hipLaunchKernelGGL(az::k_stem_fold, dim3(az::CH), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(az::k_stem_fwd, dim3(grid), dim3(az::BLOCK), 0, s, a);
+        hipLaunchKernelGGL(az::k_stem_fwd, dim3(fwd_grid(N, az::FWD_GRID)), dim3(az::BLOCK), 0, s, a);
         HIP_OK(hipGetLastError());
     });
 }
@@ -386,8 +364,9 @@ int az_train_dev_stem_bwd(const az_train_stem_params *params, const float *state
                 w + ": table, dy or workspace null or not 16-byte aligned");
         require(aligned(grads->d_piece_emb, 4) && aligned(grads->d_pos_emb, 4) && aligned(grads->d_conv_weight, 4) &&
                 aligned(grads->d_conv_bias, 4), w + ": d_piece_emb, d_pos_emb, d_conv_weight or d_conv_bias null or misaligned");
-        az::shape(N, max_workgroups, a);
-        require(grads->workspace_bytes >= az::workspace_bytes(a), w + ": a workspace smaller than az_train_stem_workspace_bytes says");
+        const Runs runs = partition(N, max_workgroups);
+        a.per = runs.per; a.rows = runs.rows;
+        require(grads->workspace_bytes >= az::workspace_bytes(a.rows), w + ": a workspace smaller than az_train_stem_workspace_bytes says");
         a.table = table; a.dy = dy;
         a.dE = grads->d_piece_emb; a.dP = grads->d_pos_emb; a.dW = grads->d_conv_weight; a.db = grads->d_conv_bias;
         a.sum = static_cast<float *>(grads->workspace) + az::TABLE_FLOATS;      // the table's place is left alone

@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
+from src import train_route as R
 from src.abi import TrainAttnGradsC, TrainAttnParamsC, _stream, check, lib
 
 CHANNELS, ROWS, COLS, HEADS, HEAD_DIM = 64, 6, 7, 4, 16
@@ -63,27 +64,19 @@ def _why_not_kernel(x, params, keep_bits, keep_scale):
         return "route='kernel' takes x of shape [N, 64, 6, 7], got %s" % (tuple(x.shape),)
     if x.shape[0] == 0:
         return "route='kernel' needs at least one sample"
-    for (name, shape), t in zip((("x", tuple(x.shape)),) + PARAM_SHAPES, (x,) + tuple(params)):
-        if t is None or tuple(t.shape) != tuple(shape):
-            return "route='kernel' takes %s of shape %s" % (name, list(shape))
-        if t.dtype != torch.float32:
-            return "route='kernel' needs float32 tensors (%s is %s)" % (name, t.dtype)
-        if t.device != x.device:
-            return "route='kernel' needs every tensor on one device (%s is on %s)" % (name, t.device)
-        if name != "x" and not t.is_contiguous():
-            return "route='kernel' needs contiguous parameters (%s is not)" % name
+    named = [("x", x.shape, x)] + [(name, shape, t) for (name, shape), t in zip(PARAM_SHAPES, params)]
+    return R.tensor_fault(named, x.device, any_strides=("x",)) or _mask_fault(x, keep_bits, keep_scale) or R.cuda_fault(x)
+
+
+def _mask_fault(x, keep_bits, keep_scale):
     if keep_bits is None:
-        if keep_scale != 1.0:
-            return "route='kernel' needs keep_scale 1 without keep_bits"
-    else:
-        if tuple(keep_bits.shape) != (x.shape[0], HEADS, TOKENS) or keep_bits.dtype != torch.int64:
-            return "route='kernel' takes keep_bits of shape [N, 4, 42] and dtype int64"
-        if keep_bits.device != x.device or not keep_bits.is_contiguous():
-            return "route='kernel' needs contiguous keep_bits on x's device"
-        if not (keep_scale >= 1.0 and keep_scale != float("inf")):
-            return "route='kernel' needs a finite keep_scale of at least 1"
-    if not x.is_cuda:
-        return "route='kernel' needs CUDA tensors"
+        return None if keep_scale == 1.0 else "route='kernel' needs keep_scale 1 without keep_bits"
+    if tuple(keep_bits.shape) != (x.shape[0], HEADS, TOKENS) or keep_bits.dtype != torch.int64:
+        return "route='kernel' takes keep_bits of shape [N, 4, 42] and dtype int64"
+    if keep_bits.device != x.device or not keep_bits.is_contiguous():
+        return "route='kernel' needs contiguous keep_bits on x's device"
+    if not (keep_scale >= 1.0 and keep_scale != float("inf")):
+        return "route='kernel' needs a finite keep_scale of at least 1"
     return None
 
 
@@ -106,7 +99,7 @@ def _launch_fwd(x, params, keep_bits, keep_scale, eps):
     y = torch.empty((n, TOKENS, CHANNELS), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         check(lib().az_train_dev_attn_fwd(C.byref(_params(params)), x.data_ptr(), _token_major(x),
-                                          None if keep_bits is None else keep_bits.data_ptr(), keep_scale, n, eps, y.data_ptr(), _stream()))
+                                          R.ptr(keep_bits), keep_scale, n, eps, y.data_ptr(), _stream()))
     return y
 
 
@@ -128,14 +121,13 @@ class _Attention(torch.autograd.Function):
         dy = dy.contiguous()
         n = x.shape[0]
         L = lib()
-        size = L.az_train_attn_workspace_bytes(n, max_workgroups)
-        work = torch.empty(size, dtype=torch.uint8, device=x.device)
+        work, size = R.workspace(L.az_train_attn_workspace_bytes, n, max_workgroups, x.device)
         dx = torch.empty_like(x)                                    # x's strides: dx leaves in the layout x came in
         d_params = [torch.empty_like(p) for p in params]
         grads = TrainAttnGradsC(dx.data_ptr(), *(g.data_ptr() for g in d_params), work.data_ptr(), size)
         with torch.cuda.device(x.device):
             check(L.az_train_dev_attn_bwd(C.byref(_params(params)), x.data_ptr(), _token_major(x),
-                                          None if keep_bits is None else keep_bits.data_ptr(), keep_scale, dy.data_ptr(), n, eps,
+                                          R.ptr(keep_bits), keep_scale, dy.data_ptr(), n, eps,
                                           max_workgroups, C.byref(grads), _stream()))
         return (dx, *d_params, None, None, None, None)
 
@@ -153,10 +145,7 @@ def gated_attention(x, prenorm_weight, qkv_weight, gate_weight, o_weight, q_norm
     differentiable again); an upstream gradient that is not contiguous is made so.  `max_workgroups` caps the workgroups
     of the backward and with them the workspace (0: the kernels' default, see az_train.h).  Under `torch.no_grad()`, or
     when no input needs a gradient, nothing is saved."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
-    if route is None:
-        route = "kernel" if x.is_cuda else "torch"
+    route = R.resolve(route, x)
     params = (prenorm_weight, qkv_weight, gate_weight, o_weight, q_norm_weight, k_norm_weight)
     keep_scale = float(keep_scale)
     if route == "torch":
@@ -164,8 +153,7 @@ def gated_attention(x, prenorm_weight, qkv_weight, gate_weight, o_weight, q_norm
     why = _why_not_kernel(x, params, keep_bits, keep_scale)
     if why is not None:
         raise ValueError(why)
-    if not (eps > 0 and eps != float("inf")) or max_workgroups < 0:
-        raise ValueError("route='kernel' needs a finite eps > 0 and max_workgroups >= 0")
+    R.check_knobs(max_workgroups, eps)
     if _token_major(x) is None:
         x = x.contiguous()
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x,) + params):
@@ -234,8 +222,7 @@ def adopt_attention(net, route=None):
     and 2351 against 10447 with dropout 0.2, the mask words included).  A whole `train_step` batch of 1024 rows on the
     Connect4 module with blocks and attention adopted was 12 to 22 % shorter at the median than with the blocks alone; the
     gap was beyond the blocks-only route's own min-max spread in two runs and inside it in the third, a noisy one."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
+    R.check_route(route)
     block = _find(net)
     _check(block.attn)
 
@@ -245,16 +232,10 @@ def adopt_attention(net, route=None):
         bits, scale = draw_keep_bits(x.shape[0], p, x.device) if (attn.training and p > 0.0) else (None, 1.0)
         return gated_attention(x, attn.prenorm.weight, attn.qkv_proj.weight, attn.gate_proj.weight, attn.o_proj.weight,
                                attn.q_norm.weight, attn.k_norm.weight, bits, scale, attn.prenorm.eps, route)
-    block.forward = forward                     # an instance attribute: the class's forward stays underneath
-    block._az_attn_adopted = True
+    R.adopt(block, "_az_attn_adopted", forward)
     return 1
 
 
 def restore_attention(net):
     """Undoes `adopt_attention`: the block runs its class's forward again.  Returns the number restored (0 or 1)."""
-    count = 0
-    for block in net.hidden.children():
-        if block.__dict__.pop("_az_attn_adopted", False):
-            del block.__dict__["forward"]
-            count += 1
-    return count
+    return sum(R.restore(block, "_az_attn_adopted") for block in net.hidden.children())

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
+from src import train_route as R
 from src.abi import TrainBlockGradsC, TrainBlockParamsC, TrainBlockSavedC, _stream, check, lib
 
 CHANNELS, ROWS, COLS = 64, 6, 7
@@ -37,23 +38,11 @@ def _why_not_kernel(x, norm_weight, norm_bias, conv_weight, conv_bias, keep):
         return "route='kernel' takes x of shape [N, 64, 6, 7], got %s" % (tuple(x.shape),)
     if x.shape[0] == 0:
         return "route='kernel' needs at least one sample"
-    shapes = (("norm_weight", norm_weight, (CHANNELS,)), ("norm_bias", norm_bias, (CHANNELS,)),
-              ("conv_weight", conv_weight, (CHANNELS, CHANNELS, 3, 3)), ("conv_bias", conv_bias, (CHANNELS,)),
-              ("keep", keep, (x.shape[0], CHANNELS)))
-    for name, t, shape in (("x", x, tuple(x.shape)),) + shapes:
-        if t is None and name == "keep":
-            continue
-        if t is None or tuple(t.shape) != shape:
-            return "route='kernel' takes %s of shape %s" % (name, list(shape))
-        if t.dtype != torch.float32:
-            return "route='kernel' needs float32 tensors (%s is %s)" % (name, t.dtype)
-        if t.device != x.device:
-            return "route='kernel' needs every tensor on one device (%s is on %s)" % (name, t.device)
-        if not t.is_contiguous():
-            return "route='kernel' needs contiguous tensors (%s is not)" % name
-    if not x.is_cuda:
-        return "route='kernel' needs CUDA tensors"
-    return None
+    named = [("x", x.shape, x), ("norm_weight", (CHANNELS,), norm_weight), ("norm_bias", (CHANNELS,), norm_bias),
+             ("conv_weight", (CHANNELS, CHANNELS, 3, 3), conv_weight), ("conv_bias", (CHANNELS,), conv_bias)]
+    if keep is not None:
+        named.append(("keep", (x.shape[0], CHANNELS), keep))
+    return R.tensor_fault(named, x.device) or R.cuda_fault(x)
 
 
 def _params(norm_weight, norm_bias, conv_weight, conv_bias):
@@ -69,7 +58,7 @@ def _launch_fwd(x, norm_weight, norm_bias, conv_weight, conv_bias, keep, eps, sa
     saved = TrainBlockSavedC(z.data_ptr(), stats.data_ptr()) if save else None
     with torch.cuda.device(x.device):
         check(lib().az_train_dev_block_fwd(C.byref(_params(norm_weight, norm_bias, conv_weight, conv_bias)), x.data_ptr(),
-                                           None if keep is None else keep.data_ptr(), n, eps, y.data_ptr(),
+                                           R.ptr(keep), n, eps, y.data_ptr(),
                                            None if saved is None else C.byref(saved), _stream()))
     return y, z, stats
 
@@ -89,15 +78,14 @@ class _Block(torch.autograd.Function):
         dy = dy.contiguous()
         n = x.shape[0]
         L = lib()
-        size = L.az_train_block_workspace_bytes(n, ctx.max_workgroups)
-        work = torch.empty(size, dtype=torch.uint8, device=x.device)
+        work, size = R.workspace(L.az_train_block_workspace_bytes, n, ctx.max_workgroups, x.device)
         dx, d_nw, d_nb = torch.empty_like(x), torch.empty_like(norm_weight), torch.empty_like(norm_bias)
         d_cw, d_cb = torch.empty_like(conv_weight), torch.empty_like(conv_bias)
         saved = TrainBlockSavedC(z.data_ptr(), stats.data_ptr())
         grads = TrainBlockGradsC(dx.data_ptr(), d_nw.data_ptr(), d_nb.data_ptr(), d_cw.data_ptr(), d_cb.data_ptr(), work.data_ptr(), size)
         with torch.cuda.device(x.device):
             check(L.az_train_dev_block_bwd(C.byref(_params(norm_weight, norm_bias, conv_weight, conv_bias)), x.data_ptr(),
-                                           None if keep is None else keep.data_ptr(), dy.data_ptr(), C.byref(saved), n,
+                                           R.ptr(keep), dy.data_ptr(), C.byref(saved), n,
                                            ctx.max_workgroups, C.byref(grads), _stream()))
         return dx, d_nw, d_nb, d_cw, d_cb, None, None, None
 
@@ -113,17 +101,12 @@ def residual_block(x, norm_weight, norm_bias, conv_weight, conv_bias, keep=None,
     gradient that is not contiguous is made so.  `max_workgroups` caps the workgroups of the backward and with them the
     workspace (0: the kernels' default, see az_train.h).  Under `torch.no_grad()`, or when no input needs a gradient,
     nothing is saved."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
-    if route is None:
-        route = "kernel" if x.is_cuda else "torch"
-    if route == "torch":
+    if R.resolve(route, x) == "torch":
         return _torch_block(x, norm_weight, norm_bias, conv_weight, conv_bias, keep, eps)
     why = _why_not_kernel(x, norm_weight, norm_bias, conv_weight, conv_bias, keep)
     if why is not None:
         raise ValueError(why)
-    if not eps > 0 or max_workgroups < 0:
-        raise ValueError("route='kernel' needs eps > 0 and max_workgroups >= 0")
+    R.check_knobs(max_workgroups, eps)
     tensors = (x, norm_weight, norm_bias, conv_weight, conv_bias)
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         return _Block.apply(x, norm_weight, norm_bias, conv_weight, conv_bias, keep, float(eps), int(max_workgroups))
@@ -168,8 +151,7 @@ def adopt_blocks(net, route=None):
     the Connect4 module was 5 to 7 % shorter at the median in two runs (3.65 against 3.85 ms, 3.97 against 4.28 ms); the
     gap was beyond the unadopted route's own min-max spread in the first of them and inside it in the second, where one
     window ran long on both routes."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
+    R.check_route(route)
     hidden = getattr(net, "hidden", None)
     if hidden is None:
         raise ValueError("adopt_blocks takes a module with the reference's names: it has no `hidden`")
@@ -183,8 +165,7 @@ def adopt_blocks(net, route=None):
             if route == "kernel" or (route is None and x.is_cuda):
                 x = x.contiguous()          # the stem hands the first block a channels-last image: one copy, here
             return residual_block(x, norm.weight, norm.bias, conv.weight, conv.bias, _keep(block, x), norm.eps, route)
-        block.forward = forward             # an instance attribute: the class's forward stays underneath
-        block._az_adopted = True
+        R.adopt(block, "_az_adopted", forward)
         count += 1
     if count == 0:
         raise ValueError("adopt_blocks found no 64-channel residual block in `hidden`")
@@ -193,9 +174,4 @@ def adopt_blocks(net, route=None):
 
 def restore_blocks(net):
     """Undoes `adopt_blocks`: every adopted block runs its class's forward again.  Returns the number restored."""
-    count = 0
-    for block in net.hidden.children():
-        if block.__dict__.pop("_az_adopted", False):
-            del block.__dict__["forward"]
-            count += 1
-    return count
+    return sum(R.restore(block, "_az_adopted") for block in net.hidden.children())

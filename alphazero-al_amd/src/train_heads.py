@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
+from src import train_route as R
 from src.abi import TrainHeadsGradsC, TrainHeadsParamsC, _stream, check, lib
 
 CHANNELS, ROWS, COLS, TOKENS, CLASSES = 64, 6, 7, 42, 3
@@ -90,27 +91,17 @@ def _why_not_kernel(tokens, legal, params, keep_policy, keep_pool):
         named.append(("keep_policy", (n, COLS, CHANNELS), keep_policy))
     if keep_pool is not None:
         named.append(("keep_pool", (n, CHANNELS), keep_pool))
-    for name, shape, t in named:
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
-            return "route='kernel' takes %s of shape %s" % (name, list(shape))
-        if t.dtype != torch.float32:
-            return "route='kernel' needs float32 tensors (%s is %s)" % (name, t.dtype)
-        if t.device != tokens.device:
-            return "route='kernel' needs every tensor on one device (%s is on %s)" % (name, t.device)
-        if name != "tokens" and not t.is_contiguous():
-            return "route='kernel' needs contiguous tensors (%s is not)" % name
-    if legal is not None:
-        if not isinstance(legal, torch.Tensor) or tuple(legal.shape) != (n, COLS) or legal.dtype != torch.bool:
-            return "route='kernel' takes legal of shape [N, 7] and dtype bool"
-        if legal.device != tokens.device or not legal.is_contiguous():
-            return "route='kernel' needs a contiguous legal on the tokens' device"
-    if not tokens.is_cuda:
-        return "route='kernel' needs CUDA tensors"
+    return R.tensor_fault(named, tokens.device, any_strides=("tokens",)) or _legal_fault(tokens, legal) or R.cuda_fault(tokens)
+
+
+def _legal_fault(tokens, legal):
+    if legal is None:
+        return None
+    if not isinstance(legal, torch.Tensor) or tuple(legal.shape) != (tokens.shape[0], COLS) or legal.dtype != torch.bool:
+        return "route='kernel' takes legal of shape [N, 7] and dtype bool"
+    if legal.device != tokens.device or not legal.is_contiguous():
+        return "route='kernel' needs a contiguous legal on the tokens' device"
     return None
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _launch_fwd(tokens, legal, params, keep_policy, keep_pool, eps):
@@ -120,8 +111,8 @@ def _launch_fwd(tokens, legal, params, keep_policy, keep_pool, eps):
     value = torch.empty((n, CLASSES), dtype=torch.float32, device=tokens.device)
     steps = torch.empty((n,), dtype=torch.float32, device=tokens.device)
     with torch.cuda.device(tokens.device):
-        check(lib().az_train_dev_heads_fwd(C.byref(TrainHeadsParamsC(*(p.data_ptr() for p in params))), tokens.data_ptr(), _ptr(legal),
-                                           _ptr(keep_policy), _ptr(keep_pool), n, eps, log_p.data_ptr(), value.data_ptr(),
+        check(lib().az_train_dev_heads_fwd(C.byref(TrainHeadsParamsC(*(p.data_ptr() for p in params))), tokens.data_ptr(), R.ptr(legal),
+                                           R.ptr(keep_policy), R.ptr(keep_pool), n, eps, log_p.data_ptr(), value.data_ptr(),
                                            steps.data_ptr(), _stream()))
     return log_p, value, steps
 
@@ -144,14 +135,13 @@ class _Heads(torch.autograd.Function):
         ups = [torch.zeros(shape, dtype=torch.float32, device=tokens.device) if g is None else g.contiguous()
                for g, shape in ((d_log_p, (n, COLS)), (d_value, (n, CLASSES)), (d_steps, (n,)))]
         L = lib()
-        size = L.az_train_heads_workspace_bytes(n, max_workgroups)
-        work = torch.empty(size, dtype=torch.uint8, device=tokens.device)
+        work, size = R.workspace(L.az_train_heads_workspace_bytes, n, max_workgroups, tokens.device)
         d_tokens = torch.empty_like(tokens)
         d_params = [torch.empty_like(p) for p in params]
         grads = TrainHeadsGradsC(d_tokens.data_ptr(), *(g.data_ptr() for g in d_params), work.data_ptr(), size)
         with torch.cuda.device(tokens.device):
-            check(L.az_train_dev_heads_bwd(C.byref(TrainHeadsParamsC(*(p.data_ptr() for p in params))), tokens.data_ptr(), _ptr(legal),
-                                           _ptr(keep_policy), _ptr(keep_pool), *(u.data_ptr() for u in ups), n, eps, max_workgroups,
+            check(L.az_train_dev_heads_bwd(C.byref(TrainHeadsParamsC(*(p.data_ptr() for p in params))), tokens.data_ptr(), R.ptr(legal),
+                                           R.ptr(keep_policy), R.ptr(keep_pool), *(u.data_ptr() for u in ups), n, eps, max_workgroups,
                                            C.byref(grads), _stream()))
         return (d_tokens, None, None, None, None, None, *d_params)
 
@@ -173,10 +163,7 @@ def heads(tokens, legal, policy_norm_weight, row_gate_weight, row_gate_bias, pol
     None (an output nobody used) counts as zero.  `max_workgroups` caps the workgroups of the backward and with them the
     workspace (0: the kernels' default, see az_train.h).  Under `torch.no_grad()`, or when nothing needs a gradient,
     nothing is saved."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
-    if route is None:
-        route = "kernel" if isinstance(tokens, torch.Tensor) and tokens.is_cuda else "torch"
+    route = R.resolve(route, tokens)
     params = (policy_norm_weight, row_gate_weight, row_gate_bias, policy_fc_weight, policy_fc_bias, policy_out_weight, policy_out_bias,
               pool_norm_weight, pool_fc_weight, pool_fc_bias, norm_weight, fc_weight, fc_bias, out_norm_weight, value_out_weight,
               value_out_bias, aux_out_weight, aux_out_bias)
@@ -185,8 +172,7 @@ def heads(tokens, legal, policy_norm_weight, row_gate_weight, row_gate_bias, pol
     why = _why_not_kernel(tokens, legal, params, keep_policy, keep_pool)
     if why is not None:
         raise ValueError(why)
-    if not (eps > 0 and eps != float("inf")) or max_workgroups < 0:
-        raise ValueError("route='kernel' needs a finite eps > 0 and max_workgroups >= 0")
+    R.check_knobs(max_workgroups, eps)
     if not tokens.is_contiguous():
         tokens = tokens.contiguous()
     if torch.is_grad_enabled() and any(t.requires_grad for t in (tokens,) + params):
@@ -272,8 +258,7 @@ def adopt_heads(net, route=None):
     blocks, attention and heads adopted took 1.43 against 2.47 ms and 1.43 against 2.53 ms at the median, 42 % less than
     with the other three alone; the gap was beyond that route's own min-max spread in both runs.  The unadopted heads were
     1.36 ms, 50 %, of such a batch's forward + loss + backward."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
+    R.check_route(route)
     eps = _check(net)
     embed_name = next(k for k in _EMBED_NAMES if callable(getattr(type(net), k, None)))
 
@@ -290,17 +275,13 @@ def adopt_heads(net, route=None):
         keep_pool = draw_keep((n, CHANNELS), _rate(dh, "pool_drop"), tokens.device) if dh.training else None
         return heads(tokens, legal, *(_resolve(net, path) for _, path, _ in PARAMS), keep_policy=keep_policy, keep_pool=keep_pool,
                      eps=eps, route=route)
-    net.forward = forward                       # an instance attribute: the class's forward stays underneath
-    net._az_heads_adopted = True
+    R.adopt(net, "_az_heads_adopted", forward)
     return 1
 
 
 def restore_heads(net):
     """Undoes `adopt_heads`: the module runs its class's forward again.  Returns the number restored (0 or 1)."""
-    if not net.__dict__.pop("_az_heads_adopted", False):
-        return 0
-    net.__dict__.pop("forward", None)
-    return 1
+    return R.restore(net, "_az_heads_adopted")
 
 
 def adopt_all(net, route=None):

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
+from src import train_route as R
 from src.abi import TrainStemGradsC, TrainStemParamsC, _stream, check, lib
 
 EMBED, CHANNELS, ROWS, COLS, CELLS, ORBITS = 32, 64, 6, 7, 42, 24
@@ -50,18 +51,8 @@ def _why_not_kernel(state, params):
         return "route='kernel' takes a state of shape [N, 3, 6, 7], got %s" % (tuple(getattr(state, "shape", ())),)
     if state.shape[0] == 0:
         return "route='kernel' needs at least one sample"
-    for (name, shape), t in zip((("state", tuple(state.shape)),) + PARAM_SHAPES, (state,) + tuple(params)):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-            return "route='kernel' takes %s of shape %s" % (name, list(shape))
-        if t.dtype != torch.float32:
-            return "route='kernel' needs float32 tensors (%s is %s)" % (name, t.dtype)
-        if t.device != state.device:
-            return "route='kernel' needs every tensor on one device (%s is on %s)" % (name, t.device)
-        if not t.is_contiguous():
-            return "route='kernel' needs contiguous tensors (%s is not)" % name
-    if not state.is_cuda:
-        return "route='kernel' needs CUDA tensors"
-    return None
+    named = [("state", state.shape, state)] + [(name, shape, t) for (name, shape), t in zip(PARAM_SHAPES, params)]
+    return R.tensor_fault(named, state.device) or R.cuda_fault(state)
 
 
 def _params(params):
@@ -94,8 +85,7 @@ class _Stem(torch.autograd.Function):
         dy = dy.contiguous()
         n = state.shape[0]
         L = lib()
-        size = L.az_train_stem_workspace_bytes(n, ctx.max_workgroups)
-        work = torch.empty(size, dtype=torch.uint8, device=state.device)
+        work, size = R.workspace(L.az_train_stem_workspace_bytes, n, ctx.max_workgroups, state.device)
         out = [torch.empty_like(p) for p in params]
         grads = TrainStemGradsC(*(g.data_ptr() for g in out), work.data_ptr(), size)
         with torch.cuda.device(state.device):
@@ -117,18 +107,14 @@ def stem(state, piece_emb, pos_emb, conv_weight, conv_bias, route=None, max_work
     gradient that is not contiguous is made so.  `max_workgroups` caps the workgroups of the backward and with them the
     workspace (0: the kernels' default, see az_train.h).  Under `torch.no_grad()`, or when no parameter needs a gradient,
     only the forward runs."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
-    if route is None:
-        route = "kernel" if isinstance(state, torch.Tensor) and state.is_cuda else "torch"
+    route = R.resolve(route, state)
     params = (piece_emb, pos_emb, conv_weight, conv_bias)
     if route == "torch":
         return _torch_stem(state, *params)
     why = _why_not_kernel(state, params)
     if why is not None:
         raise ValueError(why)
-    if max_workgroups < 0:
-        raise ValueError("route='kernel' needs max_workgroups >= 0")
+    R.check_knobs(max_workgroups)
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         return _Stem.apply(state.detach(), *params, int(max_workgroups))
     return _launch_fwd(state.detach(), tuple(p.detach() for p in params))[0]
@@ -179,8 +165,7 @@ def adopt_stem(net, route=None):
     attention and stem adopted took 2.66 against 3.01 ms and 2.97 against 3.33 ms at the median, about 11 % less than with
     blocks and attention alone; the gap was beyond that route's own min-max spread in both runs.  The unadopted stem was
     0.42 ms, 14 %, of such a batch's forward + loss + backward."""
-    if route not in (None, "kernel", "torch"):
-        raise ValueError("route must be 'kernel' or 'torch'")
+    R.check_route(route)
     conv, act = _check(net)
 
     def forward(state):

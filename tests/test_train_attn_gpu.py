@@ -24,23 +24,18 @@ same bytes.
 8. `adopt_attention`, alone and with `adopt_blocks`, through three `train_step` batches against an unadopted twin;
 9. `attn.dropout_p = 0.2` in training mode."""
 import ctypes as C
-import os
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 import train_attn_ref as R
+import train_gpu_harness as H
 import train_loss_ref as TR
-from test_train_loss_cpu import golden_batch
+from train_gpu_harness import AZ_ERR_ARG, Slab, fields, loaders, swap
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "alphazero-al_amd")
-AZ_ERR_ARG = 1
-GUARD = 256
-FILL = 0xA5
 INPUTS = ("x",) + R.PARAMS + ("bits", "dy")
 GRADS = R.QUANTITIES[1:]
 OUTPUTS = R.QUANTITIES + ("ws",)
@@ -48,51 +43,7 @@ OUTPUTS = R.QUANTITIES + ("ws",)
 
 @pytest.fixture(scope="module")
 def env():
-    sys.path.insert(0, ROOT)
-    import torch  # noqa: F401  (before the engine library: one HIP runtime per process)
-    import __graft_entry__ as ge
-    ge.build()
-    if PKG not in sys.path:
-        sys.path.insert(0, PKG)
-    from src import abi, az_net, optim, train_attn, train_block, train_loss
-    return dict(torch=torch, TA=train_attn, TB=train_block, TL=train_loss, NET=az_net, O=optim, L=abi.lib(), abi=abi)
-
-
-# ---------------------------------------------------------------------------------------- tensors between guard regions
-
-class Slab:
-    """Every tensor of a call in one byte slab on the device, each 16-byte aligned with 256 guard bytes before and after;
-    outputs start as the fill pattern."""
-
-    def __init__(self, torch, inputs, out_bytes):
-        self.torch, self.at, self.size = torch, {}, {}
-        off = GUARD
-        for name, nbytes in [(k, v.nbytes) for k, v in inputs.items() if v is not None] + list(out_bytes.items()):
-            self.at[name], self.size[name] = off, nbytes
-            off = (off + nbytes + 15) // 16 * 16 + GUARD
-        self.host = np.full(off, FILL, np.uint8)
-        for k, v in inputs.items():
-            if v is not None:
-                self.host[self.at[k]:self.at[k] + v.nbytes] = np.ascontiguousarray(v).view(np.uint8).ravel()
-        self.dev = torch.empty(off, dtype=torch.uint8, device="cuda")
-        assert self.dev.data_ptr() % 16 == 0
-        self.upload()
-
-    def upload(self):
-        self.dev.copy_(self.torch.from_numpy(self.host))
-
-    def ptr(self, name, shift=0):
-        return self.dev.data_ptr() + self.at[name] + shift if name in self.at else None
-
-    def untouched_outside(self, image, written):
-        """Everything but the named outputs - guards, inputs, the other outputs' fill - is byte for byte what it was."""
-        mask = np.ones(image.size, bool)
-        for name in written:
-            mask[self.at[name]:self.at[name] + self.size[name]] = False
-        return np.array_equal(image[mask], self.host[mask])
-
-    def get(self, image, name, shape):
-        return image[self.at[name]:self.at[name] + self.size[name]].view(np.float32).reshape(shape).copy()
+    return H.load_env(("az_net", "optim", "train_attn", "train_block", "train_loss"))
 
 
 def structs(env, slab):
@@ -141,13 +92,7 @@ def run_attn(env, d, max_workgroups, token_major=0):
     return got
 
 
-def held(got, ref, own, what, quantities=R.QUANTITIES):
-    devs = R.deviations(got, ref, quantities)
-    for q in quantities:
-        print("%s %-7s kernel %.3e  torch %.3e  bound %.3e" % (what, q, devs[q], own[q], R.bound(own[q])))
-    for q in quantities:
-        assert devs[q] <= R.bound(own[q]), (what, q, devs[q], own[q])
-    return devs
+held = functools.partial(H.held, R)
 
 
 def tokens_of(x):
@@ -226,9 +171,6 @@ def test_argument_errors_enqueue_and_write_nothing(env):
     n = 7
     slab = make_slab(env, d, 0)
 
-    def fields(struct):
-        return {f[0]: getattr(struct, f[0]) for f in struct._fields_}
-
     params, grads = structs(env, slab)
 
     def fwd(**kw):
@@ -243,9 +185,6 @@ def test_argument_errors_enqueue_and_write_nothing(env):
         a.update(kw)
         return L.az_train_dev_attn_bwd(None if a["params"] is None else C.byref(a["params"]), a["x"], a["tm"], a["bits"], a["scale"],
                                        a["dy"], a["n"], a["eps"], a["cap"], None if a["grads"] is None else C.byref(a["grads"]), None)
-
-    def swap(struct, **kw):
-        return type(struct)(**dict(fields(struct), **kw))
 
     bad = []
     # null required pointers
@@ -342,43 +281,13 @@ def test_gated_attention_kernel_route_against_the_torch_route(env, monkeypatch):
 # ---------------------------------------------------------------------------------------- 8. adopt_attention under train_step
 
 def module(env, dtype, device, attention, blocks):
-    torch, O = env["torch"], env["O"]
-    torch.manual_seed(11)
-    net = env["NET"].Connect4Net(device="cpu")
-    with torch.no_grad():                       # the reference zeroes the heads' output weights: move them off zero
-        for lin in (net.policy_head.out, net.dual_head.value_out, net.dual_head.aux_out):
-            lin.weight.normal_(0, 0.05)
-    net = net.to(dtype).to(device)
-    net.opt = torch.optim.AdamW(O.reference_param_groups(net, 1e-3), lr=1e-3, weight_decay=1e-2)
-    net.scheduler = torch.optim.lr_scheduler.LambdaLR(net.opt, lambda _: 1.0)
-    if blocks:
-        assert env["TB"].adopt_blocks(net) == 3
-    if attention:
-        assert env["TA"].adopt_attention(net) == 1
-    return net
-
-
-_LOADERS = {}
-
-
-def loaders(env):
-    if not _LOADERS:
-        torch = env["torch"]
-        batch = tuple(torch.from_numpy(x) for x in golden_batch("c4"))
-        _LOADERS["cpu"] = [tuple(t[a:a + 64] for t in batch) for a in (0, 64, 32)]
-        _LOADERS["cuda"] = [tuple(t.cuda() for t in b) for b in _LOADERS["cpu"]]
-    return _LOADERS
+    return H.module(env, dtype, device, ("blocks",) * blocks + ("attention",) * attention)
 
 
 @pytest.fixture(scope="module")
 def baselines(env):
     """The unadopted float32 twin on the GPU and the float64 net on the CPU, run once for both cases."""
-    torch, TL = env["torch"], env["TL"]
-    out = {}
-    for which, dtype, device, route in (("twin", torch.float32, "cuda", "kernel"), ("exact", torch.float64, "cpu", "torch")):
-        net = module(env, dtype, device, False, False)
-        out[which] = TL.train_step(net, loaders(env)[device], lambda b: b, n_epochs=1, route=route, **dict(TR.CONFIGS["b"]))
-    return out
+    return H.baselines(env)
 
 
 @pytest.mark.parametrize("blocks", (False, True))

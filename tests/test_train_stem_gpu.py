@@ -24,22 +24,18 @@ after the forward, and every call runs twice from the same start and must give t
 6. `adopt_stem`, alone and with `adopt_blocks` + `adopt_attention`, through three `train_step` batches against an
    unadopted twin and the float64 net; with all three adopted the first block gets a contiguous image."""
 import ctypes as C
-import os
-import sys
+import functools
 
 import numpy as np
 import pytest
 
+import train_gpu_harness as H
 import train_loss_ref as TR
 import train_stem_ref as R
-from test_train_attn_gpu import Slab
-from test_train_loss_cpu import golden_batch
+from train_gpu_harness import AZ_ERR_ARG, Slab, fields, loaders, swap
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "alphazero-al_amd")
-AZ_ERR_ARG = 1
 TABLE_BYTES = 15360
 ROW_BYTES = 3840 * 4
 INPUTS = ("state",) + R.PARAMS + ("dy",)
@@ -49,14 +45,7 @@ OUTPUTS = R.QUANTITIES + ("ws",)
 
 @pytest.fixture(scope="module")
 def env():
-    sys.path.insert(0, ROOT)
-    import torch  # noqa: F401  (before the engine library: one HIP runtime per process)
-    import __graft_entry__ as ge
-    ge.build()
-    if PKG not in sys.path:
-        sys.path.insert(0, PKG)
-    from src import abi, az_net, optim, train_attn, train_block, train_loss, train_stem
-    return dict(torch=torch, TS=train_stem, TA=train_attn, TB=train_block, TL=train_loss, NET=az_net, O=optim, L=abi.lib(), abi=abi)
+    return H.load_env(("az_net", "optim", "train_attn", "train_block", "train_loss", "train_stem"))
 
 
 def structs(env, slab):
@@ -107,13 +96,7 @@ def run_stem(env, d, max_workgroups):
     return got
 
 
-def held(got, ref, own, what, quantities=R.QUANTITIES):
-    devs = R.deviations(got, ref, quantities)
-    for q in quantities:
-        print("%s %-3s kernel %.3e  torch %.3e  bound %.3e  share %.2f" % (what, q, devs[q], own[q], R.bound(own[q]), devs[q] / R.bound(own[q])))
-    for q in quantities:
-        assert devs[q] <= R.bound(own[q]), (what, q, devs[q], own[q])
-    return devs
+held = functools.partial(H.held, R)
 
 
 # ---------------------------------------------------------------------------------------- 1. sizes and caps
@@ -179,9 +162,6 @@ def test_argument_errors_enqueue_and_write_nothing(env):
     n = 7
     slab = make_slab(env, d, 0)
 
-    def fields(struct):
-        return {f[0]: getattr(struct, f[0]) for f in struct._fields_}
-
     params, grads = structs(env, slab)
 
     def fwd(**kw):
@@ -195,9 +175,6 @@ def test_argument_errors_enqueue_and_write_nothing(env):
         a.update(kw)
         return L.az_train_dev_stem_bwd(None if a["params"] is None else C.byref(a["params"]), a["state"], a["table"], a["dy"], a["n"],
                                        a["cap"], None if a["grads"] is None else C.byref(a["grads"]), None)
-
-    def swap(struct, **kw):
-        return type(struct)(**dict(fields(struct), **kw))
 
     bad = []
     # null required pointers
@@ -282,44 +259,13 @@ def test_stem_kernel_route_against_the_torch_route(env, monkeypatch):
 # ---------------------------------------------------------------------------------------- 6. adopt_stem under train_step
 
 def module(env, dtype, device, stem, others):
-    torch, O = env["torch"], env["O"]
-    torch.manual_seed(11)
-    net = env["NET"].Connect4Net(device="cpu")
-    with torch.no_grad():                       # the reference zeroes the heads' output weights and the biases: move them off zero
-        for lin in (net.policy_head.out, net.dual_head.value_out, net.dual_head.aux_out):
-            lin.weight.normal_(0, 0.05)
-        net.hidden[0].bias.normal_(0, 0.1)
-    net = net.to(dtype).to(device)
-    net.opt = torch.optim.AdamW(O.reference_param_groups(net, 1e-3), lr=1e-3, weight_decay=1e-2)
-    net.scheduler = torch.optim.lr_scheduler.LambdaLR(net.opt, lambda _: 1.0)
-    if others:
-        assert env["TB"].adopt_blocks(net) == 3 and env["TA"].adopt_attention(net) == 1
-    if stem:
-        assert env["TS"].adopt_stem(net) == 1
-    return net
-
-
-_LOADERS = {}
-
-
-def loaders(env):
-    if not _LOADERS:
-        torch = env["torch"]
-        batch = tuple(torch.from_numpy(x) for x in golden_batch("c4"))
-        _LOADERS["cpu"] = [tuple(t[a:a + 64] for t in batch) for a in (0, 64, 32)]
-        _LOADERS["cuda"] = [tuple(t.cuda() for t in b) for b in _LOADERS["cpu"]]
-    return _LOADERS
+    return H.module(env, dtype, device, ("blocks", "attention") * others + ("stem",) * stem, stem_bias=True)
 
 
 @pytest.fixture(scope="module")
 def baselines(env):
     """The unadopted float32 twin on the GPU and the float64 net on the CPU, run once for both cases."""
-    torch, TL = env["torch"], env["TL"]
-    out = {}
-    for which, dtype, device, route in (("twin", torch.float32, "cuda", "kernel"), ("exact", torch.float64, "cpu", "torch")):
-        net = module(env, dtype, device, False, False)
-        out[which] = TL.train_step(net, loaders(env)[device], lambda b: b, n_epochs=1, route=route, **dict(TR.CONFIGS["b"]))
-    return out
+    return H.baselines(env, stem_bias=True)
 
 
 @pytest.mark.parametrize("others", (False, True))

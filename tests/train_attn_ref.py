@@ -8,11 +8,12 @@ import functools
 import numpy as np
 import torch
 
+from train_ref_common import FACTOR, FLOOR, bound, dev, deviations as plain_deviations      # noqa: F401  (the tests reach them through this module)
+
 CH, HEADS, HD, ROWS, COLS, TOK = 64, 4, 16, 6, 7, 42
 EPS = 1e-5
 PARAMS = ("pre", "Wqkv", "Wg", "Wo", "qn", "kn")
 QUANTITIES = ("y", "dx", "d_pre", "d_qkv", "d_gate", "d_o", "d_qn", "d_kn")
-FLOOR, FACTOR = 1e-6, 4.0
 GPU_N = (1, 2, 7, 65)
 KEEP_P = 0.2
 DEFAULT_CAP = 256           # workgroups of the backward when max_workgroups is 0 (csrc/train_attn_kernels.hip)
@@ -86,20 +87,8 @@ def torch_route(x, pre, Wqkv, Wg, Wo, qn, kn, bits, keep_scale, dy, eps=EPS, dty
     return dict(y=y.detach().numpy(), **{k: v.grad.numpy() for k, v in zip(QUANTITIES[1:], t)})
 
 
-def dev(got, ref):
-    """Largest absolute difference over the reference's largest magnitude."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    scale = np.abs(ref).max()
-    return float(np.abs(got - ref).max() / scale) if scale > 0 else float(np.abs(got).max())
-
-
 def deviations(got, ref, quantities=QUANTITIES):
-    return {q: dev(got[q], ref[q]) for q in quantities}
-
-
-def bound(own):
-    """What a kernel may deviate from float64, given what float32 torch deviates on the same inputs."""
-    return max(FACTOR * own, FLOOR)
+    return plain_deviations(got, ref, quantities)
 
 
 @functools.lru_cache(maxsize=None)

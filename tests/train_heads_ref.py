@@ -18,6 +18,8 @@ import functools
 
 import numpy as np
 
+from train_ref_common import FACTOR, FLOOR, bound, dev      # noqa: F401  (the tests reach them through this module)
+
 ROWS, COLS, TOK, CH, CLASSES = 6, 7, 42, 64, 3
 EPS = 1e-5
 FIELDS = ("policy_norm_weight", "row_gate_weight", "row_gate_bias", "policy_fc_weight", "policy_fc_bias", "policy_out_weight",
@@ -32,7 +34,6 @@ UPSTREAM = ("d_log_p", "d_value", "d_steps")
 QUANTITIES = OUTPUTS + ("d_tokens",) + GRADS
 CANCELLING = {"d_row_gate_bias": "abs_ds", "d_policy_out_bias": "abs_dlogit"}
 ILLEGAL_ABS = 64.0
-FLOOR, FACTOR = 1e-6, 4.0
 GPU_N = (1, 2, 7, 65)
 DEFAULT_CAP = 256           # workgroups of the backward when max_workgroups is 0 (csrc/train_heads_kernels.hip)
 ROW_FLOATS = 13128          # a partial row: 13126 floats, padded
@@ -133,13 +134,6 @@ def torch_route(d, dtype=None, fn=None):
     return got
 
 
-def dev(got, ref):
-    """Largest absolute difference over the reference's largest magnitude."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    scale = np.abs(ref).max()
-    return float(np.abs(got - ref).max() / scale) if scale > 0 else float(np.abs(got).max())
-
-
 def deviations(got, ref, quantities=QUANTITIES):
     """Per quantity as the module's docstring says; `ref` is a restatement (it carries `legal`, `abs_ds`, `abs_dlogit`).
     With "log_p" among the quantities the result has "log_p_illegal" too: an absolute figure, to be held to ILLEGAL_ABS."""
@@ -155,11 +149,6 @@ def deviations(got, ref, quantities=QUANTITIES):
         else:
             out[q] = dev(g, r)
     return out
-
-
-def bound(own):
-    """What a kernel may deviate from float64, given what float32 torch deviates on the same inputs."""
-    return max(FACTOR * own, FLOOR)
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,11 +7,12 @@ import functools
 
 import numpy as np
 
+from train_ref_common import FACTOR, FLOOR, bound, dev, deviations as plain_deviations      # noqa: F401  (the tests reach them through this module)
+
 ROWS, COLS, CELLS = 6, 7, 42
 EMBED, CH, ORBITS = 32, 64, 24
 PARAMS = ("E", "P", "W", "b")
 QUANTITIES = ("y", "dW", "db", "dE", "dP")
-FLOOR, FACTOR = 1e-6, 4.0
 GPU_N = (1, 2, 7, 65)
 DEFAULT_CAP = 256           # workgroups of the backward when max_workgroups is 0 (csrc/train_stem_kernels.hip)
 ORBIT = np.array([4 * (cell // COLS) + min(cell % COLS, COLS - 1 - cell % COLS) for cell in range(CELLS)])
@@ -69,20 +70,8 @@ def torch_route(state, E, P, W, b, dy, dtype=None, fn=None):
     return dict(y=y.detach().numpy(), **{k: v.grad.numpy() for k, v in zip(("dE", "dP", "dW", "db"), t)})
 
 
-def dev(got, ref):
-    """Largest absolute difference over the reference's largest magnitude."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    scale = np.abs(ref).max()
-    return float(np.abs(got - ref).max() / scale) if scale > 0 else float(np.abs(got).max())
-
-
 def deviations(got, ref, quantities=QUANTITIES):
-    return {q: dev(got[q], ref[q]) for q in quantities}
-
-
-def bound(own):
-    """What a kernel may deviate from float64, given what float32 torch deviates on the same inputs."""
-    return max(FACTOR * own, FLOOR)
+    return plain_deviations(got, ref, quantities)
 
 
 @functools.lru_cache(maxsize=None)

@@ -30,6 +30,9 @@
 //
 // k_stem_conv_block is the first residual block with the folded stem (nn_stem.hip) computed in front of
 // it: no x is read at all, each wavefront builds the raw tile of its sample from the leaf's position.
+//
+// k_conv_chain is that kernel and the residual blocks behind it in ONE launch: the body once per layer, the activations
+// through HBM / L2 between layers exactly as between the separate launches, no grid-wide barrier (layer_switch below).
 #include <cstdio>
 #include <cstdlib>
 
@@ -138,7 +141,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_block(const uint16_t *x, const 
                                                        const uint16_t *gamma, const uint16_t *beta, uint16_t *y,
                                                        int64_t B, float eps, int dbg, const int64_t *batch_dev, EmbedIn em)
 {
-    constexpr bool STEM = false;
+    constexpr bool STEM = false, CHAINED = false;
     const StemIn st{};
 #include "nn_conv_body.h"
 }
@@ -149,10 +152,64 @@ __global__ void __launch_bounds__(256, 2) k_stem_conv_block(StemIn st, const uin
                                                             int64_t B, float eps, int dbg, const int64_t *batch_dev)
 {
     constexpr int CIN = 64;
-    constexpr bool NORM = true, RESID = true, EMBED = false, STEM = true;
+    constexpr bool NORM = true, RESID = true, EMBED = false, STEM = true, CHAINED = false;
     const uint16_t *x = nullptr;
     const EmbedIn em{};
 #include "nn_conv_body.h"
+}
+
+// k_conv_chain: the folded stem with the first residual block and the residual blocks behind it, layer after layer in
+// ONE launch.  Per-layer arguments, by value: layer L reads y[L - 1] (layer 0: the positions) and writes y[L].
+struct ChainIn {
+    const uint16_t *w[AZ_NN_MAX_BLOCKS], *bias[AZ_NN_MAX_BLOCKS], *gamma[AZ_NN_MAX_BLOCKS], *beta[AZ_NN_MAX_BLOCKS];
+    uint16_t *y[AZ_NN_MAX_BLOCKS];
+    int n;
+};
+
+// Between two layers of k_conv_chain.  The launches this kernel replaces use the same grid, the same tile order (tile =
+// blockIdx.x + k * gridDim.x) and the same wave-to-sample rule (wave s stages and stores sample tile * 4 + s), so the only
+// reader of what a wave stored in layer L is that same wave in layer L + 1: no workgroup waits for another one.  The wave
+// waits for its own stores - the L1 is write-through: they are then in the L2 of this CU's XCD, the one its loads are
+// served from - and an agent-scope ACQUIRE drops the lines its CU's L1 may still hold of the buffer it reads next (layer
+// L + 1 writes the buffer layer L read - the two scratch tensors ping-pong - so a line cached two layers ago would be
+// stale).  No release: nothing outside this CU reads the activations before the kernel ends, and the write-back of the
+// whole L2 that an agent-scope release (__threadfence()) performs made the kernel 97 us slower than the launches it
+// replaces (EXPERIMENTS.md E21).  The barrier keeps the next prologue's LDS zeroing behind every wave's last reads of
+// the output tile.
+__device__ __forceinline__ void layer_switch()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    __syncthreads();
+}
+
+// The body once with the stem in front (layer 0) and once more, in a loop that is not unrolled, for the layers behind
+// it: the same text as the kernels above, so every layer computes the bytes its own launch would have.  The first
+// inclusion clamps B from batch_dev; the others find it clamped (their batch_dev is null) and restart at raw buffer 0
+// (par is the body's own).  Dynamic LDS: the larger of the two layouts.
+__global__ void __launch_bounds__(256, 2) k_conv_chain(StemIn st_in, ChainIn ch, int64_t B, float eps, int dbg, const int64_t *batch_dev_in)
+{
+    constexpr int CIN = 64;
+    constexpr bool NORM = true, RESID = true, EMBED = false;
+    const EmbedIn em{};
+    {
+        constexpr bool STEM = true, CHAINED = false;
+        const StemIn &st = st_in;
+        const uint16_t *x = nullptr, *w = ch.w[0], *bias = ch.bias[0], *gamma = ch.gamma[0], *beta = ch.beta[0];
+        uint16_t *y = ch.y[0];
+        const int64_t *batch_dev = batch_dev_in;
+#include "nn_conv_body.h"
+    }
+#pragma unroll 1
+    for (int layer = 1; layer < ch.n; ++layer) {
+        layer_switch();
+        constexpr bool STEM = false, CHAINED = true;
+        const StemIn st{};
+        const uint16_t *x = ch.y[layer - 1], *w = ch.w[layer], *bias = ch.bias[layer], *gamma = ch.gamma[layer], *beta = ch.beta[layer];
+        uint16_t *y = ch.y[layer];
+        const int64_t *batch_dev = nullptr;
+#include "nn_conv_body.h"
+    }
 }
 
 // az_nn_debug: timing experiments (1 skips the MFMA loop, 2 skips the store, ...: bits 0-7 go to the kernels of this file)
@@ -160,7 +217,7 @@ __global__ void __launch_bounds__(256, 2) k_stem_conv_block(StemIn st, const uin
 int g_dbg = 0;
 
 // What a launch of either kernel does once its pointer and its dynamic LDS bytes are known: the once-per-device set-up
-// (with AZ_NN_VERBOSE: the occupancy line; c_in 0 words it for k_stem_conv_block), then the grid - one workgroup per
+// (with AZ_NN_VERBOSE: the occupancy line; c_in 0 words it for k_stem_conv_block, c_in < 0 for k_conv_chain), then the grid - one workgroup per
 // tile of TS samples, at most AZ_NN_CONV_GRID - and the kernel's dbg word.  `setup` is the caller's: one static
 // DeviceSetup per kernel instantiation (nn_common.h).  The environment is read once per process.  Returns 0, or 2 when
 // the device refused the set-up.
@@ -170,7 +227,9 @@ int prepare(DeviceSetup &setup, const void *kern, size_t smem, int c_in, int64_t
             if (getenv("AZ_NN_VERBOSE") != nullptr) {
                 int per_cu = 0;
                 (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, smem);
-                if (c_in != 0)
+                if (c_in < 0)
+                    fprintf(stderr, "[az_nn] stem + conv chain: %zu B LDS, %d workgroups per CU\n", smem, per_cu);
+                else if (c_in != 0)
                     fprintf(stderr, "[az_nn] conv block C_in=%d: %zu B LDS, %d workgroups per CU\n", c_in, smem, per_cu);
                 else
                     fprintf(stderr, "[az_nn] stem + conv block: %zu B LDS, %d workgroups per CU\n", smem, per_cu);
@@ -221,6 +280,24 @@ int launch_stem(const StemIn &st, const void *w, const void *bias, const void *g
     return 0;
 }
 
+int launch_chain(const StemIn &st, const ChainIn &ch, int64_t B, float eps, const int64_t *batch_dev, hipStream_t s)
+{
+    // the larger of the two layouts: the blocks' (images, TWO raw tiles, gamma / beta + the dummy slots) and the stem
+    // block's (launch_stem)
+    constexpr size_t smem_block = static_cast<size_t>(TS) * PCELLS * CELLB + 2 * static_cast<size_t>(TS) * CELLS * 64 * 2 +
+                                  2 * 64 * sizeof(float) + 512;
+    constexpr size_t smem_stem = static_cast<size_t>(TS) * PCELLS * CELLB + static_cast<size_t>(TS) * CELLS * 64 * 2 +
+                                 2 * 64 * sizeof(float) + 512 + PMAPB + FRAGB;
+    constexpr size_t smem = smem_block > smem_stem ? smem_block : smem_stem;
+    static_assert(smem == 80896 && 2 * smem <= 160 * 1024, "two workgroups per CU");
+    static DeviceSetup setup;
+    unsigned grid;
+    int dbg;
+    if (prepare(setup, reinterpret_cast<const void *>(k_conv_chain), smem, -1, B, grid, dbg) != 0) return 2;
+    hipLaunchKernelGGL(k_conv_chain, dim3(grid), dim3(256), smem, s, st, ch, B, eps, dbg, batch_dev);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,6 +335,30 @@ int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void
     const StemIn st{positions->bb_p1, positions->bb_p2, positions->turn, positions->sym, gather,
                     static_cast<const uint16_t *>(w_frag), pmap};
     return launch_stem(st, weight_ohwi, bias, gamma, beta, y, batch, eps, batch_dev, static_cast<hipStream_t>(stream));
+}
+
+int az_nn_stem_conv_chain_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap, int n_blocks,
+                                    const void *const *weight_ohwi, const void *const *bias, const void *const *gamma,
+                                    const void *const *beta, void *y_even, void *y_odd, int64_t batch, float eps,
+                                    const int32_t *gather, const int64_t *batch_dev, void *stream)
+{
+    if (batch <= 0 || positions == nullptr || !positions->bb_p1 || !positions->bb_p2 || !positions->turn || !positions->sym ||
+        w_frag == nullptr || pmap == nullptr || n_blocks < 1 || n_blocks > AZ_NN_MAX_BLOCKS || weight_ohwi == nullptr ||
+        bias == nullptr || gamma == nullptr || beta == nullptr || y_even == nullptr || y_odd == nullptr || y_even == y_odd)
+        return 1;
+    ChainIn ch{};
+    for (int i = 0; i < n_blocks; ++i) {
+        if (!weight_ohwi[i] || !bias[i] || !gamma[i] || !beta[i]) return 1;
+        ch.w[i] = static_cast<const uint16_t *>(weight_ohwi[i]);
+        ch.bias[i] = static_cast<const uint16_t *>(bias[i]);
+        ch.gamma[i] = static_cast<const uint16_t *>(gamma[i]);
+        ch.beta[i] = static_cast<const uint16_t *>(beta[i]);
+        ch.y[i] = static_cast<uint16_t *>((i & 1) ? y_odd : y_even);
+    }
+    ch.n = n_blocks;
+    const StemIn st{positions->bb_p1, positions->bb_p2, positions->turn, positions->sym, gather,
+                    static_cast<const uint16_t *>(w_frag), pmap};
+    return launch_chain(st, ch, batch, eps, batch_dev, static_cast<hipStream_t>(stream));
 }
 
 int az_nn_stem_embed(const float *features, const void *emb_own, const void *emb_opp, const void *pos,

@@ -1,5 +1,5 @@
 // nn_conv_body.h - the text of the kernels of nn_conv.hip, included as the body of each of them (not a header in the
-// usual sense: no declarations of its own).  The including kernel provides CIN, NORM, RESID, EMBED, STEM as constant
+// usual sense: no declarations of its own).  The including kernel provides CIN, NORM, RESID, EMBED, STEM, CHAINED as constant
 // expressions and x, w, bias, gamma, beta, y, B, eps, dbg, batch_dev, em (EmbedIn), st (StemIn) as variables.
 //
 // STEM (C_in 64, normalised, residual only): the raw tile is not staged from HBM; wave s computes the folded stem of
@@ -36,7 +36,11 @@
     uint8_t *dump = reinterpret_cast<uint8_t *>(s_gam + 2 * CIN);         // 4 x 8 x 16 B: results of dummy tokens
     uint8_t *s_pm = dump + 512, *s_fr = s_pm + PMAPB;                     // STEM: pmap and the table fragments
 
-    const int tid = threadIdx.x;
+    // CHAINED (an inclusion behind another one in the same kernel): the thread id as an opaque copy, so that nothing
+    // this inclusion derives from it is one value with the earlier inclusion's and kept in registers across that one's
+    // tile loop, where the resident weights leave no room for it
+    int tid = threadIdx.x;
+    if (CHAINED) asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mh = wave & 1, th = wave >> 1;

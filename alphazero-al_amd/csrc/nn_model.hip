@@ -21,6 +21,7 @@ struct az_nn_model {
     int kind = AZ_NN_KIND_CONNECT4_CNN;
     bool attn_heads_fused = true;        // az_nn_attn_heads in place of az_nn_attn_block + az_nn_heads
     bool stem_fused = true;              // az_nn_stem_conv_block_positions in place of the folded stem + the first residual block
+    bool conv_chain = true;              // az_nn_stem_conv_chain_positions in place of that launch + one per further block
     uint64_t hash_salt = 0;              // AZ_NN_KIND_HASH_*: az_nn_model_create_hash_salted
     az_nn_model_weights w{};
     az_nn_othello_weights ow{};
@@ -259,7 +260,15 @@ int forward_connect4(const az_nn_model *m, const float *features, const az_nn_po
     int first = 0;                                        // the first residual block still to run
     // the folded stem from positions and the first residual block as one launch (a call that carries event pairs
     // runs the two, so that the STEM and CONV rings keep timing the kernels they are named after)
-    if (m->stem_fused && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr && w.n_blocks >= 1) {
+    if (m->stem_fused && m->conv_chain && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr &&
+        w.n_blocks >= 2) {
+        // ... and every residual block behind it in the same launch: block i writes a (i even) or b (i odd), as the loop
+        // below would have, and the result is left where that loop would have left it
+        rc = az_nn_stem_conv_chain_positions(positions, w.stem_frag, w.stem_pmap, w.n_blocks, w.block_w, w.block_b, w.block_gamma,
+                                             w.block_beta, a, b, batch, w.eps, rows, n_rows, stream);
+        first = w.n_blocks;
+        if ((w.n_blocks & 1) == 0) { char *t = a; a = b; b = t; }
+    } else if (m->stem_fused && !timed && positions != nullptr && w.stem_frag != nullptr && w.stem_pmap != nullptr && w.n_blocks >= 1) {
         rc = az_nn_stem_conv_block_positions(positions, w.stem_frag, w.stem_pmap, w.block_w[0], w.block_b[0], w.block_gamma[0],
                                              w.block_beta[0], a, batch, w.eps, rows, n_rows, stream);
         first = 1;
@@ -339,6 +348,9 @@ int az_nn_model_create(const az_nn_model_weights *w, az_nn_model **out)
     // AZ_STEM_FUSED=0: the folded stem and the first residual block as two launches (likewise)
     const char *stem = getenv("AZ_STEM_FUSED");
     m->stem_fused = stem == nullptr || strcmp(stem, "0") != 0;
+    // AZ_CONV_CHAIN=0: the stem block and the residual blocks behind it as one launch each (likewise)
+    const char *chain = getenv("AZ_CONV_CHAIN");
+    m->conv_chain = chain == nullptr || strcmp(chain, "0") != 0;
     *out = m;
     return 0;
 }

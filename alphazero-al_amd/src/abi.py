@@ -299,6 +299,7 @@ PROTOTYPES = (
     ("az_nn_stem_folded_positions", i32, [P(Positions), vp, vp, vp, i64, vp, vp, vp]),
     ("az_nn_conv_block", i32, [vp, i32, vp, vp, vp, vp, i32, vp, i64, f32, vp, vp]),
     ("az_nn_stem_conv_block_positions", i32, [P(Positions), vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, vp]),
+    ("az_nn_stem_conv_chain_positions", i32, [P(Positions), vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp, vp]),
     ("az_nn_attn_block", i32, [vp, vp, vp, vp, vp, vp, vp, i64, f32, vp, vp]),
     ("az_nn_heads", i32, [vp, P(HeadsWeights), vp, vp, vp, vp, i64, f32, vp, vp, vp]),
     ("az_nn_attn_heads", i32, [vp, vp, vp, vp, vp, vp, P(HeadsWeights), vp, vp, vp, vp, i64, f32, vp, vp, vp]),

@@ -78,6 +78,18 @@ int az_nn_conv_block(const void *x, int c_in, const void *weight_ohwi, const voi
 int az_nn_stem_conv_block_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap,
                                     const void *weight_ohwi, const void *bias, const void *gamma, const void *beta, void *y,
                                     int64_t batch, float eps, const int32_t *gather, const int64_t *batch_dev, void *stream);
+/* az_nn_stem_conv_block_positions followed by az_nn_conv_block(c_in 64, gamma, beta, residual 1) for blocks 1 ..
+ * n_blocks - 1 as ONE kernel (nn_conv.hip, k_conv_chain): the layers run back to back inside the launch, each with the
+ * grid, the tile order and the wave-to-sample rule its own launch has, so a wavefront reads in layer L + 1 only what it
+ * stored itself in layer L and no workgroup waits for another.  weight_ohwi .. beta: arrays of n_blocks (1 ..
+ * AZ_NN_MAX_BLOCKS) pointers, one per block.  Block i writes y_even (i even) or y_odd (i odd), two distinct (batch, 42,
+ * 64) tensors - the buffers the separate launches ping-pong between - so the result is in y_even when n_blocks is odd
+ * and in y_odd when it is even; rows from batch_dev on are not written in either.  Every layer is the text of its own
+ * kernel: the bytes are those of the separate launches. */
+int az_nn_stem_conv_chain_positions(const az_nn_positions *positions, const void *w_frag, const float *pmap, int n_blocks,
+                                    const void *const *weight_ohwi, const void *const *bias, const void *const *gamma,
+                                    const void *const *beta, void *y_even, void *y_odd, int64_t batch, float eps,
+                                    const int32_t *gather, const int64_t *batch_dev, void *stream);
 /* The whole gated attention block as a single MFMA kernel (nn_attn.hip):
  *   y = x + o_proj(sigmoid(gate) * softmax(qnorm(Q) knorm(K)^T / 4) V),  [Q|K|V|gate] = qkvg(RMSNorm(x))
  * (Network.py:51-93).  x, y (batch, 42, 64); qkvg_w (196, 64) row-major [out][in] with rows
@@ -124,6 +136,8 @@ int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, c
  *       stem (stem_frag / stem_pmap) and n_blocks >= 1 and the call is given POSITIONS (AZ_STEM_FUSED=0 in the
  *       environment when the object is created: two launches; same bits either way).  Else a stem form of its own:
  *       az_nn_stem_folded[_positions] with the folded stem, az_nn_stem_embed[_positions] without;
+ *       with n_blocks >= 2 that launch is az_nn_stem_conv_chain_positions, which runs every residual block behind the
+ *       first one too (AZ_CONV_CHAIN=0 in the environment when the object is created: one launch per block; same bits);
  *   the blocks  az_nn_conv_block (64 -> 64, normalised, residual) for each of the n_blocks not yet run;
  *   attention and heads  az_nn_attn_heads (AZ_ATTN_HEADS_FUSED=0 in the environment when the object is created:
  *       az_nn_attn_block, then az_nn_heads).

@@ -5,7 +5,8 @@
 // counter that moves per use, an index (tree, leaf, game) and a small constant per purpose - streams
 // in use: b = 3 playouts, 7 symmetry ids, 16.. and 128.. root noise, SP_STREAM the driver's moves,
 // REPLAY_STREAM the replay sampler's ring indices (replay_kernels.hip), MATCH_STREAM the evaluation-match
-// driver's moves (match_kernels.hip).
+// driver's moves (match_kernels.hip), LEARN_STREAM + t (t = 0 .. 10) the learner's dropout draws of tensor t
+// (learn_driver.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,5 +57,6 @@ struct DevRng {
 constexpr uint64_t SP_STREAM = 0x5350;       // the self-play driver's move draws
 constexpr uint64_t REPLAY_STREAM = 0x5242;   // ring indices of a training sample (k_replay_indices)
 constexpr uint64_t MATCH_STREAM = 0x4D54;    // the evaluation-match driver's move draws (k_match_ply)
+constexpr uint64_t LEARN_STREAM = 0x4C52;    // + tensor id: the learner's dropout draws (k_learn_keep), 0x4C52 .. 0x4C5C
 
 }  // namespace az

@@ -334,6 +334,17 @@ PROTOTYPES = (
     ("az_opt_destroy", None, [vp]),
     ("az_opt_bind", i32, [vp, vp, vp, vp]),
     ("az_opt_dev_step", i32, [vp, vp, vp, vp, f32, vp, vp]),
+    # az_learn_config and az_learn_out travel as plain c_void_p too; their mirrors live in src/learner.py under its own
+    # table and tests/test_learner_cpu.py holds their layouts to the header
+    ("az_learn_create", i32, [vp, P(vp)]),
+    ("az_learn_destroy", None, [vp]),
+    ("az_learn_bind", i32, [vp, i64, vp, vp, i32, vp, vp, vp, vp]),
+    ("az_learn_dev_step", i32, [vp, P(ReplayBatchC), i64, P(TrainLossConfigC), vp, vp, u64, vp]),
+    ("az_learn_dev_epoch", i32, [vp, P(ReplayTensorsC), vp, vp, i64, i64, i32, P(TrainLossConfigC), vp, vp, u64, P(i64), vp]),
+    ("az_learn_dev_eval", i32, [vp, P(ReplayBatchC), i64, P(TrainLossConfigC), vp]),
+    ("az_learn_dev_keep", i32, [vp, i64, u64, vp]),
+    ("az_learn_outputs", i32, [vp, vp]),
+    ("az_learn_reset_sums", i32, [vp, vp]),
     ("az_train_block_workspace_bytes", i64, [i64, i32]),
     ("az_train_dev_block_fwd", i32, [vp, vp, vp, i64, f32, vp, vp, vp]),
     ("az_train_dev_block_bwd", i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),

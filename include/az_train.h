@@ -3,8 +3,9 @@
  * (az_opt_*, alphazero-al_amd/csrc/optim_kernels.hip), the Connect4 residual block's training forward and
  * backward (az_train_*block*, alphazero-al_amd/csrc/train_block_kernels.hip), the Connect4 gated attention
  * block's (az_train_*attn*, alphazero-al_amd/csrc/train_attn_kernels.hip), the Connect4 stem's
- * (az_train_*stem*, alphazero-al_amd/csrc/train_stem_kernels.hip), and last the Connect4 heads'
- * (az_train_*heads*, alphazero-al_amd/csrc/train_heads_kernels.hip).
+ * (az_train_*stem*, alphazero-al_amd/csrc/train_stem_kernels.hip), the Connect4 heads'
+ * (az_train_*heads*, alphazero-al_amd/csrc/train_heads_kernels.hip); and, declared between the optimiser and the blocks, the
+ * native learner, which drives all of them for a whole batch or epoch (az_learn_*, alphazero-al_amd/csrc/learn_driver.hip).
  *
  * The reference's training step turns a batch and the network's three head outputs into up to five loss terms
  * (src/environments/NetworkBase.py:30-192: `_prepare_training_batch`, `_policy_loss`, `_value_loss`,
@@ -155,6 +156,136 @@ int  az_opt_bind(az_opt *o, void *const *param, void *const *exp_avg, void *cons
  * gradient; max_norm > 0 with a null or misaligned grad_norm; a max_norm that is not a number. */
 int  az_opt_dev_step(az_opt *o, const void *const *grad, const int64_t *step, const double *group_hp,
                      float max_norm, float *grad_norm, void *stream);
+
+/* ---- The native learner: a Connect4 training batch, or a whole epoch of them, as ONE call (alphazero-al_amd/csrc/learn_driver.hip).
+ * What the Python route does through four autograd nodes, the loss node and ClipAdamW - stem, residual blocks, attention
+ * block, heads, losses, their gradients, the backward chain, clipping and the AdamW step - az_learn_dev_step enqueues from
+ * C in the same order, with the same arguments, on the same bytes: a network trained through either route holds the same
+ * parameters and moments.  (Declared ahead of the units it drives: tests/test_train_heads_cpu.py holds the heads' three
+ * functions to the end of this header.)  The handle owns every buffer a batch needs besides the network's own tensors; after
+ * az_learn_create nothing is allocated.  Connect4 only.
+ *
+ * DROPOUT.  With a rate above 0 every dropout input of a batch is written by one launch, k_learn_keep, under this
+ * contract (tests/learner_ref.py restates it in numpy):
+ *   thr      = (uint32) floor(p * 2^32 + 0.5), formed in double on the host; a value of 2^32 counts as 2^32 - 1
+ *   kept     iff the element's 32-bit draw is >= thr
+ *   factor   1.0f / (1.0f - (float) p) for a kept element (rounded once, on the host; the attention block's keep_scale is
+ *            the same expression), 0 for a dropped one
+ *   draws    element or bit j of group a of tensor t is draw number j of the device generator's stream
+ *            (seed, call, a, LEARN_STREAM + t) (csrc/dev_rng.h): with s0 the stream's state,
+ *            mix64(s0 + (j + 1) * 0x9E3779B97F4A7C15) >> 32
+ *   t, a     block k's factors [N][64]: t = k, a = n;   the attention block's bits [N][4][42]: t = AZ_LEARN_KEEP_ATTN,
+ *            a = (4 n + h) * 42 + i, bit j of that word, bits 42 .. 63 zero;   the policy head's factors [N][7][64]:
+ *            t = AZ_LEARN_KEEP_POLICY, a = 7 n + c;   the value head's pool factors [N][64]: t = AZ_LEARN_KEEP_POOL, a = n
+ * A tensor whose rate is 0 is never written and its piece gets a null keep.
+ *
+ * The roles name the network's tensors to az_learn_bind.  (Defines, not an enum: apart from structs and assertions this
+ * header holds prototypes only.) */
+#define AZ_LEARN_MAX_BLOCKS 8
+#define AZ_LEARN_ROLE_PIECE_EMB 0           /* [2][32] */
+#define AZ_LEARN_ROLE_POS_EMB 1             /* [24][32] */
+#define AZ_LEARN_ROLE_STEM_CONV_WEIGHT 2    /* [64][32][3][3] */
+#define AZ_LEARN_ROLE_STEM_CONV_BIAS 3      /* [64] */
+#define AZ_LEARN_ROLE_BLOCK 4               /* + 4 k + (0 norm_weight, 1 norm_bias, 2 conv_weight, 3 conv_bias), k < n_blocks */
+#define AZ_LEARN_ROLE_ATTN 36               /* + the index of the field in az_train_attn_params (6) */
+#define AZ_LEARN_ROLE_HEADS 42              /* + the index of the field in az_train_heads_params (18) */
+#define AZ_LEARN_ROLES 60
+#define AZ_LEARN_KEEP_ATTN 8                /* tensor ids of the dropout streams; block k is k */
+#define AZ_LEARN_KEEP_POLICY 9
+#define AZ_LEARN_KEEP_POOL 10
+typedef struct az_learn az_learn;           /* opaque */
+
+typedef struct az_learn_config {
+    int64_t  max_rows;          /* the largest S * B of a batch, 1 .. 2^20 */
+    int32_t  n_blocks;          /* residual blocks, 1 .. AZ_LEARN_MAX_BLOCKS */
+    int32_t  max_workgroups;    /* the cap of every backward; 0: each unit's default */
+    float    eps_block;         /* the blocks' GroupNorm */
+    float    eps_attn;          /* the attention block's three norms */
+    float    eps_heads;         /* the heads' four norms */
+    float    max_norm;          /* gradient-norm clipping as az_opt_dev_step takes it */
+    double   p_block;           /* the four dropout rates, each in [0, 1) */
+    double   p_attn;
+    double   p_policy;
+    double   p_pool;
+    uint64_t seed;              /* of the dropout draws */
+} az_learn_config;
+#define AZ_LEARN_CONFIG_BYTES 72
+
+/* DEVICE addresses inside the handle, valid until az_learn_destroy. */
+typedef struct az_learn_out {
+    float    *sums;             /* [3] running sums of the policy, value and aux loss over the batches since the last reset */
+    int32_t  *batches;          /* [1] how many */
+    float    *entropy;          /* [1] the policy entropy of the last training batch (az_learn_dev_eval leaves it alone) */
+    float    *losses;           /* [4] the last loss pass, as az_train_loss_out */
+    int32_t  *counts;           /* [11] the last loss pass, as az_train_loss_out */
+    float    *grad_norm;        /* [1] the last training batch's total gradient norm (max_norm > 0) */
+    float    *keep_blocks;      /* block k's factors [N][64] start at keep_blocks + k * keep_block_stride */
+    int64_t   keep_block_stride;    /* in floats: 64 * max_rows */
+    uint64_t *keep_attn;        /* [N][4][42] */
+    float    *keep_policy;      /* [N][7][64] */
+    float    *keep_pool;        /* [N][64] */
+    az_replay_batch batch;      /* the handle's own batch tensors, max_rows rows each: what az_learn_dev_epoch's last batch left */
+} az_learn_out;
+#define AZ_LEARN_OUT_BYTES 152
+#ifdef __cplusplus
+static_assert(sizeof(az_learn_config) == AZ_LEARN_CONFIG_BYTES && sizeof(az_learn_out) == AZ_LEARN_OUT_BYTES, "az_learn structs");
+#else
+_Static_assert(sizeof(az_learn_config) == AZ_LEARN_CONFIG_BYTES && sizeof(az_learn_out) == AZ_LEARN_OUT_BYTES, "az_learn structs");
+#endif
+
+/* Allocates, on the current device and once, everything a batch of up to max_rows rows needs: the activations (the stem's
+ * output, every block's y, z and stats, the tokens, the three head outputs), the gradients of the chain, the keep
+ * tensors, ONE workspace that serves the loss pass and the four backwards in turn, the stem's table apart from it, the
+ * loss outputs, the upstream (1, 1, 1), the running sums, and batch tensors of its own for az_learn_dev_epoch.  Waits for
+ * the device.  AZ_ERR_ARG, with *out null: a null argument; max_rows outside [1, 2^20]; n_blocks outside
+ * [1, AZ_LEARN_MAX_BLOCKS]; an eps that is not positive and finite; a rate outside [0, 1), or so close to 1 that its float32 value is 1 (its
+ * factor would not be finite); a negative max_workgroups; a
+ * max_norm that is not a number. */
+int  az_learn_create(const az_learn_config *config, az_learn **out);
+void az_learn_destroy(az_learn *l);
+/* The network's tensors in the OPTIMISER'S flat order (k_opt_sqsum adds the per-tensor partials in tensor order: only
+ * that order gives the norm ClipAdamW gives).  role[i]: which tensor of the network tensor i is, every role of the
+ * n_blocks-block network exactly once (n_tensors = 28 + 4 n_blocks); group[i]: its parameter group, as az_opt_create
+ * takes it.  param, grad, exp_avg, exp_avg_sq: HOST arrays of DEVICE addresses; every backward writes its gradient
+ * straight into grad[i].  Alignment as the five units ask: 16 bytes for param and grad of the blocks' conv_weight, the
+ * attention block's qkv_weight and o_weight and the heads' three 64 x 64 weights, 4 bytes for everything else.  The handle
+ * builds an az_opt of its own over them.  May wait for the device.  AZ_ERR_ARG, with nothing changed: a null argument; a
+ * count that is not 28 + 4 n_blocks; a role out of range, missing or repeated; a null or misaligned address; what
+ * az_opt_create refuses. */
+int  az_learn_bind(az_learn *l, int64_t n_tensors, const int32_t *role, const int32_t *group, int32_t n_groups,
+                   void *const *param, void *const *grad, void *const *exp_avg, void *const *exp_avg_sq);
+/* One training batch of N rows on `stream`; only enqueues, nothing waits.  In order: k_learn_keep (when a rate is above
+ * 0), az_train_dev_stem_fwd, az_train_dev_block_fwd per block (z and stats saved), az_train_dev_attn_fwd (x_token_major
+ * 0), az_train_dev_heads_fwd (legal = batch->valid_mask), az_train_dev_loss, az_train_dev_loss_grad (upstream 1, 1, 1),
+ * az_train_dev_heads_bwd, az_train_dev_attn_bwd, az_train_dev_block_bwd per block in reverse, az_train_dev_stem_bwd,
+ * az_opt_dev_step (the norm to az_learn_out.grad_norm), k_learn_tail (sums += the three losses, batches += 1, the entropy
+ * copied).  `batch` as az_replay_dev_batch writes it; `config` with aux_target_offset 42 for the reference's network;
+ * step[i] and group_hp as az_opt_dev_step takes them (HOST arrays; every step >= 1); `call` numbers the batch for the
+ * dropout draws.  A handle's steps belong on one stream at a time.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: a null argument; a step before az_learn_bind; N outside
+ * [1, max_rows]; a null batch tensor or one that is not 16-byte aligned (valid_mask: any alignment); what
+ * az_train_dev_loss refuses of `config` and az_opt_dev_step of step and group_hp. */
+int  az_learn_dev_step(az_learn *l, const az_replay_batch *batch, int64_t N, const az_train_loss_config *config,
+                       const int64_t *step, const double *group_hp, uint64_t call, void *stream);
+/* One epoch over a sample of a replay ring: batch k = az_replay_dev_batch(Connect4, ring, idx, order, k B, min(B, n - k B))
+ * into the handle's own batch tensors, then az_learn_dev_step on its 2 B rows with step[i] + k and call first_call + k; no
+ * other host work between batches.  The last batch is short unless drop_last.  *n_batches: how many were enqueued.
+ * AZ_ERR_ARG, with nothing enqueued: as az_learn_dev_step and az_replay_dev_batch, n <= 0, B <= 0, 2 B > max_rows, a
+ * null n_batches, a sample that gives no batch. */
+int  az_learn_dev_epoch(az_learn *l, const az_replay_tensors *ring, const int64_t *idx, const int64_t *order, int64_t n,
+                        int64_t B, int drop_last, const az_train_loss_config *config, const int64_t *step,
+                        const double *group_hp, uint64_t first_call, int64_t *n_batches, void *stream);
+/* The forward without keeps, nothing saved, and az_train_dev_loss on it: az_learn_out.losses and .counts hold the batch's
+ * losses and confusion afterwards; sums, batches, entropy, grad_norm and every network tensor stay as they are.
+ * AZ_ERR_ARG as az_learn_dev_step. */
+int  az_learn_dev_eval(az_learn *l, const az_replay_batch *batch, int64_t N, const az_train_loss_config *config, void *stream);
+/* k_learn_keep alone, as az_learn_dev_step launches it for a batch of N rows numbered `call` - for tests and tools; with
+ * every rate 0 nothing is enqueued.  AZ_ERR_ARG: a null handle, N outside [1, max_rows]. */
+int  az_learn_dev_keep(az_learn *l, int64_t N, uint64_t call, void *stream);
+/* The addresses of what the handle keeps for its caller.  AZ_ERR_ARG: a null argument. */
+int  az_learn_outputs(az_learn *l, az_learn_out *out);
+/* sums, batches and entropy to zero, on `stream`. */
+int  az_learn_reset_sums(az_learn *l, void *stream);
 
 /* ---- The Connect4 residual block's training forward and backward (alphazero-al_amd/csrc/train_block_kernels.hip):
  * y = x + keep * silu(conv3x3(GroupNorm(1, 64)(x))), the reference's `ResidualBlock(64, 64)` with its Dropout2d factor

@@ -160,6 +160,31 @@ int az_game_dev_valid_mask(int game, const uint64_t *bb_p1, const uint64_t *bb_p
     });
 }
 
+int az_game_dev_pick(int game, const int32_t *counts, const float *q, const int32_t *ply, const uint8_t *dead,
+                     int32_t *actions, int64_t n, int temp_decay_moves, int hot_early, int hot_late, void *stream)
+{
+    return guarded([&] {
+        require(known_game(game), "az_game_dev_pick: unknown game");
+        require(n >= 0 && n <= INT32_MAX, "az_game_dev_pick: size out of range");
+        require(counts && q && ply && actions, "az_game_dev_pick: null array");
+        if (n == 0) return;
+        az::launch_ply_pick(game, counts, q, ply, dead, actions, static_cast<int>(n), temp_decay_moves, hot_early != 0,
+                            hot_late != 0, static_cast<hipStream_t>(stream));
+    });
+}
+
+int az_mcts_dev_ply_advance(az_mcts *m, uint64_t *bb_p1, uint64_t *bb_p2, int32_t *turns, int32_t *aux,
+                            const int32_t *actions, uint8_t *done, int32_t *winner, int32_t *ply, uint8_t *dead,
+                            int64_t *totals, int refill, void *stream)
+{
+    return guarded([&] {
+        require(bb_p1 && bb_p2 && turns && aux && actions && done && winner && ply && dead && totals,
+                "az_mcts_dev_ply_advance: null array");
+        az::launch_ply_advance(m->game, m->arena(), bb_p1, bb_p2, turns, aux, actions, done, winner, ply, dead, totals,
+                               refill != 0, static_cast<hipStream_t>(stream));
+    });
+}
+
 int az_mcts_max_used(az_mcts *m, int64_t *out)
 {
     return guarded([&] {

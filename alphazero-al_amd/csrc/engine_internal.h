@@ -468,8 +468,9 @@ struct az_mcts {
         growth_after[q % 8] = 0;
         HIP_OK(hipMemsetAsync(max_live.p, 0, sizeof(int), s));
         // compact the trees that could not take two more plies' worth of growth where they are
-        // (AZ_COMPACT_ALWAYS=1: every tree at every re-rooting)
-        static const bool always = getenv("AZ_COMPACT_ALWAYS") != nullptr && getenv("AZ_COMPACT_ALWAYS")[0] == '1';
+        // (AZ_COMPACT_ALWAYS=1: every tree at every re-rooting; read per call, so a test can turn it on for one engine)
+        const char *const env_always = getenv("AZ_COMPACT_ALWAYS");
+        const bool always = env_always != nullptr && env_always[0] == '1';
         // (one ply = what was reserved since the previous re-rooting; the host entry points reserve per backprop
         // call, so the last call's figure alone would let a tree run into the end of its half mid-search)
         const int64_t ply = std::max<int64_t>(std::max(growth_since_prune, last_extra), geo.max_edges);

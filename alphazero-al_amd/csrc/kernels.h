@@ -140,6 +140,14 @@ void launch_rollout_search(int game, TreeArena ar, RootState rs, LeafBuf lf, Sea
                            unsigned long long *counters, int *err, hipStream_t s);
 void launch_game_step(int game, uint64_t *bb0, uint64_t *bb1, int32_t *turns, int32_t *aux, const int32_t *actions,
                       uint8_t *done, int32_t *winner, int64_t n, bool reset_finished, hipStream_t s);
+// The device driver's ply tail (az_mcts_dev_ply_pick / az_mcts_dev_ply_advance, include/az_mcts.h): counts -> move at
+// temperature 1 from the caller's exponential draws q [n, A]; and step + result + refill or death + tree reset + ply
+// counters + totals behind the re-rooting, for the ar.B games of the engine's trees.
+void launch_ply_pick(int game, const int32_t *counts, const float *q, const int32_t *ply, const uint8_t *dead,
+                     int32_t *actions, int n, int decay_moves, bool hot_early, bool hot_late, hipStream_t s);
+void launch_ply_advance(int game, TreeArena ar, uint64_t *bb0, uint64_t *bb1, int32_t *turns, int32_t *aux,
+                        const int32_t *actions, uint8_t *done, int32_t *winner, int32_t *ply, uint8_t *dead,
+                        int64_t *totals, bool refill, hipStream_t s);
 void launch_game_valid_mask(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, const int32_t *aux,
                             uint8_t *mask, int64_t n, hipStream_t s);
 

@@ -1,6 +1,7 @@
 // kernels.hip - gfx950 kernels of the batched PUCT search, instantiated per game (games.h).  Three units over
 // tree_dev.h: select_kernels.hip (selection), backup_kernels.hip (virtual-loss removal, expansion + backup) and this
-// one (import, leaf export, tree maintenance, root queries, rollout, game step).  What follows holds for all three.
+// one (import, leaf export, tree maintenance, root queries, rollout, game step, the device driver's ply tail).  What
+// follows holds for all three.
 //
 // Work decomposition: ONE TREE PER LANE GROUP of G::LANES lanes (Connect4: 8 lanes, 8 trees
 // per 64-wide wavefront; Othello: 64 lanes, one tree per wavefront), one wavefront per
@@ -189,6 +190,38 @@ __device__ __forceinline__ unsigned long long group_ballot(bool pred, int lane)
     return (bal >> (lane - lane % L)) & mask;
 }
 
+// One node's child block (nE records at `src` of the old half) to `dst` of the new half, parent = q: CH records
+// are loaded before the first of them is stored, so a lane waits for one memory round trip per CH records, not
+// one per record (Connect4: CH = ACTIONS, a whole block; Othello: chunks of 8, which bounds the registers).
+template <int CH>
+__device__ __forceinline__ void copy_child_block(const HotRec *__restrict__ hot, const ColdRec *__restrict__ cold,
+                                                 HotRec *__restrict__ nhot, ColdRec *__restrict__ ncold, int src, int dst,
+                                                 int nE, int q)
+{
+    typedef uint4 __attribute__((may_alias)) rec4;                     // a record's dwordx4 halves, whatever their fields
+    static_assert(sizeof(HotRec) == 2 * sizeof(rec4) && sizeof(ColdRec) == sizeof(rec4) && offsetof(ColdRec, parent) == 8,
+                  "records as dwordx4, parent in .z");
+    for (int j0 = 0; j0 < nE; j0 += CH) {
+        const rec4 *hs = reinterpret_cast<const rec4 *>(hot + src + j0);
+        const rec4 *cs = reinterpret_cast<const rec4 *>(cold + src + j0);
+        rec4 *hd = reinterpret_cast<rec4 *>(nhot + dst + j0);
+        rec4 *cd = reinterpret_cast<rec4 *>(ncold + dst + j0);
+        const int m = nE - j0;                                         // records of this chunk: k < m
+        uint4 ha[CH], hb[CH], cb[CH];
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            ha[k] = hb[k] = cb[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (k < m) { ha[k] = hs[2 * k]; hb[k] = hs[2 * k + 1]; cb[k] = cs[k]; }
+        }
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+            if (k < m) {
+                cb[k].z = static_cast<unsigned>(q);                    // ColdRec::parent
+                hd[2 * k] = ha[k]; hd[2 * k + 1] = hb[k]; cd[k] = cb[k];
+            }
+    }
+}
+
 // MCTS.h:90-132: re-root at the child reached by `action` if the reference would have allocated it,
 // else reset.  The reference keeps the whole old tree in its pools until the next reset
 // (MCTS.h:100-101: only `root_idx` moves); here the KEPT SUBTREE IS COPIED into the tree's other
@@ -210,10 +243,11 @@ __global__ void __launch_bounds__(WAVE) k_prune(TreeArena ar, SearchParams p, co
     const int t = blockIdx.x;
     const int S = static_cast<int>(ar.S);
     const int h = ar.half[t];
-    HotRec *hot = ar.hot + (static_cast<size_t>(t) * 2 + h) * ar.S;
-    ColdRec *cold = ar.cold + (static_cast<size_t>(t) * 2 + h) * ar.S;
-    HotRec *nhot = ar.hot + (static_cast<size_t>(t) * 2 + (1 - h)) * ar.S;
-    ColdRec *ncold = ar.cold + (static_cast<size_t>(t) * 2 + (1 - h)) * ar.S;
+    // the two halves of a tree never overlap, nor do the hot and the cold arena
+    HotRec *__restrict__ hot = ar.hot + (static_cast<size_t>(t) * 2 + h) * ar.S;
+    ColdRec *__restrict__ cold = ar.cold + (static_cast<size_t>(t) * 2 + h) * ar.S;
+    HotRec *__restrict__ nhot = ar.hot + (static_cast<size_t>(t) * 2 + (1 - h)) * ar.S;
+    ColdRec *__restrict__ ncold = ar.cold + (static_cast<size_t>(t) * 2 + (1 - h)) * ar.S;
     const int root = ar.root[t];
     const HotRec R = hot[root];
     const int action = actions[t];
@@ -293,12 +327,7 @@ __global__ void __launch_bounds__(WAVE) k_prune(TreeArena ar, SearchParams p, co
             if (nE > 0) {
                 const int dst = used + incl - nE;
                 nhot[q].child_off = dst;
-                for (int j = 0; j < nE; ++j) {
-                    nhot[dst + j] = hot[rec.child_off + j];
-                    ColdRec y = cold[rec.child_off + j];
-                    y.parent = q;
-                    ncold[dst + j] = y;
-                }
+                copy_child_block<(G::ACTIONS < 8 ? G::ACTIONS : 8)>(hot, cold, nhot, ncold, rec.child_off, dst, nE, q);
             }
             used += total;
         }
@@ -492,6 +521,98 @@ __global__ void __launch_bounds__(256) k_game_step(uint64_t *bb0, uint64_t *bb1,
     if (aux != nullptr) aux[i] = s.aux;
 }
 
+// ------------------------------------------------------------------ the device driver's ply tail
+
+// Root visit counts -> move, for a driver whose temperature is exactly 1 (player.py:348-371 with the schedule of
+// game.py:55-63): what the driver's torch chain computes, value for value.  The weights are the positive counts
+// as floats (a row without one: all ones), the sampled move is the arg-max of weight / q over the row with q the
+// caller's exponential draws - the form torch.multinomial gives one draw per row - and the greedy move the arg-max
+// of the counts; the lowest index wins a tie in both.  hot_early / hot_late: whether the temperature in force
+// before / from ply `decay_moves` (<= 0: always the early one) is above the greedy threshold.  dead: slots that
+// get -1 (nullptr: none).  One thread per game.
+template <class G>
+__global__ void __launch_bounds__(256) k_ply_pick(const int32_t *__restrict__ counts, const float *__restrict__ q,
+                                                  const int32_t *__restrict__ ply, const uint8_t *__restrict__ dead,
+                                                  int32_t *__restrict__ actions, int n, int decay_moves, int hot_early,
+                                                  int hot_late)
+{
+    constexpr int A = G::ACTIONS;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (dead != nullptr && dead[i]) { actions[i] = -1; return; }
+    const int32_t *c = counts + static_cast<size_t>(i) * A;
+    const float *e = q + static_cast<size_t>(i) * A;
+    bool any = false;
+    int greedy = 0, gbest = c[0];
+    for (int a = 0; a < A; ++a) {
+        const int v = c[a];
+        any = any || v > 0;
+        if (v > gbest) { gbest = v; greedy = a; }
+    }
+    int sampled = 0;
+    float sbest = 0.0f;
+    for (int a = 0; a < A; ++a) {
+        const int v = c[a];
+        const float w = any ? (v > 0 ? static_cast<float>(v) : 0.0f) : 1.0f;
+        const float r = __fdiv_rn(w, e[a]);
+        if (a == 0 || r > sbest) { sbest = r; sampled = a; }
+    }
+    const bool hot = (decay_moves <= 0 || ply[i] < decay_moves) ? hot_early != 0 : hot_late != 0;
+    actions[i] = hot ? sampled : greedy;
+}
+
+// What follows the re-rooting, in one launch: k_game_step's step and result, the restart of a finished game
+// (refill) or its slot going dead (no refill), the reset of its tree (k_reset_masked), the ply counters and the
+// running totals {positions, games, P1 wins, P2 wins, draws} (+n positions per call, as the driver counts them).
+// A slot whose action is out of range (a dead slot's -1) is left as it is with done = 0.  One thread per game;
+// the four counts are summed per workgroup and reach `totals` with one atomic each.
+template <class G>
+__global__ void __launch_bounds__(256) k_ply_advance(TreeArena ar, uint64_t *bb0, uint64_t *bb1, int32_t *turns,
+                                                     int32_t *aux, const int32_t *actions, uint8_t *done,
+                                                     int32_t *winner, int32_t *ply, uint8_t *dead,
+                                                     unsigned long long *totals, int n, int refill)
+{
+    __shared__ int s_cnt[4][4];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool fin = false;
+    int w = 0;
+    if (i < n) {
+        const int a = actions[i];
+        if (a >= 0 && a < G::ACTIONS) {
+            GameState s;
+            s.bb0 = bb0[i]; s.bb1 = bb1[i]; s.turn = turns[i]; s.aux = aux[i];
+            G::step(s, a);
+            const int res = G::result(s);
+            fin = res >= 0;
+            w = res == 1 ? 1 : (res == 2 ? -1 : 0);
+            if (fin && refill) G::start(s);
+            bb0[i] = s.bb0; bb1[i] = s.bb1; turns[i] = s.turn; aux[i] = s.aux;
+        }
+        done[i] = fin ? 1 : 0;
+        winner[i] = w;
+        const bool was_dead = dead[i] != 0;
+        int pl = ply[i] + (was_dead ? 0 : 1);
+        if (fin) {
+            write_fresh_root(ar.hot + tree_base(ar, i), ar.cold + tree_base(ar, i));
+            ar.root[i] = 0;
+            ar.used[i] = 1;
+            if (refill) pl = 0; else dead[i] = 1;
+        }
+        ply[i] = pl;
+    }
+    const int c0 = __popcll(__ballot(fin)), c1 = __popcll(__ballot(fin && w == 1));
+    const int c2 = __popcll(__ballot(fin && w == -1)), c3 = __popcll(__ballot(fin && w == 0));
+    if (lane == 0) { s_cnt[wave][0] = c0; s_cnt[wave][1] = c1; s_cnt[wave][2] = c2; s_cnt[wave][3] = c3; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        const int sum = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
+        if (sum) atomicAdd(totals + 1 + k, static_cast<unsigned long long>(sum));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 4) atomicAdd(totals, static_cast<unsigned long long>(n));
+}
+
 // legal actions of HBM-resident positions, one byte per action (env_common.h `valid_mask()`)
 template <class G>
 __global__ void __launch_bounds__(256) k_game_valid_mask(const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns,
@@ -593,6 +714,22 @@ void launch_game_step(int game, uint64_t *bb0, uint64_t *bb1, int32_t *turns, in
 {
     AZ_DISPATCH(game, hipLaunchKernelGGL(k_game_step<G>, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s,
                                          bb0, bb1, turns, aux, actions, done, winner, n, reset_finished ? 1 : 0));
+}
+
+void launch_ply_pick(int game, const int32_t *counts, const float *q, const int32_t *ply, const uint8_t *dead,
+                     int32_t *actions, int n, int decay_moves, bool hot_early, bool hot_late, hipStream_t s)
+{
+    AZ_DISPATCH(game, hipLaunchKernelGGL(k_ply_pick<G>, dim3((n + 255) / 256), dim3(256), 0, s, counts, q, ply, dead,
+                                         actions, n, decay_moves, hot_early ? 1 : 0, hot_late ? 1 : 0));
+}
+
+void launch_ply_advance(int game, TreeArena ar, uint64_t *bb0, uint64_t *bb1, int32_t *turns, int32_t *aux,
+                        const int32_t *actions, uint8_t *done, int32_t *winner, int32_t *ply, uint8_t *dead,
+                        int64_t *totals, bool refill, hipStream_t s)
+{
+    AZ_DISPATCH(game, hipLaunchKernelGGL(k_ply_advance<G>, dim3((ar.B + 255) / 256), dim3(256), 0, s, ar, bb0, bb1,
+                                         turns, aux, actions, done, winner, ply, dead,
+                                         reinterpret_cast<unsigned long long *>(totals), ar.B, refill ? 1 : 0));
 }
 
 void launch_game_valid_mask(int game, const uint64_t *bb0, const uint64_t *bb1, const int32_t *turns, const int32_t *aux,

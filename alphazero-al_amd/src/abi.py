@@ -236,6 +236,8 @@ PROTOTYPES = (
     ("az_c4_dev_step", i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp]),
     ("az_game_dev_step", i32, [i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
     ("az_game_dev_valid_mask", i32, [i32, vp, vp, vp, vp, vp, i64, vp]),
+    ("az_game_dev_pick", i32, [i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    ("az_mcts_dev_ply_advance", i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     ("az_mcts_dev_set_noise_epsilons", i32, [vp, vp]),
     ("az_mcts_dev_live_leaves", i32, [vp, i32, vp, vp, vp]),
     ("az_mcts_dev_search", i32, [vp, vp, i32, i32, i32, vp]),

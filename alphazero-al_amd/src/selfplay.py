@@ -9,7 +9,10 @@ loop and keeps finished games in the batch until the slowest one ends.  Here a p
     -> prune_roots with fresh device Dirichlet noise (HIP) -> game step + result (HIP; Othello's
        pass counter travels with the position, the trees forget it at every ply as the reference's do)
     -> finished games are replaced by fresh ones at once, their trees reset (HIP)
-so every slot plays a live position on every ply.  Same search semantics as
+so every slot plays a live position on every ply.  At temperature 1 the sampling is one torch call - the
+exponential draws torch.multinomial would make - and one kernel (az_game_dev_pick), and everything behind the
+re-rooting is one launch (az_mcts_dev_ply_advance); other temperatures, the reference sampler and recording drivers
+keep the torch calls, and AZ_PLY_TAIL=0 keeps them for every driver.  Same search semantics as
 BatchedMCTS.batch_playout; the schedule of temperatures follows game.py:55-63.
 
 This file is what bench.py times.
@@ -33,6 +36,8 @@ call into the library.  `DeviceSelfPlay` stays what bench.py times.
 """
 
 import ctypes as C
+import math
+import os
 
 import numpy as np
 import torch
@@ -130,6 +135,22 @@ class DeviceSelfPlay:
         # the host only enqueues; it may run at most `max_plies_ahead` plies ahead of the device
         self.max_plies_ahead = 1
         self._ply_events = []
+        # The ply's tail as native launches (az_game_dev_pick, az_mcts_dev_ply_advance) instead of torch chains;
+        # AZ_PLY_TAIL=0 keeps the torch tail.  The native pick is the torch one value for value at temperature
+        # exactly 1 (w ** 1.0 is w; any other exponent goes through torch's powf): wherever the sampled move can be
+        # played, the temperature has to be 1.  A recording driver keeps the torch advance, whose order lets the
+        # end state of a finished game survive until it is recorded.
+        tail = os.environ.get("AZ_PLY_TAIL", "1") != "0"
+        t_early, t_late = np.float32(self.temperature), np.float32(self.temp_endgame)
+        self._hot_early = bool(t_early > np.float32(1e-6))
+        self._hot_late = bool(t_late > np.float32(1e-6)) if self.temp_decay_moves > 0 else self._hot_early
+        plain = float(self.temperature) == 1.0 and (self.temp_decay_moves <= 0 or not self._hot_late
+                                                    or float(self.temp_endgame) == 1.0)
+        self._native_pick = tail and sampler == "device" and plain
+        self._native_advance = tail and not self.record
+        if self._native_pick:
+            self._q = torch.empty((self.B, self.search.action_size), dtype=torch.float32, **z)
+            self._decay_moves = int(math.ceil(self.temp_decay_moves))
         # noise-epsilon decay over the plies of a game (game.py:87-91 with AlphaZeroPlayer.noise_steps /
         # noise_eps_min, player.py:122,159-161): the reference moves ONE epsilon for a batch of games that
         # start together; here every game decays from its own first ply (az_mcts_dev_set_noise_epsilons)
@@ -243,7 +264,13 @@ class DeviceSelfPlay:
             self.eps_tree.copy_((self.noise_eps_min + (self.noise_eps_init - self.noise_eps_min) * decay).float())
         self.fused.search(self.n_playout, self.vl_batch)
         F.check(L.az_mcts_dev_counts(self.h, self.counts.data_ptr(), s))
-        if self.sampler == "reference":
+        if self._native_pick:
+            # the draws torch.multinomial(x, 1) makes for a (B, A) float input: the generator moves as it does there
+            self._q.exponential_(1.0, generator=self.gen)
+            F.check(L.az_game_dev_pick(self.game_id, self.counts.data_ptr(), self._q.data_ptr(), self.ply.data_ptr(),
+                                       None if self.refill else self.dead.data_ptr(), self.actions.data_ptr(), self.B,
+                                       self._decay_moves, int(self._hot_early), int(self._hot_late), s))
+        elif self.sampler == "reference":
             self._pick_actions_reference()
         else:
             self._pick_actions()
@@ -253,6 +280,26 @@ class DeviceSelfPlay:
             F.check(L.az_mcts_dev_root_stats(self.h, self.stats.data_ptr(), s))
             self._record_position()
         F.check(L.az_mcts_dev_prune_roots(self.h, self.actions.data_ptr(), s))
+        if self._native_advance:
+            F.check(L.az_mcts_dev_ply_advance(self.h, self.bb_p1.data_ptr(), self.bb_p2.data_ptr(), self.turn.data_ptr(),
+                                              self.aux.data_ptr(), self.actions.data_ptr(), self.done.data_ptr(),
+                                              self.winner.data_ptr(), self.ply.data_ptr(), self.dead.data_ptr(),
+                                              self.totals.data_ptr(), int(self.refill), s))
+        else:
+            self._advance_torch(s)
+        # sticky device error word (arena full, compact list overflow), polled without a stall:
+        # raises one ply after the fact instead of letting the trees thin out silently
+        F.check(L.az_mcts_dev_check(self.h, s))
+        # bounded run-ahead: ~550 launches per ply would otherwise pile up without limit
+        ev = torch.cuda.Event()
+        ev.record()
+        self._ply_events.append(ev)
+        if len(self._ply_events) > self.max_plies_ahead:
+            self._ply_events.pop(0).synchronize()
+
+    def _advance_torch(self, s):
+        """Game step, refill or death, tree reset, ply counters and totals as torch calls around two launches."""
+        L = F.lib()
         # with recording the end state has to survive the step: finished boards are reset below
         kernel_refill = 1 if (self.refill and not self.record) else 0
         F.check(L.az_game_dev_step(self.game_id, self.bb_p1.data_ptr(), self.bb_p2.data_ptr(), self.turn.data_ptr(),
@@ -276,15 +323,6 @@ class DeviceSelfPlay:
         self.totals += torch.stack([self._c_B, fin.sum(),
                                     (fin * (self.winner == 1)).sum(), (fin * (self.winner == -1)).sum(),
                                     (fin * (self.winner == 0)).sum()])
-        # sticky device error word (arena full, compact list overflow), polled without a stall:
-        # raises one ply after the fact instead of letting the trees thin out silently
-        F.check(L.az_mcts_dev_check(self.h, s))
-        # bounded run-ahead: ~550 launches per ply would otherwise pile up without limit
-        ev = torch.cuda.Event()
-        ev.record()
-        self._ply_events.append(ev)
-        if len(self._ply_events) > self.max_plies_ahead:
-            self._ply_events.pop(0).synchronize()
 
     def drain(self):
         """Finished games since the last call, as the reference's `batch_self_play` returns them:

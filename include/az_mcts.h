@@ -215,6 +215,28 @@ int az_game_dev_step(int game, uint64_t *bb_p1, uint64_t *bb_p2, int32_t *turns,
 int az_game_dev_valid_mask(int game, const uint64_t *bb_p1, const uint64_t *bb_p2, const int32_t *turns,
                            const int32_t *aux, uint8_t *mask, int64_t n, void *stream);
 
+/* The tail of a self-play ply for a driver that keeps its games in HBM next to the trees, as two launches.
+ *
+ * az_game_dev_pick: root visit counts int32[n*A] -> actions int32[n] at temperature 1 (player.py:348-371 with the
+ * schedule of game.py:55-63).  Weights are the positive counts as floats, a row without one counts as all ones; the
+ * sampled move is the arg-max over the row of weight / q[i, a] (float32[n*A], the caller's Exp(1) draws: one draw
+ * per row of a multinomial, the form torch.multinomial uses, so a caller that fills q from its torch generator
+ * plays what torch.multinomial would have played); the greedy move is the arg-max of the counts; the lowest index
+ * wins ties.  A game takes the sampled move when the temperature in force is above the greedy threshold:
+ * hot_early while ply[i] < temp_decay_moves (always, when temp_decay_moves <= 0), hot_late from then on.
+ * dead uint8[n] (NULL: none): slots that get action -1.
+ *
+ * az_mcts_dev_ply_advance, behind az_mcts_dev_prune_roots, for the n_envs games of the engine's trees:
+ * az_game_dev_step's step, done[] and winner[] (a slot with an action out of range is left alone, done = 0); a
+ * finished game restarts from the initial position with ply 0 (refill != 0) or its slot turns dead (dead[i] = 1);
+ * its tree is reset (az_mcts_dev_reset_masked with done[] as the mask); ply[i] += 1 in slots that were not dead;
+ * totals int64[5] += {n_envs, finished games, wins of +1, wins of -1, draws}.  All arrays in HBM, updated in place. */
+int az_game_dev_pick(int game, const int32_t *counts, const float *q, const int32_t *ply, const uint8_t *dead,
+                     int32_t *actions, int64_t n, int temp_decay_moves, int hot_early, int hot_late, void *stream);
+int az_mcts_dev_ply_advance(az_mcts *m, uint64_t *bb_p1, uint64_t *bb_p2, int32_t *turns, int32_t *aux,
+                            const int32_t *actions, uint8_t *done, int32_t *winner, int32_t *ply, uint8_t *dead,
+                            int64_t *totals, int refill, void *stream);
+
 /* Root-noise epsilon PER TREE: `per_tree` (n_envs floats in DEVICE memory, owned and kept alive by the
  * caller; NULL switches back to the config's scalar) replaces az_search_config.noise_epsilon in every
  * selection from the next launch on.  The reference decays one global epsilon over the plies of a batch

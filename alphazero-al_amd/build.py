@@ -56,7 +56,7 @@ def build_engine(force=False):
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(LIB, "libaz_mcts.so")
-    names = ("kernels", "select_kernels", "backup_kernels", "rollout_search", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "optim_kernels", "train_block_kernels", "train_attn_kernels", "train_stem_kernels", "train_heads_kernels", "learn_driver", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "nn_othello", "nn_othello_heads", "nn_selftest")
+    names = ("kernels", "select_kernels", "backup_kernels", "rollout_search", "tt_kernels", "selfplay_kernels", "match_kernels", "replay_kernels", "train_kernels", "optim_kernels", "train_block_kernels", "train_attn_kernels", "train_stem_kernels", "train_heads_kernels", "learn_driver", "engine", "engine_host", "engine_dev", "selfplay_driver", "match_driver", "nn_kernels", "nn_conv", "nn_stem", "nn_attn", "nn_attn_heads", "nn_heads", "nn_model", "publish_kernels", "nn_othello", "nn_othello_heads", "nn_selftest")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = _headers()
     # a library newer than every source and header is up to date, whether or not the objects it was linked from are kept

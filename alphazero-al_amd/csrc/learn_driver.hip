@@ -535,4 +535,29 @@ int az_learn_reset_sums(az_learn *l, void *stream)
     });
 }
 
+int az_learn_publish(az_learn *l, struct az_nn_model *m, float *scalars_dev, void *stream)
+{
+    return guarded([&] {
+        const std::string w("az_learn_publish");
+        require(l != nullptr && m != nullptr && scalars_dev != nullptr, w + ": null argument");
+        require(l->bound, w + ": called before az_learn_bind");
+        auto p = [&](int r) { return static_cast<const float *>(l->param[r]); };
+        az_nn_publish_src s{};
+        s.piece_emb = p(AZ_LEARN_ROLE_PIECE_EMB); s.pos_emb = p(AZ_LEARN_ROLE_POS_EMB);
+        s.stem_conv_weight = p(AZ_LEARN_ROLE_STEM_CONV_WEIGHT); s.stem_conv_bias = p(AZ_LEARN_ROLE_STEM_CONV_BIAS);
+        s.n_blocks = l->c.n_blocks;
+        for (int k = 0; k < l->c.n_blocks; ++k) {
+            s.block_norm_weight[k] = p(AZ_LEARN_ROLE_BLOCK + 4 * k); s.block_norm_bias[k] = p(AZ_LEARN_ROLE_BLOCK + 4 * k + 1);
+            s.block_conv_weight[k] = p(AZ_LEARN_ROLE_BLOCK + 4 * k + 2); s.block_conv_bias[k] = p(AZ_LEARN_ROLE_BLOCK + 4 * k + 3);
+        }
+        // the six attention tensors and the eighteen head tensors follow in the roles' order
+        static_assert(offsetof(az_nn_publish_src, aux_out_bias) - offsetof(az_nn_publish_src, prenorm_weight) == 23 * sizeof(float *) &&
+                      AZ_LEARN_ROLE_HEADS == AZ_LEARN_ROLE_ATTN + 6, "az_nn_publish_src ends in 24 pointers in the roles' order");
+        const float **f = &s.prenorm_weight;
+        for (int i = 0; i < 6 + 18; ++i) f[i] = p(AZ_LEARN_ROLE_ATTN + i);
+        const int rc = az_nn_model_publish(m, &s, scalars_dev, stream);
+        if (rc != 0) throw AzError(rc, w + ": az_nn_model_publish refused the call (the model's kind or n_blocks, an alignment, a capturing stream)");
+    });
+}
+
 }  // extern "C"

@@ -3,8 +3,9 @@
 // reference's Connect4 network) issued from native code on the caller's stream.
 //
 // The object holds POINTERS to the caller's weight arrays (bf16, the layouts az_nn.h documents
-// for each kernel) and nothing else: it is immutable after creation, so any number of host
-// threads / streams may run az_nn_model_forward on it at once, each with scratch of its own.
+// for each kernel) and nothing else.  Only az_nn_model_publish / az_nn_model_set_head_biases change
+// it (the arrays in place, the three head biases it carries by value); between such calls any number
+// of host threads / streams may run az_nn_model_forward on it at once, each with scratch of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -409,6 +410,38 @@ int az_nn_model_forward_positions(const az_nn_model *m, const az_nn_positions *p
 {
     if (positions == nullptr || !positions->bb_p1 || !positions->bb_p2 || !positions->turn || !positions->sym) return 1;
     return forward(m, nullptr, positions, mask, probs, wdl, moves_left, batch, rows, n_rows, scratch, scratch_bytes, stream);
+}
+
+int az_nn_model_set_head_biases(az_nn_model *m, float p_gate_b, float p_out_b, float d_aux_b)
+{
+    if (m == nullptr || m->kind != AZ_NN_KIND_CONNECT4_CNN) return 1;
+    m->w.heads.p_gate_b = p_gate_b;
+    m->w.heads.p_out_b = p_out_b;
+    m->w.heads.d_aux_b = d_aux_b;
+    return 0;
+}
+
+int az_nn_model_head_biases(const az_nn_model *m, float out[3])
+{
+    if (m == nullptr || out == nullptr || m->kind != AZ_NN_KIND_CONNECT4_CNN) return 1;
+    out[0] = m->w.heads.p_gate_b;
+    out[1] = m->w.heads.p_out_b;
+    out[2] = m->w.heads.d_aux_b;
+    return 0;
+}
+
+int az_nn_model_publish(az_nn_model *m, const az_nn_publish_src *src, float *scalars_dev, void *stream)
+{
+    if (m == nullptr || m->kind != AZ_NN_KIND_CONNECT4_CNN) return 1;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(hs, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return 1;      // it waits below
+    const int rc = az_nn_publish_dev(src, &m->w, scalars_dev, stream);
+    if (rc != 0) return rc;
+    float host[3] = {0.0f, 0.0f, 0.0f};
+    if (hipMemcpyAsync(host, scalars_dev, sizeof(host), hipMemcpyDeviceToHost, hs) != hipSuccess) return 2;
+    if (hipStreamSynchronize(hs) != hipSuccess) return 2;
+    return az_nn_model_set_head_biases(m, host[0], host[1], host[2]);
 }
 
 int az_nn_model_profile(int enable)

@@ -316,6 +316,12 @@ PROTOTYPES = (
     ("az_nn_model_profile", i32, [i32]),
     ("az_nn_model_profile_read", i32, [P(C.c_double), P(i64)]),
     ("az_nn_model_profile_read_kernels", i32, [P(C.c_double * 4), P(i64 * 4)]),
+    # az_nn_publish_src travels as plain c_void_p; its mirror lives in src/publish.py under its own table and
+    # tests/test_publish_cpu.py holds its layout to the header
+    ("az_nn_publish_dev", i32, [vp, P(ModelWeights), vp, vp]),
+    ("az_nn_model_set_head_biases", i32, [vp, f32, f32, f32]),
+    ("az_nn_model_head_biases", i32, [vp, P(f32 * 3)]),
+    ("az_nn_model_publish", i32, [vp, vp, vp, vp]),
     ("az_nn_debug", i32, [i32]),
     ("az_nn_debug_flags", i32, []),
     ("az_nn_conv_profile", i32, [vp, i32]),
@@ -347,6 +353,7 @@ PROTOTYPES = (
     ("az_learn_dev_keep", i32, [vp, i64, u64, vp]),
     ("az_learn_outputs", i32, [vp, vp]),
     ("az_learn_reset_sums", i32, [vp, vp]),
+    ("az_learn_publish", i32, [vp, vp, vp, vp]),
     ("az_train_block_workspace_bytes", i64, [i64, i32]),
     ("az_train_dev_block_fwd", i32, [vp, vp, vp, i64, f32, vp, vp, vp]),
     ("az_train_dev_block_bwd", i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),

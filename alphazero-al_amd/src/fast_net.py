@@ -169,6 +169,12 @@ class FastConnect4Net(torch.nn.Module):
             self.__dict__["_model"] = h
         return self.__dict__["_model"]
 
+    def publish_from(self, source):
+        """`source`'s parameters - a module with the reference's names, or a `NativeLearner` - into THIS twin's buffers as
+        one launch (src/publish.py): the native model and every captured graph stay valid.  Returns the three head biases."""
+        from src.publish import publish
+        return publish(self, source)
+
     def __del__(self):
         # may run while the interpreter is being torn down: no nn.Module machinery, no exceptions
         try:

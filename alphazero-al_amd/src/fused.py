@@ -19,6 +19,7 @@ plays recorded draws back so that the loop can be compared with the oracle bit f
 """
 import ctypes as C
 import gc
+import struct
 import weakref
 import os
 
@@ -116,6 +117,37 @@ class FusedSearch:
             self._eager_runs.clear()
             if self.table_log2:         # cached outputs belong to the old weights (MCTS_cpp.py:361-377)
                 self.refresh_table()
+
+    def publish_weights(self):
+        """The module's current parameters into the evaluator.  With a Connect4 twin already there and the module still
+        publishable into it (src/publish.py: same shapes, float32 on the twin's GPU): ONE launch into the twin's existing
+        buffers - the twin, its native model and the captured graphs stay; the graphs go only if one of the three head
+        biases changed in bits, because those are kernel arguments inside a capture - and "published".  Otherwise what
+        `_sync_fast_net()` does, and "rebuilt".  Opt-in: `_sync_fast_net` never calls it."""
+        from src.fast_net import FastConnect4Net
+        from src import publish as PB
+        fast = self.fast
+        if self.use_fast and isinstance(fast, FastConnect4Net) and fast.hip and not hasattr(self.net, "predict_device"):
+            try:
+                PB.source_struct(self.net, fast)
+            except ValueError:
+                fast = None
+        else:
+            fast = None
+        if fast is None:
+            self._sync_fast_net()
+            return "rebuilt"
+        bits = lambda b: struct.pack("<3f", *b)      # noqa: E731
+        before = bits((fast._heads_w.p_gate_b, fast._heads_w.p_out_b, fast._heads_w.d_aux_b))
+        after = bits(PB.publish(fast, self.net))
+        self._fast_version = (tuple(p._version for p in self.net.parameters()) + tuple(p.data_ptr() for p in self.net.parameters()) +
+                              tuple(b._version for b in self.net.buffers()))
+        if after != before:
+            self._graphs.clear()
+            self._eager_runs.clear()
+        if self.table_log2:
+            self.refresh_table()
+        return "published"
 
     def _native_model(self):
         """az_nn_model* when the search can run as one native call: HIP inference twin, compact

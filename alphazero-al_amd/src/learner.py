@@ -393,6 +393,12 @@ class NativeLearner:
         host = torch.cat([self.sums / n_batches, self.entropy, self.grad_norm, confusion.reshape(-1).to(torch.float32)]).cpu()
         return (float(host[0]), float(host[1]), float(host[2]), float(host[3]), float(host[4]), TL.macro_f1(host[5:14]))
 
+    def publish(self, fast):
+        """What this learner has trained into the live inference twin `fast` (a `FastConnect4Net`) by az_learn_publish: one
+        launch into the twin's existing buffers and one wait (src/publish.py).  Returns the three head biases."""
+        from src.publish import publish
+        return publish(fast, self)
+
     # ------------------------------------------------------------------------------------ the end
 
     def _require_open(self):

@@ -17,7 +17,7 @@
  * shows, `scatter[b]` (heads) the row of the mask and of the three output arrays it belongs to;
  * NULL = identity.
  *
- * In this order: the forward pass; the model object and its profiling; debug and self-test entry
+ * In this order: the forward pass; the model object, its profiling and publishing weights into it; debug and self-test entry
  * points; kernels kept as test oracles; the Othello network.
  */
 #ifndef AZ_NN_H
@@ -141,8 +141,9 @@ int az_nn_attn_heads(const void *x, const void *prenorm_w, const void *qkvg_w, c
  *   the blocks  az_nn_conv_block (64 -> 64, normalised, residual) for each of the n_blocks not yet run;
  *   attention and heads  az_nn_attn_heads (AZ_ATTN_HEADS_FUSED=0 in the environment when the object is created:
  *       az_nn_attn_block, then az_nn_heads).
- * The object keeps the POINTERS given here (the caller keeps the arrays alive and unchanged) and is immutable, so it
- * may be used from several host threads / streams at once; each call brings its own `scratch`
+ * The object keeps the POINTERS given here (the caller keeps the arrays alive) and nothing changes it or them except
+ * az_nn_model_publish / az_nn_model_set_head_biases below; between such calls it may be used from several host threads /
+ * streams at once; each call brings its own `scratch`
  * (device memory, az_nn_model_scratch_bytes(batch) bytes: two activation tensors).
  * rows / n_rows: the compact form described at the top (both NULL = every row 0..batch-1). */
 #define AZ_NN_MAX_BLOCKS 8
@@ -202,6 +203,70 @@ int az_nn_model_profile_read(double *out_ms, int64_t *out_launches);
 #define AZ_NN_PROFILE_ATTN  2
 #define AZ_NN_PROFILE_HEADS 3
 int az_nn_model_profile_read_kernels(double out_ms[4], int64_t out_launches[4]);
+
+/* Publishing trained weights into a live model (alphazero-al_amd/csrc/publish_kernels.hip, k_publish): the evaluator's
+ * arrays are a pure function of the network's float32 parameters, and az_nn_publish_dev computes that function in ONE
+ * launch, writing the arrays an az_nn_model_weights names IN PLACE - the model handle, the twin's buffers and every
+ * pointer inside a captured graph stay valid.  Connect4 network only.
+ * Sources: the float32 tensors of the reference's Connect4 state dict in DEVICE memory, contiguous, 4-byte aligned, with
+ * the shapes of AZ_LEARN_ROLE_* (az_train.h).  "bf16" = float32 rounded to nearest-even (torch's .to(torch.bfloat16)
+ * for finite values and infinities).  Every destination byte is written.
+ *   plain casts, same element order:  emb_own, emb_opp = piece_emb[0], [1];  stem_b;  every block's bias, gamma (norm
+ *       weight), beta (norm bias);  pre_w, qn_w, kn_w, o_w;  qkvg_w rows 0 .. 191 = qkv_weight, rows 192 .. 195 =
+ *       gate_weight;  the 15 pointers of az_nn_heads_weights from the policy_head.* / dual_head.* tensors of the same name
+ *   pos[cell][c]       = bf16(pos_emb[orbit(cell)][c]),  orbit(cell) = 4 * (cell / 7) + min(cell % 7, 6 - cell % 7)
+ *   stem_w[o][tap][c]  = bf16(W[o][c][tap]),  c_in 32;  every block_w the same with c_in 64  (OIHW -> OHWI)
+ *   stem_frag, stem_pmap (when the destination has them): as az_nn_stem_folded above defines them, from
+ *       w = float(bf16(W)), b = float(bf16(stem bias)) and the two embedding tables in float32.  The order of every sum
+ *       is FIXED, each step one float32 multiply and one float32 add (no fused multiply-add), starting from +0:
+ *         T[o][2 tap + plane] = sum over c = 0, 1, .. 31 of w[o][c][tap] * piece_emb[plane][c];   T[o][k >= 18] = 0
+ *         hi = bf16(T),  lo = bf16(T - float(hi)),  both scattered into the fragment order
+ *         pmap[cell][o] = (one running sum over the taps INSIDE the board, ascending (ky, then kx), and inside a tap over
+ *                         c = 0 .. 31, of w[o][c][tap] * pos_emb[orbit(cell + tap)][c]) + b[o], the bias added last;
+ *                         rows 42 .. 47 and columns 64 .. 67 are zeros
+ *       so that a numpy float32 restatement (tests/publish_ref.py) reproduces the bytes.
+ *   scalars_dev[0 .. 2] = row_gate_bias, policy_out_bias, aux_out_bias as float32 (the slot's fourth float is not written)
+ * Every job reads sources only; no workgroup waits for another. */
+typedef struct az_nn_publish_src {
+    const float *piece_emb, *pos_emb, *stem_conv_weight, *stem_conv_bias;       /* [2][32], [24][32], [64][32][3][3], [64] */
+    int32_t n_blocks;                                                           /* 1 .. AZ_NN_MAX_BLOCKS */
+    const float *block_norm_weight[AZ_NN_MAX_BLOCKS], *block_norm_bias[AZ_NN_MAX_BLOCKS];       /* [64] each */
+    const float *block_conv_weight[AZ_NN_MAX_BLOCKS], *block_conv_bias[AZ_NN_MAX_BLOCKS];       /* [64][64][3][3], [64] */
+    const float *prenorm_weight, *qkv_weight, *gate_weight, *o_weight, *q_norm_weight, *k_norm_weight;  /* as az_train_attn_params */
+    const float *policy_norm_weight, *row_gate_weight, *row_gate_bias, *policy_fc_weight, *policy_fc_bias;  /* as az_train_heads_params */
+    const float *policy_out_weight, *policy_out_bias, *pool_norm_weight, *pool_fc_weight, *pool_fc_bias;
+    const float *norm_weight, *fc_weight, *fc_bias, *out_norm_weight, *value_out_weight, *value_out_bias;
+    const float *aux_out_weight, *aux_out_bias;
+} az_nn_publish_src;
+#define AZ_NN_PUBLISH_SRC_BYTES 488
+#ifdef __cplusplus
+static_assert(sizeof(az_nn_publish_src) == AZ_NN_PUBLISH_SRC_BYTES, "az_nn_publish_src");
+#else
+_Static_assert(sizeof(az_nn_publish_src) == AZ_NN_PUBLISH_SRC_BYTES, "az_nn_publish_src");
+#endif
+/* The one launch on `stream` and nothing else: it does not wait, allocate or copy, so it may be captured.  It WRITES
+ * through dst's pointers (const in the struct because the evaluator only reads them): they must be writable device
+ * memory owned by the caller.  dst->stem_frag and dst->stem_pmap may both be NULL: no folded stem; dst's scalars (the
+ * four floats of its heads, eps) are not read.
+ * Returns 1 with nothing enqueued and nothing written: a null struct, source, destination or scalars_dev; n_blocks
+ * outside 1 .. AZ_NN_MAX_BLOCKS or different between src and dst; only one of stem_frag / stem_pmap; a source not 4-byte
+ * aligned; a destination written with 16-byte stores - pos, stem_w, every block_w, qkvg_w, o_w, heads.p_fc_w,
+ * heads.d_pool_w, heads.d_fc_w, stem_frag - not 16-byte aligned, another bf16 destination not 2-byte aligned, stem_pmap
+ * or scalars_dev not 4-byte aligned.  2: the launch was refused. */
+int az_nn_publish_dev(const az_nn_publish_src *src, const az_nn_model_weights *dst, float *scalars_dev, void *stream);
+/* The three biases that travel to the evaluator kernels BY VALUE inside az_nn_heads_weights, on the host: set them / read
+ * them back (out: p_gate_b, p_out_b, d_aux_b).  aux_scale is never touched.  Connect4 network kind only, else 1 (as for
+ * a null argument).  A forward enqueued afterwards carries the new values; one captured before carries the old ones. */
+int az_nn_model_set_head_biases(az_nn_model *m, float p_gate_b, float p_out_b, float d_aux_b);
+int az_nn_model_head_biases(const az_nn_model *m, float out[3]);
+/* az_nn_publish_dev on the model's own arrays, then the 12 bytes of scalars_dev to the host, a wait for `stream`, and
+ * az_nn_model_set_head_biases with them.  Returns 1 with nothing enqueued as az_nn_publish_dev does, for a model of
+ * another kind, and for a stream that is capturing.
+ * It WAITS once and must not be captured: the three biases are kernel arguments, so the host has to see them (reading
+ * them on the device instead would change the evaluator kernels).
+ * No forward of this model may be in flight on another stream, or be enqueued from another thread, during the call;
+ * forwards enqueued on `stream` afterwards see the new weights. */
+int az_nn_model_publish(az_nn_model *m, const az_nn_publish_src *src, float *scalars_dev, void *stream);
 
 /* ---- debug and self-test entry points */
 

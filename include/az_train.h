@@ -286,6 +286,13 @@ int  az_learn_dev_keep(az_learn *l, int64_t N, uint64_t call, void *stream);
 int  az_learn_outputs(az_learn *l, az_learn_out *out);
 /* sums, batches and entropy to zero, on `stream`. */
 int  az_learn_reset_sums(az_learn *l, void *stream);
+/* What the learner has just trained, into a live evaluator: az_nn_model_publish (include/az_nn.h) with its source struct
+ * filled from the tensors az_learn_bind holds by role.  One launch on `stream`, a 12-byte copy and ONE wait for `stream`
+ * (the three head biases are kernel arguments of the evaluator); not to be captured, and no forward of `m` may be in
+ * flight elsewhere meanwhile.  scalars_dev: three float32 in device memory, 4-byte aligned, the caller's.
+ * AZ_ERR_ARG, with nothing enqueued and nothing written: a null argument; a call before az_learn_bind; a model that is
+ * not a Connect4 network or whose n_blocks differs from the learner's; whatever else az_nn_model_publish refuses. */
+int  az_learn_publish(az_learn *l, struct az_nn_model *m, float *scalars_dev, void *stream);
 
 /* ---- The Connect4 residual block's training forward and backward (alphazero-al_amd/csrc/train_block_kernels.hip):
  * y = x + keep * silu(conv3x3(GroupNorm(1, 64)(x))), the reference's `ResidualBlock(64, 64)` with its Dropout2d factor

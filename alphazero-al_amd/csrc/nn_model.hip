@@ -3,7 +3,8 @@
 // reference's Connect4 network) issued from native code on the caller's stream.
 //
 // The object holds POINTERS to the caller's weight arrays (bf16, the layouts az_nn.h documents
-// for each kernel) and nothing else.  Only az_nn_model_publish / az_nn_model_set_head_biases change
+// for each kernel) and nothing else.  Only az_nn_model_publish / az_nn_model_set_head_biases and, for an
+// Othello model, az_nn_model_publish_othello / az_nn_model_set_othello_head_biases change
 // it (the arrays in place, the three head biases it carries by value); between such calls any number
 // of host threads / streams may run az_nn_model_forward on it at once, each with scratch of its own.
 #include <hip/hip_runtime.h>
@@ -442,6 +443,38 @@ int az_nn_model_publish(az_nn_model *m, const az_nn_publish_src *src, float *sca
     if (hipMemcpyAsync(host, scalars_dev, sizeof(host), hipMemcpyDeviceToHost, hs) != hipSuccess) return 2;
     if (hipStreamSynchronize(hs) != hipSuccess) return 2;
     return az_nn_model_set_head_biases(m, host[0], host[1], host[2]);
+}
+
+int az_nn_model_set_othello_head_biases(az_nn_model *m, float board_b, float pass_fc_b, float a_out_b)
+{
+    if (m == nullptr || m->kind != AZ_NN_KIND_OTHELLO_CNN) return 1;
+    m->ow.heads.board_b = board_b;
+    m->ow.heads.pass_fc_b = pass_fc_b;
+    m->ow.heads.a_out_b = a_out_b;
+    return 0;
+}
+
+int az_nn_model_othello_head_biases(const az_nn_model *m, float out[3])
+{
+    if (m == nullptr || out == nullptr || m->kind != AZ_NN_KIND_OTHELLO_CNN) return 1;
+    out[0] = m->ow.heads.board_b;
+    out[1] = m->ow.heads.pass_fc_b;
+    out[2] = m->ow.heads.a_out_b;
+    return 0;
+}
+
+int az_nn_model_publish_othello(az_nn_model *m, const az_nn_othello_publish_src *src, float *scalars_dev, void *stream)
+{
+    if (m == nullptr || m->kind != AZ_NN_KIND_OTHELLO_CNN) return 1;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(hs, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return 1;      // it waits below
+    const int rc = az_nn_othello_publish_dev(src, &m->ow, scalars_dev, stream);
+    if (rc != 0) return rc;
+    float host[3] = {0.0f, 0.0f, 0.0f};
+    if (hipMemcpyAsync(host, scalars_dev, sizeof(host), hipMemcpyDeviceToHost, hs) != hipSuccess) return 2;
+    if (hipStreamSynchronize(hs) != hipSuccess) return 2;
+    return az_nn_model_set_othello_head_biases(m, host[0], host[1], host[2]);
 }
 
 int az_nn_model_profile(int enable)

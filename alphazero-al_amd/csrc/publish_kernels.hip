@@ -241,3 +241,245 @@ extern "C" int az_nn_publish_dev(const az_nn_publish_src *src, const az_nn_model
     hipLaunchKernelGGL(k_publish, dim3(static_cast<unsigned>(wgs)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The Othello network's (az_nn_othello_publish_dev in az_nn.h): the same recipe - a job table in the kernel arguments, a
+// workgroup finds its job from its index, every job reads SOURCES only.
+//
+//   k_publish_othello
+//     O_EMBED   the (64 cells x 4 kinds, 32) table: one float32 add per element, one 16-byte store per eight channels.
+//     O_CONV    workgroup (tile, kc) of a [rows][c_in][3][3] weight: its 16 rows of 288 contiguous floats in element order
+//               into LDS (rows padded to 289 floats), out as nine runs of 1 KB, one per tap: 64 lanes x one 16-byte store,
+//               each lane's eight j packed from LDS.  128 workgroups for a 256-channel layer, 16 for the stem, 8 for the
+//               bottleneck (one tile, rows 8 .. 15 zeros).
+//     O_BN      one BatchNorm as scale / shift, one workgroup; it takes two table entries (weight, var -> scale; bias,
+//               mean -> shift).  `pad16`: entries count .. 15 are 1.0f / 0.0f (the bottleneck's).
+//     O_TRANS   a 64 x 64 tile of the 512 x 512 transpose through LDS: loads and stores both in element order.
+//     O_PERM16  eight rows of a_fc_w16: 8 x 512 floats into LDS, out as [cell][c] bf16, one 16-byte store per cell.
+//     O_VCONV   v_conv_w[ci * 9 + k][co] = W[co][ci][k] (576 floats);  O_COPY a float32 copy;  O_BF16 a bf16 cast of a small
+//               tensor;  O_SCALARS the three biases (two table entries).
+//   No atomics, no scratch, plain vector stores; every destination byte is written by exactly one lane.
+//
+// The BatchNorm affine is four float32 operations, each correctly rounded: the build has -ffp-contract=off and no fast-math
+// flag, and sqrtf and / are correctly rounded under hipcc's defaults.
+
+namespace {
+
+constexpr int O_CH = 256, O_EMB = 32, O_CELLS = 64, O_ROW = 32 * TAPS;          // 288 floats of one output row and kc chunk
+constexpr int O_ROW_PAD = O_ROW + 1;                                             // LDS stride of a row: odd, so that the 16 rows of a tap spread over the banks
+constexpr int O_TILE = 64, O_TILE_PAD = O_TILE + 1;                              // the transpose's tile
+constexpr int O_FC = 512, O_PERM_ROWS = 8;
+constexpr int O_LDS = 16 * O_ROW_PAD;                                            // 4624 floats: >= 64 * 65 and >= 8 * 512
+constexpr int O_MAX_JOBS = 100;                                                  // 16 convolutions, 34 BatchNorms at two entries, 16 more
+static_assert(O_LDS >= O_TILE * O_TILE_PAD && O_LDS >= O_PERM_ROWS * O_FC, "one LDS buffer serves every job kind");
+enum OKind : int32_t { O_EMBED = 0, O_CONV = 1, O_BN = 2, O_TRANS = 3, O_PERM16 = 4, O_VCONV = 5, O_COPY = 6, O_BF16 = 7, O_SCALARS = 8,
+                       O_SECOND = 9 };
+
+struct OJob {
+    void *dst;
+    const float *src, *aux;     // O_EMBED: pos_emb, piece_emb (the entry behind it: legal_emb); O_BN: weight, var / bias, mean
+    int32_t kind;
+    int32_t count;              // elements; O_CONV: c_in | rows << 16 | tiles << 24; O_BN: channels | pad16 << 16
+};
+static_assert(sizeof(OJob) == 32, "OJob");
+
+struct OthelloPublishArgs {
+    OJob job[O_MAX_JOBS];
+    int32_t first[O_MAX_JOBS + 1];          // job j owns workgroups first[j] .. first[j + 1] - 1
+    int32_t n_jobs;
+    float bn_eps;
+};
+static_assert(sizeof(OthelloPublishArgs) <= 4096, "the job table travels in the kernel arguments");
+
+// the reference's 64-entry orbit table (Othello/Network.py _ORBIT_MAP) as its closed form: the octant's triangle a <= b <= 3
+// numbered row by row
+__device__ __forceinline__ int othello_orbit(int cell)
+{
+    const int r = cell >> 3, c = cell & 7;
+    const int fr = r < 7 - r ? r : 7 - r, fc = c < 7 - c ? c : 7 - c;
+    const int a = fr < fc ? fr : fc, b = fr < fc ? fc : fr;
+    return (a == 0 ? 0 : a == 1 ? 4 : a == 2 ? 7 : 9) + b - a;
+}
+
+// n floats in element order into LDS (4-byte loads: the sources are only 4-byte aligned)
+__device__ __forceinline__ void stage(float *lds, const float *src, int n, int t)
+{
+    for (int i = t; i < n; i += THREADS) lds[i] = src[i];
+}
+
+__global__ void __launch_bounds__(THREADS) k_publish_othello(const OthelloPublishArgs a)
+{
+    __shared__ float buf[O_LDS];
+    const int t = threadIdx.x;
+    const int wg = blockIdx.x;
+    int j = 0;
+    while (j + 1 < a.n_jobs && wg >= a.first[j + 1]) ++j;
+    const int part = wg - a.first[j];
+    const OJob job = a.job[j];
+
+    if (job.kind == O_EMBED) {
+        const float *pos = job.src, *piece = job.aux, *legal = a.job[j + 1].src;
+        for (int i = t; i < O_CELLS * 4 * (O_EMB / 8); i += THREADS) {
+            const int row = i / (O_EMB / 8), c0 = 8 * (i % (O_EMB / 8));
+            const int cell = row >> 2, kind = row & 3;
+            const float *k = kind == 0 ? piece : kind == 1 ? piece + O_EMB : kind == 2 ? legal + O_EMB : legal;
+            const float *p = pos + othello_orbit(cell) * O_EMB;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = p[c0 + e] + k[c0 + e];
+            *reinterpret_cast<V8 *>(static_cast<uint16_t *>(job.dst) + row * O_EMB + c0) = pack8(v);
+        }
+    } else if (job.kind == O_CONV) {
+        const int c_in = job.count & 0xffff, rows = (job.count >> 16) & 0xff, tiles = job.count >> 24;
+        const int nkc = c_in / 32, tile = part / nkc, kc = part % nkc;
+        for (int i = t; i < 16 * O_ROW; i += THREADS) {
+            const int tl = i / O_ROW, r = i % O_ROW;
+            buf[tl * O_ROW_PAD + r] = tl < rows ? job.src[(static_cast<int64_t>(16 * tile + tl) * c_in + 32 * kc) * TAPS + r] : 0.0f;
+        }
+        __syncthreads();
+        for (int i = t; i < TAPS * 64; i += THREADS) {
+            const int tap = i >> 6, lane = i & 63, g = lane >> 4, tl = lane & 15;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = buf[tl * O_ROW_PAD + (8 * g + e) * TAPS + tap];
+            *reinterpret_cast<V8 *>(static_cast<uint16_t *>(job.dst) + ((static_cast<int64_t>(tap * nkc + kc) * tiles + tile) * 64 + lane) * 8) = pack8(v);
+        }
+    } else if (job.kind == O_BN) {
+        const OJob second = a.job[j + 1];
+        const int n = job.count & 0xffff, pad16 = job.count >> 16;
+        float *scale = static_cast<float *>(job.dst), *shift = static_cast<float *>(second.dst);
+        for (int i = t; i < n; i += THREADS) {
+            const float s0 = job.aux[i] + a.bn_eps;
+            const float root = sqrtf(s0);
+            const float sc = job.src[i] / root;
+            const float prod = second.aux[i] * sc;
+            scale[i] = sc;
+            shift[i] = second.src[i] - prod;
+        }
+        if (pad16 && t >= n && t < 16) { scale[t] = 1.0f; shift[t] = 0.0f; }
+    } else if (job.kind == O_TRANS) {
+        const int to = part / (O_FC / O_TILE), ti = part % (O_FC / O_TILE);         // the tile's first out row / in column, in tiles
+        for (int i = t; i < O_TILE * O_TILE; i += THREADS) {
+            const int r = i / O_TILE, c = i % O_TILE;
+            buf[r * O_TILE_PAD + c] = job.src[(O_TILE * to + r) * O_FC + O_TILE * ti + c];
+        }
+        __syncthreads();
+        float *dst = static_cast<float *>(job.dst);
+        for (int i = t; i < O_TILE * O_TILE; i += THREADS) {
+            const int r = i / O_TILE, c = i % O_TILE;                                // r: in, c: out
+            dst[(O_TILE * ti + r) * O_FC + O_TILE * to + c] = buf[c * O_TILE_PAD + r];
+        }
+    } else if (job.kind == O_PERM16) {
+        const int row0 = part * O_PERM_ROWS;
+        stage(buf, job.src + row0 * O_FC, O_PERM_ROWS * O_FC, t);
+        __syncthreads();
+        for (int i = t; i < O_PERM_ROWS * O_CELLS; i += THREADS) {
+            const int r = i / O_CELLS, cell = i % O_CELLS;
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = buf[r * O_FC + O_CELLS * c + cell];
+            *reinterpret_cast<V8 *>(static_cast<uint16_t *>(job.dst) + (row0 + r) * O_FC + 8 * cell) = pack8(v);
+        }
+    } else if (job.kind == O_VCONV) {
+        float *dst = static_cast<float *>(job.dst);
+        for (int i = t; i < 8 * 72; i += THREADS) dst[i] = job.src[(i & 7) * 72 + (i >> 3)];
+    } else if (job.kind == O_COPY) {
+        float *dst = static_cast<float *>(job.dst);
+        for (int i = t; i < job.count; i += THREADS) dst[i] = job.src[i];
+    } else if (job.kind == O_BF16) {
+        uint16_t *dst = static_cast<uint16_t *>(job.dst);
+        for (int i = t; i < job.count; i += THREADS) dst[i] = bf16_bits(job.src[i]);
+    } else if (job.kind == O_SCALARS) {
+        float *dst = static_cast<float *>(job.dst);
+        if (t == 0) dst[0] = *job.src;
+        if (t == 1) dst[1] = *job.aux;
+        if (t == 2) dst[2] = *a.job[j + 1].src;
+    }
+}
+
+bool supported_conv(int c_in, int h_in, int pad)
+{
+    return (c_in == 32 && h_in == 8 && pad == 2) || (c_in == 256 && h_in == 10 && (pad == 1 || pad == 0)) || (c_in == 256 && h_in == 8 && pad == 1);
+}
+
+}  // namespace
+
+extern "C" int az_nn_othello_publish_dev(const az_nn_othello_publish_src *src, const az_nn_othello_weights *dst, float *scalars_dev,
+                                         void *stream)
+{
+    if (src == nullptr || dst == nullptr) return 1;
+    if (src->n_body < 2 || src->n_body % 2 != 0 || src->n_convs != src->n_body + 2 || src->n_convs > AZ_NN_OTHELLO_MAX_CONVS) return 1;
+    if (src->n_body != dst->n_body || src->n_convs != dst->n_convs) return 1;
+    if (!(src->bn_eps >= 0.0f) || !(src->bn_eps <= 3.402823466e38f)) return 1;             // NaN, negative, infinite
+    if (!aligned_to(scalars_dev, 4)) return 1;
+
+    OthelloPublishArgs a{};
+    int n = 0, wgs = 0;
+    bool ok = true;
+    auto w = [](const void *p) { return const_cast<void *>(p); };
+    // an entry: a null destination only for the second entry of a job that needs three sources, an `aux` exactly for the
+    // kinds that read one
+    auto add = [&](const void *d, uintptr_t dst_align, const float *s, const float *aux, int32_t kind, int32_t count, int n_wg) {
+        const bool reads_aux = kind == O_EMBED || kind == O_BN || kind == O_SCALARS || (kind == O_SECOND && d != nullptr);
+        ok = ok && aligned_to(s, 4) && (reads_aux ? aligned_to(aux, 4) : aux == nullptr) &&
+             (kind == O_SECOND && d == nullptr ? true : aligned_to(d, dst_align)) && n < O_MAX_JOBS;
+        if (!ok) return;
+        a.job[n] = OJob{w(d), s, aux, kind, count};
+        a.first[n] = wgs;
+        wgs += n_wg;
+        ++n;
+    };
+    // a BatchNorm: 0 none, 1 complete, -1 only some of its four pointers
+    auto have = [](const az_nn_othello_bn_src &b) {
+        const int k = (b.weight != nullptr) + (b.bias != nullptr) + (b.mean != nullptr) + (b.var != nullptr);
+        return k == 0 ? 0 : k == 4 ? 1 : -1;
+    };
+    auto bn = [&](const az_nn_othello_bn_src &b, const float *scale, const float *shift, int channels, int pad16) {
+        ok = ok && have(b) == 1 && aligned_to(b.bias, 4) && aligned_to(b.mean, 4);
+        if (!ok) return;
+        add(scale, 4, b.weight, b.var, O_BN, channels | pad16 << 16, 1);
+        add(shift, 4, b.bias, b.mean, O_SECOND, 0, 0);
+    };
+    auto copy = [&](const float *d, const float *s, int count) {
+        if (d != nullptr && d == s) { ok = ok && aligned_to(s, 4); return; }           // an alias of the source: it already holds the value
+        const uintptr_t x = reinterpret_cast<uintptr_t>(d), y = reinterpret_cast<uintptr_t>(s), bytes = 4u * static_cast<uintptr_t>(count);
+        ok = ok && d != nullptr && s != nullptr && (x + bytes <= y || y + bytes <= x);
+        add(d, 4, s, nullptr, O_COPY, count, 1);
+    };
+    const az_nn_othello_heads_weights &h = dst->heads;
+
+    add(dst->embed_table, 16, src->pos_emb, src->piece_emb, O_EMBED, 0, 1);
+    add(nullptr, 1, src->legal_emb, nullptr, O_SECOND, 0, 0);
+    for (int i = 0; ok && i < src->n_convs; ++i) {
+        const az_nn_othello_conv_layer &l = dst->conv[i];
+        ok = ok && supported_conv(l.c_in, l.h_in, l.pad);
+        if (!ok) break;
+        add(l.w_packed, 16, src->conv_weight[i], nullptr, O_CONV, l.c_in | 16 << 16 | 16 << 24, 16 * (l.c_in / 32));
+        const int pre = have(src->conv_pre[i]), post = have(src->conv_post[i]);
+        ok = ok && pre >= 0 && post >= 0 && (l.pre_scale != nullptr) == (l.pre_shift != nullptr) && (l.pre_scale != nullptr) == (pre == 1);
+        if (ok && pre == 1) bn(src->conv_pre[i], l.pre_scale, l.pre_shift, l.c_in, 0);
+        if (ok && post == 1) bn(src->conv_post[i], l.post_scale, l.post_shift, O_CH, 0);
+    }
+    add(dst->dual_w16, 16, src->dual_weight, nullptr, O_CONV, O_CH | 8 << 16 | 1 << 24, O_CH / 32);
+    bn(src->dual_bn, dst->dual_scale16, dst->dual_shift16, 8, 1);
+    add(h.board_w, 2, src->board_weight, nullptr, O_BF16, O_CH, 1);
+    copy(h.pass_norm_w, src->pass_norm_weight, O_CH);
+    copy(h.pass_fc_w, src->pass_fc_weight, O_CH);
+    add(h.v_conv_w, 4, src->v_conv_weight, nullptr, O_VCONV, 8 * 72, 1);
+    bn(src->v_bn, h.v_bn_s, h.v_bn_b, 8, 0);
+    copy(h.v_fc_w, src->v_fc_weight, 3 * 72);
+    copy(h.v_fc_b, src->v_fc_bias, 3);
+    add(h.a_fc_wt, 16, src->a_fc_weight, nullptr, O_TRANS, O_FC * O_FC, (O_FC / O_TILE) * (O_FC / O_TILE));
+    if (h.a_fc_w16 != nullptr) add(h.a_fc_w16, 16, src->a_fc_weight, nullptr, O_PERM16, O_FC * O_FC, O_FC / O_PERM_ROWS);
+    copy(h.a_fc_b, src->a_fc_bias, O_FC);
+    copy(h.a_norm_w, src->a_norm_weight, O_FC);
+    copy(h.a_out_w, src->a_out_weight, O_FC);
+    add(scalars_dev, 4, src->board_bias, src->pass_fc_bias, O_SCALARS, 3, 1);
+    add(nullptr, 1, src->a_out_bias, nullptr, O_SECOND, 0, 0);
+    if (!ok) return 1;
+    a.first[n] = wgs;
+    a.n_jobs = n;
+    a.bn_eps = src->bn_eps;
+    hipLaunchKernelGGL(k_publish_othello, dim3(static_cast<unsigned>(wgs)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}

@@ -333,6 +333,12 @@ PROTOTYPES = (
     ("az_nn_othello_embed", i32, [P(Positions), vp, vp, vp, i64, vp, vp, vp]),
     ("az_nn_othello_heads", i32, [vp, vp, P(_HeadsW), vp, vp, vp, i64, vp, vp, vp]),
     ("az_nn_model_create_othello", i32, [P(_OthelloW), P(vp)]),
+    # az_nn_othello_publish_src travels as plain c_void_p, as az_nn_publish_src does: its mirror lives in src/publish.py
+    # and tests/test_publish_othello_cpu.py holds its layout to the header
+    ("az_nn_othello_publish_dev", i32, [vp, P(_OthelloW), vp, vp]),
+    ("az_nn_model_set_othello_head_biases", i32, [vp, f32, f32, f32]),
+    ("az_nn_model_othello_head_biases", i32, [vp, P(f32 * 3)]),
+    ("az_nn_model_publish_othello", i32, [vp, vp, vp, vp]),
     # include/az_train.h
     ("az_train_loss_workspace_bytes", i64, [i32, i64]),
     ("az_train_dev_loss", i32, [i32, P(ReplayBatchC), P(TrainHeadsC), i64, P(TrainLossConfigC), P(TrainLossOutC), vp]),

@@ -152,6 +152,12 @@ class FastOthelloNet(torch.nn.Module):
         self.__dict__["_model"] = handle
         return handle
 
+    def publish_from(self, net=None):
+        """This twin's module's current parameters and BatchNorm buffers into its existing arrays, in place, as ONE launch
+        (src/publish.py `publish_othello`): the native model and every captured pointer stay.  `net`: `self.net` or None."""
+        from src.publish import publish_othello
+        return publish_othello(self, net)
+
     def __del__(self):
         try:
             h = self.__dict__.get("_model")

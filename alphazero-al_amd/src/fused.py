@@ -119,17 +119,20 @@ class FusedSearch:
                 self.refresh_table()
 
     def publish_weights(self):
-        """The module's current parameters into the evaluator.  With a Connect4 twin already there and the module still
+        """The module's current parameters into the evaluator.  With a Connect4 twin, or an Othello twin of this very module
+        (BatchNorm buffers included), already there and the module still
         publishable into it (src/publish.py: same shapes, float32 on the twin's GPU): ONE launch into the twin's existing
         buffers - the twin, its native model and the captured graphs stay; the graphs go only if one of the three head
         biases changed in bits, because those are kernel arguments inside a capture - and "published".  Otherwise what
         `_sync_fast_net()` does, and "rebuilt".  Opt-in: `_sync_fast_net` never calls it."""
         from src.fast_net import FastConnect4Net
+        from src.fast_othello import FastOthelloNet
         from src import publish as PB
         fast = self.fast
-        if self.use_fast and isinstance(fast, FastConnect4Net) and fast.hip and not hasattr(self.net, "predict_device"):
+        othello = isinstance(fast, FastOthelloNet) and self.game_name == "Othello" and fast.net is self.net
+        if self.use_fast and not hasattr(self.net, "predict_device") and (othello or (isinstance(fast, FastConnect4Net) and fast.hip)):
             try:
-                PB.source_struct(self.net, fast)
+                PB.othello_source_struct(fast) if othello else PB.source_struct(self.net, fast)
             except ValueError:
                 fast = None
         else:
@@ -138,8 +141,15 @@ class FusedSearch:
             self._sync_fast_net()
             return "rebuilt"
         bits = lambda b: struct.pack("<3f", *b)      # noqa: E731
-        before = bits((fast._heads_w.p_gate_b, fast._heads_w.p_out_b, fast._heads_w.d_aux_b))
-        after = bits(PB.publish(fast, self.net))
+        if othello:
+            # the Othello twin: the same contract over its own three by-value biases (board_out, pass_fc, aux_out[5])
+            fast.native_model()                      # created on demand: `_model_w` is what it was built from
+            hw = fast._model_w.heads
+            before = bits((hw.board_b, hw.pass_fc_b, hw.a_out_b))
+            after = bits(PB.publish_othello(fast))
+        else:
+            before = bits((fast._heads_w.p_gate_b, fast._heads_w.p_out_b, fast._heads_w.d_aux_b))
+            after = bits(PB.publish(fast, self.net))
         self._fast_version = (tuple(p._version for p in self.net.parameters()) + tuple(p.data_ptr() for p in self.net.parameters()) +
                               tuple(b._version for b in self.net.buffers()))
         if after != before:

@@ -1,5 +1,6 @@
-"""Trained Connect4 weights into a live evaluator, in place, as ONE launch (az_nn_publish_dev / az_nn_model_publish in
-include/az_nn.h, csrc/publish_kernels.hip).
+"""Trained weights into a live evaluator, in place, as ONE launch: Connect4 (az_nn_publish_dev / az_nn_model_publish in
+include/az_nn.h, csrc/publish_kernels.hip) and, in the second half of this file, Othello (az_nn_othello_publish_dev /
+az_nn_model_publish_othello; `publish_othello`).
 
 `FastConnect4Net.from_module(net)` builds a NEW inference twin from a module: about a hundred small torch operations, every
 buffer allocated again, four device reads, a new az_nn_model - so every captured graph goes.  `publish(fast, source)`
@@ -157,4 +158,172 @@ def publish(fast, source):
     hw = fast._heads_w
     hw.p_gate_b, hw.p_out_b, hw.d_aux_b = biases
     fast.p_gate_b_host = biases[0]
+    return biases
+
+
+# ---------------------------------------------------------------------------------------------------------------- Othello
+#
+# `FastOthelloNet(net)` packs eleven convolution weights through permute chains, folds a dozen BatchNorms, transposes two
+# 512 x 512 matrices and reads three biases back; `native_model()` then makes a new az_nn_model.  `publish_othello(fast)`
+# writes the same function of `fast.net`'s parameters AND BatchNorm buffers into the arrays the twin and its model already
+# have.  The BatchNorm affines are computed in correctly rounded float32 steps (az_nn.h), which torch's `sqrt` is not
+# everywhere: they agree with `_bn_affine` within a few ulp, not in bytes.
+
+O_CH, O_FC, OTHELLO_MAX_CONVS = 256, 512, 16
+BN_FIELDS = (("weight", "weight"), ("bias", "bias"), ("mean", "running_mean"), ("var", "running_var"))
+# (field of az_nn_othello_publish_src, state dict name, shape) of everything that is not a convolution of the chain
+O_TENSORS = (("piece_emb", "piece_emb.weight", (2, EMB)), ("pos_emb", "pos_emb.weight", (10, EMB)), ("legal_emb", "legal_emb.weight", (2, EMB)),
+             ("dual_weight", "dual_head.stem.0.weight", (8, O_CH, 3, 3)),
+             ("board_weight", "policy_head.board_out.weight", (1, O_CH, 1, 1)), ("board_bias", "policy_head.board_out.bias", (1,)),
+             ("pass_norm_weight", "policy_head.pass_norm.weight", (O_CH,)), ("pass_fc_weight", "policy_head.pass_fc.weight", (1, O_CH)),
+             ("pass_fc_bias", "policy_head.pass_fc.bias", (1,)), ("v_conv_weight", "dual_head.value_out.0.weight", (8, 8, 3, 3)),
+             ("v_fc_weight", "dual_head.value_out.5.weight", (3, 72)), ("v_fc_bias", "dual_head.value_out.5.bias", (3,)),
+             ("a_fc_weight", "dual_head.aux_out.1.weight", (O_FC, O_FC)), ("a_fc_bias", "dual_head.aux_out.1.bias", (O_FC,)),
+             ("a_norm_weight", "dual_head.aux_out.2.weight", (O_FC,)), ("a_out_weight", "dual_head.aux_out.5.weight", (1, O_FC)),
+             ("a_out_bias", "dual_head.aux_out.5.bias", (1,)))
+O_NORMS = (("dual_bn", "dual_head.stem.1", 8), ("v_bn", "dual_head.value_out.1", 8))
+O_BIASES = ("policy_head.board_out.bias", "policy_head.pass_fc.bias", "dual_head.aux_out.5.bias")
+
+
+class OthelloBnSrcC(C.Structure):
+    """az_nn_othello_bn_src (include/az_nn.h)."""
+    _fields_ = [(n, C.c_void_p) for n, _ in BN_FIELDS]
+
+
+class OthelloPublishSrcC(C.Structure):
+    """az_nn_othello_publish_src (include/az_nn.h).  Passed by address to a c_void_p parameter, as PublishSrcC is;
+    tests/test_publish_othello_cpu.py holds its layout to the header."""
+    _fields_ = ([(n, C.c_void_p) for n in ("piece_emb", "pos_emb", "legal_emb")] + [("n_body", C.c_int32), ("n_convs", C.c_int32), ("bn_eps", C.c_float)] +
+                [("conv_weight", C.c_void_p * OTHELLO_MAX_CONVS), ("conv_pre", OthelloBnSrcC * OTHELLO_MAX_CONVS),
+                 ("conv_post", OthelloBnSrcC * OTHELLO_MAX_CONVS), ("dual_weight", C.c_void_p), ("dual_bn", OthelloBnSrcC)] +
+                [(n, C.c_void_p) for n in ("board_weight", "board_bias", "pass_norm_weight", "pass_fc_weight", "pass_fc_bias", "v_conv_weight")] +
+                [("v_bn", OthelloBnSrcC)] +
+                [(n, C.c_void_p) for n in ("v_fc_weight", "v_fc_bias", "a_fc_weight", "a_fc_bias", "a_norm_weight", "a_out_weight", "a_out_bias")])
+
+
+# a table of their own: tests/test_publish_cpu.py fixes `MIRRORS` above at its one entry
+OTHELLO_MIRRORS = {"az_nn_othello_bn_src": OthelloBnSrcC, "az_nn_othello_publish_src": OthelloPublishSrcC}
+
+
+def othello_orbit_map():
+    """The reference's 64-entry orbit table in closed form, as the kernel has it compiled in: fold the board onto one
+    octant, number the triangle a <= b <= 3 row by row."""
+    out = []
+    for cell in range(64):
+        fr, fc = min(cell // 8, 7 - cell // 8), min(cell % 8, 7 - cell % 8)
+        a, b = min(fr, fc), max(fr, fc)
+        out.append((0, 4, 7, 9)[a] + b - a)
+    return out
+
+
+def othello_conv_names(n_blocks):
+    """[(convolution weight, BatchNorm in front or None, BatchNorm behind or None, c_in)] in the order of
+    az_nn_othello_weights.conv, as state dict prefixes."""
+    out = [("stem.0.weight", None, "stem.1", EMB)]
+    for k in range(n_blocks):
+        out += [("stem.%d.conv1.weight" % (3 + k), "stem.%d.norm1" % (3 + k), None, O_CH),
+                ("stem.%d.conv2.weight" % (3 + k), "stem.%d.norm2" % (3 + k), None, O_CH)]
+    out.append(("stem.%d.weight" % (3 + n_blocks), None, "stem.%d" % (4 + n_blocks), O_CH))
+    return out + [("policy_head.stem.0.weight", None, "policy_head.stem.1", O_CH), ("policy_head.stem.4.weight", None, "policy_head.stem.5", O_CH)]
+
+
+def othello_source_struct(fast):
+    """`fast.net`'s tensors as an az_nn_othello_publish_src after every precondition -> (struct, the tensors it points at).
+    ValueError with the reason otherwise."""
+    net = fast.net
+    sd = net.state_dict()
+    n_blocks = 0
+    while "stem.%d.conv1.weight" % (3 + n_blocks) in sd:
+        n_blocks += 1
+    if 2 * n_blocks + 2 != fast.n_body or fast.n_body + 2 > OTHELLO_MAX_CONVS:
+        raise ValueError("publish_othello: the module has %d residual blocks, the twin's body %d convolutions (2 per block and 2)"
+                         % (n_blocks, fast.n_body))
+    device = fast.embed_table.device
+    keep = {}
+
+    def tensor(name, shape):
+        t = sd.get(name)
+        if t is None:
+            raise ValueError("publish_othello: the module has no tensor %r (the reference's Othello parameter names are needed)" % name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("publish_othello: %s has shape %s, the evaluator's layout needs %s" % (name, tuple(t.shape), tuple(shape)))
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("publish_othello: %s must be a contiguous float32 CUDA tensor" % name)
+        if t.device != device:
+            raise ValueError("publish_othello: %s is on %s, the twin on %s" % (name, t.device, device))
+        keep[name] = t
+        return t.data_ptr()
+
+    def norm(into, prefix, channels):
+        for field, key in BN_FIELDS:
+            setattr(into, field, tensor("%s.%s" % (prefix, key), (channels,)))
+
+    src = OthelloPublishSrcC()
+    src.n_body, src.n_convs = fast.n_body, fast.n_body + 2
+    for field, name, shape in O_TENSORS:
+        setattr(src, field, tensor(name, shape))
+    for i, (weight, pre, post, c_in) in enumerate(othello_conv_names(n_blocks)):
+        src.conv_weight[i] = tensor(weight, (O_CH, c_in, 3, 3))
+        if pre is not None:
+            norm(src.conv_pre[i], pre, c_in)
+        if post is not None:
+            norm(src.conv_post[i], post, O_CH)
+    for field, prefix, channels in O_NORMS:
+        norm(getattr(src, field), prefix, channels)
+    # one epsilon for every BatchNorm: it travels as one float
+    eps = None
+    for name, m in net.named_modules():
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            if eps is None:
+                eps = float(m.eps)
+            elif float(m.eps) != eps:
+                raise ValueError("publish_othello: %s has eps %g, the BatchNorms before it %g (one common eps can be published)" % (name, m.eps, eps))
+    if eps is None:
+        raise ValueError("publish_othello: the module has no BatchNorm")
+    src.bn_eps = eps
+    om = sd.get("orbit_map")
+    if om is None or om.numel() != 64:
+        raise ValueError("publish_othello: the module has no orbit_map of 64 cells")
+    # a constant of the game: compared once per tensor version, not per call (the comparison reads the device)
+    seen = (om.data_ptr(), om._version)
+    if fast.__dict__.get("_publish_orbit_ok") != seen:
+        if om.reshape(-1).tolist() != othello_orbit_map():
+            raise ValueError("publish_othello: the module's orbit_map is not the reference's table, which the kernel has compiled in")
+        fast.__dict__["_publish_orbit_ok"] = seen
+    return src, keep
+
+
+def publish_othello(fast, source=None):
+    """Writes the evaluator's layout of `fast.net`'s parameters and BatchNorm buffers into `fast`'s existing arrays on
+    torch's current stream and returns the three head biases (board_out, pass_fc, aux_out[5]) as the device holds them.
+
+    fast: a `FastOthelloNet`; its native model is created on demand.  source: `fast.net` itself, or None.  The twin's torch
+    route reads the heads straight from `fast.net` and its native model aliases that module's parameters, so another
+    module would leave the twin half old: `fast.net.load_state_dict(other.state_dict())` first.
+
+    Afterwards `fast.board_b` and the three floats of `fast._model_w.heads` hold the new values.  Waits for the stream once."""
+    if not hasattr(fast, "native_model") or not hasattr(fast, "embed_table") or not hasattr(fast, "n_body"):
+        raise ValueError("publish_othello: needs a FastOthelloNet")
+    if source is not None and source is not fast.net:
+        raise ValueError("publish_othello: the source must be the twin's own module (fast.net): its torch route and its native model "
+                         "read that module's parameters, so load_state_dict into fast.net first")
+    src, keep = othello_source_struct(fast)
+    model = fast.native_model()
+    device = fast.embed_table.device
+    slot = fast.__dict__.get("publish_slot")
+    if slot is None:
+        slot = fast.__dict__["publish_slot"] = torch.zeros(4, dtype=torch.float32, device=device)
+    L = lib()
+    with torch.cuda.device(device):
+        rc = L.az_nn_model_publish_othello(model, C.byref(src), slot.data_ptr(), _stream())
+    if rc != 0:
+        raise ValueError("publish_othello: the library refused the call (%d): az_nn_model_publish_othello" % rc)
+    del keep
+    out = (C.c_float * 3)()
+    if L.az_nn_model_othello_head_biases(model, C.byref(out)) != 0:
+        raise RuntimeError("az_nn_model_othello_head_biases failed")
+    biases = (float(out[0]), float(out[1]), float(out[2]))
+    fast.board_b = biases[0]
+    hw = fast._model_w.heads
+    hw.board_b, hw.pass_fc_b, hw.a_out_b = biases
     return biases

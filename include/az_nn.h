@@ -207,7 +207,8 @@ int az_nn_model_profile_read_kernels(double out_ms[4], int64_t out_launches[4]);
 /* Publishing trained weights into a live model (alphazero-al_amd/csrc/publish_kernels.hip, k_publish): the evaluator's
  * arrays are a pure function of the network's float32 parameters, and az_nn_publish_dev computes that function in ONE
  * launch, writing the arrays an az_nn_model_weights names IN PLACE - the model handle, the twin's buffers and every
- * pointer inside a captured graph stay valid.  Connect4 network only.
+ * pointer inside a captured graph stay valid.  This is the Connect4 network's; the Othello network's is
+ * az_nn_othello_publish_dev at the end of this header.
  * Sources: the float32 tensors of the reference's Connect4 state dict in DEVICE memory, contiguous, 4-byte aligned, with
  * the shapes of AZ_LEARN_ROLE_* (az_train.h).  "bf16" = float32 rounded to nearest-even (torch's .to(torch.bfloat16)
  * for finite values and infinities).  Every destination byte is written.
@@ -256,12 +257,12 @@ _Static_assert(sizeof(az_nn_publish_src) == AZ_NN_PUBLISH_SRC_BYTES, "az_nn_publ
 int az_nn_publish_dev(const az_nn_publish_src *src, const az_nn_model_weights *dst, float *scalars_dev, void *stream);
 /* The three biases that travel to the evaluator kernels BY VALUE inside az_nn_heads_weights, on the host: set them / read
  * them back (out: p_gate_b, p_out_b, d_aux_b).  aux_scale is never touched.  Connect4 network kind only, else 1 (as for
- * a null argument).  A forward enqueued afterwards carries the new values; one captured before carries the old ones. */
+ * a null argument; an Othello model has az_nn_model_set_othello_head_biases below).  A forward enqueued afterwards carries the new values; one captured before carries the old ones. */
 int az_nn_model_set_head_biases(az_nn_model *m, float p_gate_b, float p_out_b, float d_aux_b);
 int az_nn_model_head_biases(const az_nn_model *m, float out[3]);
 /* az_nn_publish_dev on the model's own arrays, then the 12 bytes of scalars_dev to the host, a wait for `stream`, and
  * az_nn_model_set_head_biases with them.  Returns 1 with nothing enqueued as az_nn_publish_dev does, for a model of
- * another kind, and for a stream that is capturing.
+ * another kind (an Othello model too: az_nn_model_publish_othello below), and for a stream that is capturing.
  * It WAITS once and must not be captured: the three biases are kernel arguments, so the host has to see them (reading
  * them on the device instead would change the evaluator kernels).
  * No forward of this model may be in flight on another stream, or be enqueued from another thread, during the call;
@@ -373,6 +374,90 @@ typedef struct az_nn_othello_weights {
 } az_nn_othello_weights;
 #define AZ_NN_KIND_OTHELLO_CNN 3
 int az_nn_model_create_othello(const az_nn_othello_weights *w, az_nn_model **out);
+
+/* Publishing trained weights into a live Othello model (alphazero-al_amd/csrc/publish_kernels.hip, k_publish_othello): what
+ * az_nn_publish_dev above is for the Connect4 network.  The arrays of an az_nn_othello_weights are a pure function of the
+ * network's float32 parameters and BatchNorm buffers, and az_nn_othello_publish_dev computes that function in ONE launch,
+ * writing the arrays IN PLACE.
+ * Sources: float32, DEVICE memory, contiguous, 4-byte aligned, the reference's Othello state dict (Othello/Network.py):
+ *   conv_weight[i]  [256][c_in][3][3], in the order of az_nn_othello_weights.conv;  conv_pre[i] / conv_post[i]: the
+ *                   BatchNorm in front of / behind convolution i as {weight, bias, running mean, running var}, c_in / 256
+ *                   floats each; all four NULL = none (one to three NULL: an error)
+ *   the rest        as commented in the struct
+ * The destination is an az_nn_othello_weights whose pointers name WRITABLE device memory; c_in, h_in, pad and residual are
+ * read from IT, not from the source.  "bf16" = float32 rounded to nearest-even by integer arithmetic (nn_common.h pack2).
+ *   embed_table[4 cell + kind][c] = bf16(pos_emb[orbit(cell)][c] + K[kind][c]), ONE float32 add; K = piece_emb[0],
+ *       piece_emb[1], legal_emb[1], legal_emb[0] in that order (own stone, opponent stone, empty + legal, empty + illegal);
+ *       orbit(cell): with f(i) = min(i, 7 - i), a = min(f(row), f(col)), b = max(f(row), f(col)), the entry
+ *       {0, 4, 7, 9}[a] + b - a - the 64 constants of the reference's table (Othello/Network.py _ORBIT_MAP)
+ *   conv[i].w_packed[tap][kc][tile][lane = 16 g + tl][j] = bf16(W[16 tile + tl][32 kc + 8 g + j][tap]),  tap 0 .. 8,
+ *       kc 0 .. c_in / 32 - 1, tile 0 .. 15, g 0 .. 3, tl 0 .. 15, j 0 .. 7  (fast_othello.pack_conv_weight)
+ *   dual_w16        the same order with ONE tile from dual_weight [8][256][3][3]; rows tl = 8 .. 15 are +0
+ *   a BatchNorm as an affine:  a = var + bn_eps;  r = sqrt(a);  scale = weight / r;  shift = bias - mean * scale,  each
+ *       step ONE correctly rounded float32 operation, no fused multiply-add.  conv_pre[i] -> pre_scale / pre_shift,
+ *       conv_post[i] -> post_scale / post_shift, v_bn -> heads.v_bn_s / v_bn_b, dual_bn -> entries 0 .. 7 of dual_scale16 /
+ *       dual_shift16, whose entries 8 .. 15 are 1.0f / 0.0f.  A layer whose destination has pre_scale must have conv_pre[i]
+ *       and the reverse, else 1.  A layer whose conv_post[i] is all NULL leaves the destination's post_* arrays UNWRITTEN
+ *       (the caller's shared ones / zeros)
+ *   heads.board_w = bf16(board_weight);  heads.v_conv_w[ci * 9 + k][co] = v_conv_weight[co][ci][k];
+ *   heads.a_fc_wt[in][out] = a_fc_weight[out][in];  heads.a_fc_w16[out][8 cell + c] = bf16(a_fc_weight[out][64 c + cell]),
+ *       only where the destination has the pointer
+ *   plain float32 copies: heads.pass_norm_w, pass_fc_w, v_fc_w, v_fc_b, a_fc_b, a_norm_w, a_out_w
+ *   scalars_dev[0 .. 2] = board_bias, pass_fc_bias, a_out_bias (the slot's fourth float is not written); aux_to_score and eps
+ *       of the heads are never touched
+ * Every destination byte named above is written by exactly one lane; every job reads sources only, so no workgroup waits
+ * for another, and two calls on the same inputs give the same bytes. */
+typedef struct az_nn_othello_bn_src {
+    const float *weight, *bias, *mean, *var;
+} az_nn_othello_bn_src;
+typedef struct az_nn_othello_publish_src {
+    const float *piece_emb, *pos_emb, *legal_emb;                  /* [2][32], [10][32], [2][32] */
+    int32_t n_body, n_convs;                                       /* as az_nn_othello_weights */
+    float bn_eps;                                                  /* the BatchNorms' common epsilon */
+    const float *conv_weight[AZ_NN_OTHELLO_MAX_CONVS];
+    az_nn_othello_bn_src conv_pre[AZ_NN_OTHELLO_MAX_CONVS], conv_post[AZ_NN_OTHELLO_MAX_CONVS];
+    const float *dual_weight;                                      /* dual_head.stem.0.weight [8][256][3][3] */
+    az_nn_othello_bn_src dual_bn;                                  /* dual_head.stem.1, 8 */
+    const float *board_weight, *board_bias;                        /* policy_head.board_out: [256], [1] */
+    const float *pass_norm_weight, *pass_fc_weight, *pass_fc_bias; /* policy_head.pass_norm, pass_fc: [256], [256], [1] */
+    const float *v_conv_weight;                                    /* dual_head.value_out.0.weight [8][8][3][3] */
+    az_nn_othello_bn_src v_bn;                                     /* dual_head.value_out.1, 8 */
+    const float *v_fc_weight, *v_fc_bias;                          /* dual_head.value_out.5: [3][72], [3] */
+    const float *a_fc_weight, *a_fc_bias;                          /* dual_head.aux_out.1: [512][512], [512] */
+    const float *a_norm_weight, *a_out_weight, *a_out_bias;        /* dual_head.aux_out.2, aux_out.5: [512], [512], [1] */
+} az_nn_othello_publish_src;
+#define AZ_NN_OTHELLO_PUBLISH_SRC_BYTES 1368
+#ifdef __cplusplus
+static_assert(sizeof(az_nn_othello_publish_src) == AZ_NN_OTHELLO_PUBLISH_SRC_BYTES, "az_nn_othello_publish_src");
+#else
+_Static_assert(sizeof(az_nn_othello_publish_src) == AZ_NN_OTHELLO_PUBLISH_SRC_BYTES, "az_nn_othello_publish_src");
+#endif
+/* The one launch on `stream` and nothing else: it does not wait, allocate or copy, so it may be captured.  It WRITES
+ * through dst's pointers (const in the struct because the evaluator only reads them).  dst's by-value floats are not read.
+ * Returns 1 with nothing enqueued and nothing written: a null struct or scalars_dev; a null required pointer (every source
+ * but the BatchNorms of layers that have none, every destination but pre_* / post_* of such layers and heads.a_fc_w16);
+ * n_body / n_convs that az_nn_model_create_othello refuses, or different between src and dst; a (c_in, h_in, pad) that
+ * az_nn_othello_conv does not support; bn_eps not finite or negative; a BatchNorm with only some of its four pointers, or
+ * whose presence differs from the destination's (above); a pointer not aligned: 16 bytes for w_packed, dual_w16,
+ * embed_table, a_fc_w16 and a_fc_wt, 4 bytes for float arrays and every source, 2 bytes for board_w.  2: the launch was
+ * refused.
+ * A plain float32 copy whose destination IS its source (the same address) gets no job - a twin hands the model such
+ * aliases of the module's parameters; any other overlap of a copy's two ranges returns 1. */
+int az_nn_othello_publish_dev(const az_nn_othello_publish_src *src, const az_nn_othello_weights *dst, float *scalars_dev,
+                              void *stream);
+/* The three biases that travel to the Othello heads kernel BY VALUE inside az_nn_othello_heads_weights, on the host: set
+ * them / read them back (out: board_b, pass_fc_b, a_out_b).  aux_to_score and eps are never touched.  Kind
+ * AZ_NN_KIND_OTHELLO_CNN only, else 1 (as for a null argument).  A forward enqueued afterwards carries the new values; one
+ * captured before carries the old ones. */
+int az_nn_model_set_othello_head_biases(az_nn_model *m, float board_b, float pass_fc_b, float a_out_b);
+int az_nn_model_othello_head_biases(const az_nn_model *m, float out[3]);
+/* az_nn_othello_publish_dev on the model's own arrays, then the 12 bytes of scalars_dev to the host, a wait for `stream`,
+ * and az_nn_model_set_othello_head_biases with them.  Returns 1 with nothing enqueued as az_nn_othello_publish_dev does,
+ * for a model of another kind, and for a stream that is capturing.
+ * It WAITS once and must not be captured: the three biases are kernel arguments, so the host has to see them.
+ * No forward of this model may be in flight on another stream, or be enqueued from another thread, during the call;
+ * forwards enqueued on `stream` afterwards see the new weights. */
+int az_nn_model_publish_othello(az_nn_model *m, const az_nn_othello_publish_src *src, float *scalars_dev, void *stream);
 
 #ifdef __cplusplus
 }
